@@ -8,7 +8,7 @@ One "step" = one pass of the propose-score hot path over one hypothesis batch:
     gather    (N_gpus > 1) RCCL all-gather of the per-model int32 scores, enqueued on the engine's stream by the
               native transport (multi-h_amd/host/rccl_transport.cpp: ncclAllGather; no Python in the exchange)
     select    best model on every rank, identical everywhere (the engine's own arg-max kernel, csrc/select.hip)
-Two forms of the same step are timed in every run, EXACTLY K steps each, nothing cached or skipped in either:
+Two forms of the same step (both with --full, the headline's alone otherwise), EXACTLY K steps each, nothing cached or skipped:
   sequential  propose, sweep, arg-max one after the other on one stream — the headline at ONE GPU;
   pipelined   the DLT solve of batch i+2 on the engine's second, high-priority stream beside the residual sweep of
               batch i (mh_prefetch_dlt4 / mh_adopt_prefetched) — the headline at SEVERAL GPUs, where a rank's step is 1 ms.
@@ -22,8 +22,8 @@ R is 40 GB of the 288 GB).  Inputs are resident in HBM before the timed region.
 Multi-GPU (`--gpus N`): the headline is BASELINE configs[3] — ONE batch of 100 000
 hypotheses split across the ranks (`"scaling": "strong"`: the total work per step is the
 same for every N), correspondences replicated, the only collective the RCCL all-gather of
-the int32 scores.  The same run also times the weak-scaling variant (every rank owns its
-own 100 000-hypothesis batch, disjoint RNG counters) and reports it as `"weak_scaling"`.
+the int32 scores.  With --full the same run also times the weak-scaling variant (every rank
+owns its own 100 000-hypothesis batch, disjoint RNG counters) and reports it as `"weak_scaling"`.
 `--scaling weak` swaps the two.
 
 Launching: the driver starts one process per GPU with torch.distributed.run.  Run by hand
@@ -32,7 +32,22 @@ ranks itself — before torch or the GPU is touched — and exits non-zero if an
 
 Prints ONE JSON line (rank 0) with the contract's fields plus `roofline` for
 the dominant kernel (k_residual, HBM-write bound) and `cpu_baseline` (the oracle
-score loop timed on this box's host cores, N=1 only).
+score loop timed on this box's host cores, N=1 and --full only).
+
+A plain run does only what the headline needs: it sets up (one untimed step sizes the engine's buffers), runs the
+`--warmup` steps, times exactly `--steps` steps of the headline form (the sequential form at one GPU, the pipelined
+form at several), writes the outputs if asked to and prints the line.  Everything that takes runs of its own moves behind `--full`: the other form,
+the other scaling mode and the kernel pass of several ranks, the one-GPU rehearsal of the strong split's shards, the
+side kernels (store-free score, s = 4 cost matrix, symmetric transfer), the memset reference of the roofline, the
+CPU baseline with the sustained rate beside it, the labeling and the whole-loop context.
+
+`--dump-outputs DIR` writes what the headline path handed its caller in its LAST timed step, as float64 .npy files
+(rank 0's shard at several GPUs): scores.npy (the inlier count of every hypothesis of the batch, gathered over the
+ranks), best.npy (index in the batch and count of the best-supported model), models.npy (M x 9 homographies),
+samples.npy (M x 4 correspondence indices of the DLT samples) and a fixed, seeded sample of the residual matrix
+(residuals_sample.npy, at the flat model-major positions in residuals_index.npy).  Batches of more than 262 144
+hypotheses are sampled the same way (their positions in model_index.npy / scores_index.npy).  With the same
+arguments every input is the same from run to run, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -61,14 +76,33 @@ def parse():
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
                     help="headline mode for N > 1: strong = one batch of --models split over the ranks (BASELINE "
-                         "configs[3]); weak = --models per rank.  The other mode is timed too and reported alongside.")
+                         "configs[3]); weak = --models per rank.  With --full the other mode is timed too and reported alongside.")
     ap.add_argument("--cpu-sample", type=int, default=150000, help="hypotheses in the CPU baseline sample (about 13 s on one core)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-mode", action="store_true", help="N > 1: time the headline scaling mode only (a rehearsal of 8 ranks on ONE GPU "
                     "cannot hold eight weak-scaling batches of 40 GB each)")
     ap.add_argument("--no-rehearsal", action="store_true", help="skip the one-GPU rehearsal of the strong split's shards (keeps a "
                     "profiler's per-kernel statistics to the full-size launches)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline (other form and scaling mode, "
+                    "rehearsal, side kernels, memset reference, CPU baseline, labeling, whole loop); the --no-* options apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the headline path's outputs of its last timed step "
+                    "to DIR/<name>.npy (float64)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_MAX_MODELS = 262144        # per-model arrays of larger batches: a fixed, seeded sample of this many models
+DUMP_RESIDUALS = 1 << 20        # residual-matrix entries in the dump (8 MB, plus their positions)
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (the integers here are exact in it)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 class _DevView:
@@ -392,10 +426,33 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    def capture_outputs(M: int) -> dict:
+        """After the timed steps, before anything else touches the engine: this rank's models and samples of the last step
+        and a seeded sample of its resident residual matrix (model-major, M x N doubles)."""
+        import numpy as np
+        rng = np.random.default_rng([a.seed, M, N])
+        out = {}
+        H, idx = eng.get_models(), eng.get_samples()
+        if M > DUMP_MAX_MODELS:
+            pick = np.sort(rng.choice(M, DUMP_MAX_MODELS, replace=False))
+            H, idx = H[pick], idx[pick]
+            out["model_index"] = pick
+        out["models"], out["samples"] = H, idx
+        if M > 0:
+            ptr_R, bytes_R = eng.device_buffer(2)            # MH_BUF_RESIDUALS
+            if not ptr_R or bytes_R < 8 * M * N:
+                raise SystemExit(f"bench.py: the residual matrix holds {bytes_R} bytes, {8 * M * N} expected")
+            pos = np.sort(rng.integers(0, M * N, size=min(DUMP_RESIDUALS, M * N), dtype=np.int64))
+            t_R = torch.as_tensor(_DevView(ptr_R, M * N, "<f8"), device=dev)
+            out["residuals_sample"] = t_R[torch.from_numpy(pos).to(dev)].cpu().numpy()
+            out["residuals_index"] = pos
+        return out
+
     def run_mode(scaling: str, steps: int, warmup: int, pipelined: bool = False, profile: bool = True, models: int = 0,
-                 mark_steps: bool = True):
+                 mark_steps: bool = True, capture: bool = False):
         """`warmup` untimed steps, then exactly `steps` timed ones between two fences; max over ranks.
-        models: batch size instead of --models (the one-GPU rehearsal of a strong split's per-rank shard)."""
+        models: batch size instead of --models (the one-GPU rehearsal of a strong split's per-rank shard).
+        capture: also return the last timed step's outputs (--dump-outputs) as "outputs"."""
         batch = models if models > 0 else a.models
         if scaling == "weak":
             sizes = [batch] * world                          # every GPU scores its own batch of M
@@ -445,6 +502,7 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         if world > 1:
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        outputs = capture_outputs(M) if capture else None
         if pipelined:                            # the two batches still queued are not part of any step: drop them
             eng.adopt_prefetched()
             eng.adopt_prefetched()
@@ -462,7 +520,15 @@ def main():
         else:
             ptr, _ = eng.device_buffer(0)
             scores = torch.as_tensor(_DevView(ptr, M, "<i4"), device=dev).cpu().numpy()
-        return {"sizes": sizes, "M": M, "dt": float(tt.item()), "dt_local": dt, "xchg_ms": ms_x / max(n_x, 1), "res_ms": ms_res / max(n_res, 1),
+        if outputs is not None:
+            outputs["best"] = np.array([best, score])
+            if scores.size > DUMP_MAX_MODELS:
+                pick = np.sort(np.random.default_rng([a.seed, scores.size, N]).choice(scores.size, DUMP_MAX_MODELS, replace=False))
+                outputs["scores_index"], scores_out = pick, scores[pick]
+            else:
+                scores_out = scores
+            outputs["scores"] = scores_out
+        return {"outputs": outputs, "sizes": sizes, "M": M, "dt": float(tt.item()), "dt_local": dt, "xchg_ms": ms_x / max(n_x, 1), "res_ms": ms_res / max(n_res, 1),
                 "dlt_ms": ms_dlt / max(n_dlt, 1), "best_model": int(best), "best_score": int(score),
                 "step_ms_median": per_step[len(per_step) // 2], "step_ms_min": per_step[0], "step_ms_max": per_step[-1],
                 "scores_sha256": hashlib.sha256(np.ascontiguousarray(scores).tobytes()).hexdigest()[:16]}
@@ -499,25 +565,35 @@ def main():
 
     # One GPU: kernel events inside the timed region (the roofline's launch time is measured in the run it describes).  Several
     # ranks: the headline steps carry no timing markers at all, and the kernel times come from a short pass of their own.
-    pipe = run_mode(a.scaling, a.steps, a.warmup, pipelined=True, profile=(world == 1))
-    kernel_pass = None
-    if world > 1:
-        kernel_pass = run_mode(a.scaling, min(a.steps, 8), 1, pipelined=True, profile=True)
-        pipe["res_ms"], pipe["dlt_ms"], pipe["xchg_ms"] = kernel_pass["res_ms"], kernel_pass["dlt_ms"], kernel_pass["xchg_ms"]
-    other = None
-    if world > 1 and not a.no_other_mode:
-        other = run_mode("weak" if a.scaling == "strong" else "strong", a.steps, a.warmup, pipelined=True, profile=False)
-        ko = run_mode("weak" if a.scaling == "strong" else "strong", min(a.steps, 8), 1, pipelined=True, profile=True)
-        other["res_ms"], other["dlt_ms"] = ko["res_ms"], ko["dlt_ms"]
-    seq = run_mode(a.scaling, a.steps, a.warmup, pipelined=False)
     # Which form is the headline.  One GPU: the SEQUENTIAL form — the sweep runs at the board's power cap, so a DLT beside it
     # is not free: it lengthens the sweep by what it would have cost alone (7.31 + 0.06 ms pipelined against 7.00 + 0.33 +
     # 0.04 ms in sequence, r05), the step is the same to 0.1 %, and in sequence the residual kernel's launch time — the
     # roofline's denominator — is the kernel's own.  Several GPUs: the PIPELINED form — a rank's step is 1 ms, and the
-    # hand-over between the DLT and the sweep is 5 % of it.  The other form is timed in the same run and
-    # reported beside the headline (`pipelined_form` / `sequential_form`).
-    head, other_form = (seq, pipe) if world == 1 else (pipe, seq)
+    # hand-over between the DLT and the sweep is 5 % of it.  With --full the other form is timed in the same
+    # run and reported beside the headline (`pipelined_form` / `sequential_form`).
+    dump = a.dump_outputs is not None
+    other = None
+    if a.full:
+        pipe = run_mode(a.scaling, a.steps, a.warmup, pipelined=True, profile=(world == 1), capture=dump and world > 1)
+        kernel_pass = None
+        if world > 1:
+            kernel_pass = run_mode(a.scaling, min(a.steps, 8), 1, pipelined=True, profile=True)
+            pipe["res_ms"], pipe["dlt_ms"], pipe["xchg_ms"] = kernel_pass["res_ms"], kernel_pass["dlt_ms"], kernel_pass["xchg_ms"]
+        if world > 1 and not a.no_other_mode:
+            other = run_mode("weak" if a.scaling == "strong" else "strong", a.steps, a.warmup, pipelined=True, profile=False)
+            ko = run_mode("weak" if a.scaling == "strong" else "strong", min(a.steps, 8), 1, pipelined=True, profile=True)
+            other["res_ms"], other["dlt_ms"] = ko["res_ms"], ko["dlt_ms"]
+        seq = run_mode(a.scaling, a.steps, a.warmup, pipelined=False, capture=dump and world == 1)
+        head, other_form = (seq, pipe) if world == 1 else (pipe, seq)
+    else:
+        # A plain run times the headline form alone.  Its setup ends with one untimed step, which sizes the engine's buffers
+        # (the 8 N M-byte residual matrix among them) and loads the kernels, so that even --warmup 0 times steady steps.
+        run_mode(a.scaling, 1, 0, pipelined=(world > 1), profile=False, mark_steps=False)
+        head = run_mode(a.scaling, a.steps, a.warmup, pipelined=(world > 1), profile=(world == 1), capture=dump)
+        other_form = None
     M, sizes, dt = head["M"], head["sizes"], head["dt"]
+    if dump and rank == 0:
+        dump_outputs(a.dump_outputs, head["outputs"])
     # What the transport is, read back from RCCL itself, and each rank's own figures — gathered ONCE, outside every timed
     # region: a multi-GPU number can then be decomposed into the ranks' sweeps, their waits in the exchange and their steps.
     transport = {"kind": transport_kind if world > 1 else "none (one GPU: no exchange; the arg-max runs on the engine's exchange stream)",
@@ -529,7 +605,7 @@ def main():
         if transport["rccl_ranks"] != world:
             raise SystemExit(f"bench.py: RCCL reports a communicator of {transport['rccl_ranks']} ranks, the launcher started {world}")
     per_rank = None
-    if world > 1:
+    if world > 1 and a.full:
         mine = {"rank": rank, "hypotheses_per_step": head["M"], "k_residual_ms": head["res_ms"], "exchange_ms": head.get("xchg_ms"),
                 "step_ms": head["dt_local"] / a.steps * 1e3,
                 "rccl_rank": int(native_comm[0].mhr_rank(native_comm[1])) if native_comm is not None else None}
@@ -539,7 +615,7 @@ def main():
     # One GPU only: the per-rank shards a strong split of this batch over 2 / 4 / 8 GPUs would hand a rank, stepped the same
     # way (no timing markers inside, 40 steps) — what the split can reach at best before any exchange between real ranks.
     shard_rehearsal = None
-    if world == 1 and a.models >= 8 * 1024 and not a.no_rehearsal:
+    if a.full and world == 1 and a.models >= 8 * 1024 and not a.no_rehearsal:
         ref = run_mode("strong", 20, 3, pipelined=True, profile=False, mark_steps=False)
         shard_rehearsal = {"what": "the same pipelined step on 1 GPU with this batch's per-rank shard of a 2 / 4 / 8-GPU strong split (no timing "
                                    "markers inside the timed steps); efficiency = (ms per step of the whole batch / ranks) / ms per step of the shard",
@@ -550,95 +626,99 @@ def main():
             shard_rehearsal["shards"].append({"ranks": ranks, "hypotheses": a.models // ranks, "ms_per_step": ms,
                                               "efficiency": ref["dt"] / 20 * 1e3 / ranks / ms})
 
-    # Outside the timed region: the store-free fused score kernel and the s = 4 matrix (SURVEY §8(d) "fused score
-    # kernel: not HBM-bound", "also report s = 4"), reported next to the headline for context.  They are timed on a
-    # FULL batch proposed here — whatever ran last (the rehearsal's 12 500-hypothesis shard, for one) is not what
-    # stays resident — and every figure below divides by the model count READ BACK from the engine.
-    eng.propose_dlt4(a.seed, head_first, M)
-    M_res = eng.model_count
-    if M_res != M:
-        raise SystemExit(f"bench.py: {M_res} models resident where the side metrics expect this rank's batch of {M}")
-
-    def time_score():
-        eng.score(thr2, fetch=False)
-        eng.profile_reset()
-        eng.profile_enable(True)
-        for _ in range(5):
-            eng.score(thr2, fetch=False)
-        eng.synchronize()
-        n_sc, ms_sc = eng.profile_get(2)     # MH_K_SCORE
-        eng.profile_enable(False)
-        assert eng.model_count == M_res
-        return ms_sc / max(n_sc, 1)
-
-    eng.set_tuning(15, 0)                    # the FP64 sweep for every pair (k_residual without the stores)
-    fused_ms = time_score()
-    eng.set_tuning(15, 1)                    # the product's score path: FP32 pre-test with a rigorous bound, FP64 for the doubtful pairs
-    eng.score_stats(reset=True)
-    pretest_ms = time_score()
-    pre_pairs, pre_fp64 = eng.score_stats(reset=True)
-    # ... and the s = 4 variant of the matrix: the int32 data cost of every hypothesis against every point
-    eng.profile_reset()
-    eng.profile_enable(True)
-    for _ in range(4):
-        eng.cost_matrix(fetch_C=False, fetch_counts=False)
-    eng.synchronize()
-    n_cm, ms_cm = eng.profile_get(6)         # MH_K_COSTMATRIX
-    eng.profile_enable(False)
-    cost_ms = ms_cm / max(n_cm, 1)
-    eng.set_tuning(15, 0)                    # the FP64 formula for every pair (k_cost_matrix)
-    try:
-        eng.profile_reset()
-        eng.profile_enable(True)
-        for _ in range(3):
-            eng.cost_matrix(fetch_C=False, fetch_counts=False)
-        eng.synchronize()
-        n_c64, ms_c64 = eng.profile_get(6)
-        eng.profile_enable(False)
-    finally:
-        eng.set_tuning(15, 1)
-    assert eng.model_count == M_res
-    cost64_ms = ms_c64 / max(n_c64, 1)
-    # ... and north_star's SYMMETRIC transfer error (MH_RESIDUAL_SYMMETRIC: d2 = ||H p1 - p2||^2 + ||adj(H) p2 - p1||^2, the same
-    # 8-byte matrix; the reference has the forward form only, so this is an extension — tests/test_symmetric_exact.py checks its
-    # definition in exact rationals): FP64-issue bound, 57 rounded operations per pair
-    eng.set_residual_mode(True)
-    try:
-        eng.residual_matrix(thr2, fetch_R=False, fetch_counts=False)
-        eng.profile_reset()
-        eng.profile_enable(True)
-        for _ in range(3):
-            eng.residual_matrix(thr2, fetch_R=False, fetch_counts=False)
-        eng.synchronize()
-        n_sy, ms_sy = eng.profile_get(1)
-        eng.profile_enable(False)
-    finally:
-        eng.set_residual_mode(False)
-    sym_ms = ms_sy / max(n_sy, 1)
-    cost_bytes = 4.0 * N * M_res + 32.0 * N + 72.0 * M_res + 4.0 * M_res
+    # The kernel times of the headline: inside its timed region at one GPU, from the kernel pass of --full at several.
+    kernels = world == 1 or a.full
     avg_res_ms = head["res_ms"]
     alg_bytes = 8.0 * N * M + 32.0 * N + 72.0 * M + 4.0 * M
-    achieved = alg_bytes / (avg_res_ms * 1e-3) / 1e9
+    achieved = alg_bytes / (avg_res_ms * 1e-3) / 1e9 if kernels else None
 
-    # What this box's memory takes from stores alone, measured in this run: hipMemset over the residual matrix itself (the 40 GB
-    # the sweep has just written; a fill kernel of the runtime, no arithmetic).  Context for roofline.frac — the sweep computes
-    # 28 FP64 operations per pair at the board's power cap on top of the same store stream.  A reference, not a ceiling.
-    memset_GBps = None
-    try:
-        ptr_R, bytes_R = eng.device_buffer(2)            # MH_BUF_RESIDUALS
-        if ptr_R and bytes_R >= 8 * N * M:
-            t_R = torch.as_tensor(_DevView(ptr_R, int(bytes_R), "|u1"), device=dev)
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            t_R.zero_()
-            torch.cuda.synchronize()
-            ev[0].record()
+    if a.full:
+        # Outside the timed region: the store-free fused score kernel and the s = 4 matrix (SURVEY §8(d) "fused score
+        # kernel: not HBM-bound", "also report s = 4"), reported next to the headline for context.  They are timed on a
+        # FULL batch proposed here — whatever ran last (the rehearsal's 12 500-hypothesis shard, for one) is not what
+        # stays resident — and every figure below divides by the model count READ BACK from the engine.
+        eng.propose_dlt4(a.seed, head_first, M)
+        M_res = eng.model_count
+        if M_res != M:
+            raise SystemExit(f"bench.py: {M_res} models resident where the side metrics expect this rank's batch of {M}")
+
+        def time_score():
+            eng.score(thr2, fetch=False)
+            eng.profile_reset()
+            eng.profile_enable(True)
+            for _ in range(5):
+                eng.score(thr2, fetch=False)
+            eng.synchronize()
+            n_sc, ms_sc = eng.profile_get(2)     # MH_K_SCORE
+            eng.profile_enable(False)
+            assert eng.model_count == M_res
+            return ms_sc / max(n_sc, 1)
+
+        eng.set_tuning(15, 0)                    # the FP64 sweep for every pair (k_residual without the stores)
+        fused_ms = time_score()
+        eng.set_tuning(15, 1)                    # the product's score path: FP32 pre-test with a rigorous bound, FP64 for the doubtful pairs
+        eng.score_stats(reset=True)
+        pretest_ms = time_score()
+        pre_pairs, pre_fp64 = eng.score_stats(reset=True)
+        # ... and the s = 4 variant of the matrix: the int32 data cost of every hypothesis against every point
+        eng.profile_reset()
+        eng.profile_enable(True)
+        for _ in range(4):
+            eng.cost_matrix(fetch_C=False, fetch_counts=False)
+        eng.synchronize()
+        n_cm, ms_cm = eng.profile_get(6)         # MH_K_COSTMATRIX
+        eng.profile_enable(False)
+        cost_ms = ms_cm / max(n_cm, 1)
+        eng.set_tuning(15, 0)                    # the FP64 formula for every pair (k_cost_matrix)
+        try:
+            eng.profile_reset()
+            eng.profile_enable(True)
             for _ in range(3):
-                t_R.zero_()
-            ev[1].record()
-            torch.cuda.synchronize()
-            memset_GBps = float(bytes_R) * 3 / (ev[0].elapsed_time(ev[1]) * 1e-3) / 1e9
-    except Exception:
+                eng.cost_matrix(fetch_C=False, fetch_counts=False)
+            eng.synchronize()
+            n_c64, ms_c64 = eng.profile_get(6)
+            eng.profile_enable(False)
+        finally:
+            eng.set_tuning(15, 1)
+        assert eng.model_count == M_res
+        cost64_ms = ms_c64 / max(n_c64, 1)
+        # ... and north_star's SYMMETRIC transfer error (MH_RESIDUAL_SYMMETRIC: d2 = ||H p1 - p2||^2 + ||adj(H) p2 - p1||^2, the same
+        # 8-byte matrix; the reference has the forward form only, so this is an extension — tests/test_symmetric_exact.py checks its
+        # definition in exact rationals): FP64-issue bound, 57 rounded operations per pair
+        eng.set_residual_mode(True)
+        try:
+            eng.residual_matrix(thr2, fetch_R=False, fetch_counts=False)
+            eng.profile_reset()
+            eng.profile_enable(True)
+            for _ in range(3):
+                eng.residual_matrix(thr2, fetch_R=False, fetch_counts=False)
+            eng.synchronize()
+            n_sy, ms_sy = eng.profile_get(1)
+            eng.profile_enable(False)
+        finally:
+            eng.set_residual_mode(False)
+        sym_ms = ms_sy / max(n_sy, 1)
+        cost_bytes = 4.0 * N * M_res + 32.0 * N + 72.0 * M_res + 4.0 * M_res
+
+        # What this box's memory takes from stores alone, measured in this run: hipMemset over the residual matrix itself (the 40 GB
+        # the sweep has just written; a fill kernel of the runtime, no arithmetic).  Context for roofline.frac — the sweep computes
+        # 28 FP64 operations per pair at the board's power cap on top of the same store stream.  A reference, not a ceiling.
         memset_GBps = None
+        try:
+            ptr_R, bytes_R = eng.device_buffer(2)            # MH_BUF_RESIDUALS
+            if ptr_R and bytes_R >= 8 * N * M:
+                t_R = torch.as_tensor(_DevView(ptr_R, int(bytes_R), "|u1"), device=dev)
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                t_R.zero_()
+                torch.cuda.synchronize()
+                ev[0].record()
+                for _ in range(3):
+                    t_R.zero_()
+                ev[1].record()
+                torch.cuda.synchronize()
+                memset_GBps = float(bytes_R) * 3 / (ev[0].elapsed_time(ev[1]) * 1e-3) / 1e9
+        except Exception:
+            memset_GBps = None
 
     fractions = {}
 
@@ -685,72 +765,80 @@ def main():
                                    f"propose+residual-matrix+score" + ("+all-gather" if world > 1 else "") + "+argmax",
                        "points": N, "models_per_step": int(sum(sizes)), "models_rank0": M, "planes": a.planes, "thr": thr,
                        "parallelism": f"hypothesis-sharded x{world}"},
-            "residual_kernel_GBps": achieved,
             "pair_evals_per_s": total_hyp * N / dt,
             "step_ms": {"median": head["step_ms_median"], "min": head["step_ms_min"], "max": head["step_ms_max"],
                         "mean_wall": dt / a.steps * 1e3, "note": "HIP events on the engine's stream at every step boundary"},
-            "form": "sequential (propose, sweep, arg-max on one stream)" if head is seq else "pipelined (the DLT of batch i+2 on the second stream beside sweep i)",
-            "kernel_ms": {"k_residual": avg_res_ms, "k_dlt4_span_on_the_second_stream": pipe["dlt_ms"], "k_dlt4_alone": seq["dlt_ms"],
-                          "k_score_fused_fp64": fused_ms, "k_score_fp32_pretest": pretest_ms, "k_cost_matrix_int32": cost_ms},
-            "step_minus_residual_ms": head["step_ms_median"] - avg_res_ms,
-            "kernel_ms_source": ("HIP events around every launch inside the timed region" if world == 1 else
-                                 "a separate pass of 8 steps with HIP events around every launch; the headline steps carry no timing markers"),
-            ("pipelined_form" if head is seq else "sequential_form"): {
-                "what": ("the same steps software-pipelined: the DLT of batch i+2 on the engine's second stream beside sweep i (k_residual_ms is the "
-                         "sweep WITH the DLT beside it)" if head is seq else
-                         "the same steps with the four stages in sequence on one stream (no second stream)"),
-                "value": float(sum(other_form["sizes"])) * a.steps / other_form["dt"], "ms_per_step": other_form["dt"] / a.steps * 1e3,
-                "step_ms_median": other_form["step_ms_median"], "k_residual_ms": other_form["res_ms"], "k_dlt4_ms": other_form["dlt_ms"],
-                "k_residual_frac_of_hbm_peak": frac("other_form.k_residual_frac_of_hbm_peak", alg_bytes / (other_form["res_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS),
-                "scores_identical": other_form["scores_sha256"] == head["scores_sha256"]},
+            "form": "sequential (propose, sweep, arg-max on one stream)" if world == 1 else "pipelined (the DLT of batch i+2 on the second stream beside sweep i)",
             "transport": transport,
-            "per_rank": per_rank,
-            "per_rank_note": ("k_residual_ms / exchange_ms: HIP events around every launch in a separate pass of 8 steps (exchange_ms: from the end of the batch's "
-                              "sweep to the end of the arg-max behind the all-gather, on the exchange stream = the rank's wait for its peers + the wire time); "
-                              "step_ms: this rank's own wall time over the headline steps (the headline takes the MAX over ranks)") if per_rank else None,
-            "strong_split_rehearsal_on_one_gpu": shard_rehearsal,
-            "fused_score_hypotheses_per_s_per_gpu": M_res / (pretest_ms * 1e-3),
-            "fused_score": {"what": "mh_score on the same batch, no matrix written: FP32 pre-test with a rigorous error bound, FP64 formula only for the "
-                                    "pairs it cannot decide (csrc/score32.hip); counts identical to the FP64 sweep's",
-                            "models_resident": M_res, "ms": pretest_ms, "ms_fp64_sweep": fused_ms, "pairs_decided_in_fp64": pre_fp64 / max(pre_pairs, 1)},
-            # fused score kernel, FP64 sweep: FP64-issue bound.  28 rounded FP64 operations per pair (M/MultiH.cpp:434-441 with two IEEE
-            # divisions sharing one refined reciprocal) against the chip's FP64 vector issue rate at its 2.4 GHz maximum
-            # (256 CUs x 4 SIMDs x 16 lanes per clock = 39.3 T operations/s, i.e. the 78.6 TFLOP/s spec counting an FMA as two)
-            "fused_score_fp64": {"models_resident": M_res, "ops_per_pair": 28, "ops_per_s": 28.0 * N * M_res / (fused_ms * 1e-3),
-                                 "peak_ops_per_s_at_2.4GHz": 256 * 4 * 16 * 2.4e9,
-                                 "utilisation_vs_2.4GHz_peak": frac("fused_score_fp64.utilisation_vs_2.4GHz_peak", 28.0 * N * M_res / (fused_ms * 1e-3) / (256 * 4 * 16 * 2.4e9))},
-            "cost_matrix_s4": {"what": "int32 PEARL data cost of every hypothesis against every point, materialised (mh_cost_matrix): "
-                                       "the s = 4 variant of SURVEY 8(d), through the FP32 pre-test (csrc/score32.hip k_cost32: the constant for pairs "
-                                       "proved beyond the truncation threshold, the reference's FP64 formula for the rest); ms_fp64_everywhere = "
-                                       "the FP64 formula for every pair (k_cost_matrix: FP64-issue bound, a second IEEE division per pair)",
-                               "models_resident": M_res, "ms": cost_ms, "ms_fp64_everywhere": cost64_ms, "algorithmic_bytes_per_launch": cost_bytes, "GBps": cost_bytes / (cost_ms * 1e-3) / 1e9,
-                               "frac_of_hbm_peak": frac("cost_matrix_s4.frac_of_hbm_peak", cost_bytes / (cost_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS),
-                               "frac_of_hbm_peak_fp64_everywhere": frac("cost_matrix_s4.frac_of_hbm_peak_fp64_everywhere", cost_bytes / (cost64_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS)},
-            "symmetric_transfer": {"what": "mh_residual_matrix in MH_RESIDUAL_SYMMETRIC mode on the same batch: forward + backward transfer error, R written "
-                                           "(8 B per pair); 57 rounded FP64 operations per pair (2 x 28 + the sum), FP64-issue bound",
-                                   "models_resident": M_res, "ms": sym_ms, "ops_per_pair": 57, "ops_per_s": 57.0 * N * M_res / (sym_ms * 1e-3),
-                                   "utilisation_vs_2.4GHz_fp64_vector_peak": frac("symmetric_transfer.utilisation", 57.0 * N * M_res / (sym_ms * 1e-3) / (256 * 4 * 16 * 2.4e9)),
-                                   "frac_of_hbm_peak": frac("symmetric_transfer.frac_of_hbm_peak", (8.0 * N * M_res) / (sym_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS),
-                                   "hypotheses_per_s": M_res / (sym_ms * 1e-3)},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": frac("roofline.frac", achieved / HBM_PEAK_GBPS), "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": "k_residual", "algorithmic_bytes_per_launch": alg_bytes,
-                         "measured_write_ceiling_GBps": HBM_WRITE_CEILING_GBPS,
-                         "frac_of_measured_write_ceiling": frac("roofline.frac_of_measured_write_ceiling", achieved / HBM_WRITE_CEILING_GBPS),
-                         # a same-box REFERENCE, not a ceiling (the runtime's fill kernel is not the fastest store stream: a ratio
-                         # slightly above 1 is possible and has been measured since the sweep handles 64 models per work item)
-                         "memset_of_R_on_this_box_GBps": memset_GBps,
-                         "ratio_to_that_memset": (achieved / memset_GBps) if memset_GBps else None,
-                         "models_per_launch": M},
             "best_model": head["best_model"], "best_score": head["best_score"], "scores_sha256": head["scores_sha256"],
+            "cpu_baseline": None,
         }
+        if kernels:
+            out.update({
+                "residual_kernel_GBps": achieved,
+                "kernel_ms": {"k_residual": avg_res_ms, "k_dlt4_alone": (head if world == 1 else other_form)["dlt_ms"]},
+                "step_minus_residual_ms": head["step_ms_median"] - avg_res_ms,
+                "kernel_ms_source": ("HIP events around every launch inside the timed region" if world == 1 else
+                                     "a separate pass of 8 steps with HIP events around every launch; the headline steps carry no timing markers"),
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": frac("roofline.frac", achieved / HBM_PEAK_GBPS), "traffic": traffic, "traffic_source": traffic_source,
+                             "kernel": "k_residual", "algorithmic_bytes_per_launch": alg_bytes,
+                             "measured_write_ceiling_GBps": HBM_WRITE_CEILING_GBPS,
+                             "frac_of_measured_write_ceiling": frac("roofline.frac_of_measured_write_ceiling", achieved / HBM_WRITE_CEILING_GBPS),
+                             "models_per_launch": M}})
+        if a.full:
+            out["kernel_ms"].update({"k_dlt4_span_on_the_second_stream": pipe["dlt_ms"], "k_score_fused_fp64": fused_ms,
+                                     "k_score_fp32_pretest": pretest_ms, "k_cost_matrix_int32": cost_ms})
+            # a same-box REFERENCE, not a ceiling (the runtime's fill kernel is not the fastest store stream: a ratio
+            # slightly above 1 is possible and has been measured since the sweep handles 64 models per work item)
+            out["roofline"].update({"memset_of_R_on_this_box_GBps": memset_GBps,
+                                    "ratio_to_that_memset": (achieved / memset_GBps) if memset_GBps else None})
+            out.update({
+                ("pipelined_form" if world == 1 else "sequential_form"): {
+                    "what": ("the same steps software-pipelined: the DLT of batch i+2 on the engine's second stream beside sweep i (k_residual_ms is the "
+                             "sweep WITH the DLT beside it)" if world == 1 else
+                             "the same steps with the four stages in sequence on one stream (no second stream)"),
+                    "value": float(sum(other_form["sizes"])) * a.steps / other_form["dt"], "ms_per_step": other_form["dt"] / a.steps * 1e3,
+                    "step_ms_median": other_form["step_ms_median"], "k_residual_ms": other_form["res_ms"], "k_dlt4_ms": other_form["dlt_ms"],
+                    "k_residual_frac_of_hbm_peak": frac("other_form.k_residual_frac_of_hbm_peak", alg_bytes / (other_form["res_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS),
+                    "scores_identical": other_form["scores_sha256"] == head["scores_sha256"]},
+                "transport": transport,
+                "per_rank": per_rank,
+                "per_rank_note": ("k_residual_ms / exchange_ms: HIP events around every launch in a separate pass of 8 steps (exchange_ms: from the end of the batch's "
+                                  "sweep to the end of the arg-max behind the all-gather, on the exchange stream = the rank's wait for its peers + the wire time); "
+                                  "step_ms: this rank's own wall time over the headline steps (the headline takes the MAX over ranks)") if per_rank else None,
+                "strong_split_rehearsal_on_one_gpu": shard_rehearsal,
+                "fused_score_hypotheses_per_s_per_gpu": M_res / (pretest_ms * 1e-3),
+                "fused_score": {"what": "mh_score on the same batch, no matrix written: FP32 pre-test with a rigorous error bound, FP64 formula only for the "
+                                        "pairs it cannot decide (csrc/score32.hip); counts identical to the FP64 sweep's",
+                                "models_resident": M_res, "ms": pretest_ms, "ms_fp64_sweep": fused_ms, "pairs_decided_in_fp64": pre_fp64 / max(pre_pairs, 1)},
+                # fused score kernel, FP64 sweep: FP64-issue bound.  28 rounded FP64 operations per pair (M/MultiH.cpp:434-441 with two IEEE
+                # divisions sharing one refined reciprocal) against the chip's FP64 vector issue rate at its 2.4 GHz maximum
+                # (256 CUs x 4 SIMDs x 16 lanes per clock = 39.3 T operations/s, i.e. the 78.6 TFLOP/s spec counting an FMA as two)
+                "fused_score_fp64": {"models_resident": M_res, "ops_per_pair": 28, "ops_per_s": 28.0 * N * M_res / (fused_ms * 1e-3),
+                                     "peak_ops_per_s_at_2.4GHz": 256 * 4 * 16 * 2.4e9,
+                                     "utilisation_vs_2.4GHz_peak": frac("fused_score_fp64.utilisation_vs_2.4GHz_peak", 28.0 * N * M_res / (fused_ms * 1e-3) / (256 * 4 * 16 * 2.4e9))},
+                "cost_matrix_s4": {"what": "int32 PEARL data cost of every hypothesis against every point, materialised (mh_cost_matrix): "
+                                           "the s = 4 variant of SURVEY 8(d), through the FP32 pre-test (csrc/score32.hip k_cost32: the constant for pairs "
+                                           "proved beyond the truncation threshold, the reference's FP64 formula for the rest); ms_fp64_everywhere = "
+                                           "the FP64 formula for every pair (k_cost_matrix: FP64-issue bound, a second IEEE division per pair)",
+                                   "models_resident": M_res, "ms": cost_ms, "ms_fp64_everywhere": cost64_ms, "algorithmic_bytes_per_launch": cost_bytes, "GBps": cost_bytes / (cost_ms * 1e-3) / 1e9,
+                                   "frac_of_hbm_peak": frac("cost_matrix_s4.frac_of_hbm_peak", cost_bytes / (cost_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS),
+                                   "frac_of_hbm_peak_fp64_everywhere": frac("cost_matrix_s4.frac_of_hbm_peak_fp64_everywhere", cost_bytes / (cost64_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS)},
+                "symmetric_transfer": {"what": "mh_residual_matrix in MH_RESIDUAL_SYMMETRIC mode on the same batch: forward + backward transfer error, R written "
+                                               "(8 B per pair); 57 rounded FP64 operations per pair (2 x 28 + the sum), FP64-issue bound",
+                                       "models_resident": M_res, "ms": sym_ms, "ops_per_pair": 57, "ops_per_s": 57.0 * N * M_res / (sym_ms * 1e-3),
+                                       "utilisation_vs_2.4GHz_fp64_vector_peak": frac("symmetric_transfer.utilisation", 57.0 * N * M_res / (sym_ms * 1e-3) / (256 * 4 * 16 * 2.4e9)),
+                                       "frac_of_hbm_peak": frac("symmetric_transfer.frac_of_hbm_peak", (8.0 * N * M_res) / (sym_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS),
+                                       "hypotheses_per_s": M_res / (sym_ms * 1e-3)},
+            })
         if other is not None:
             o_total = float(sum(other["sizes"])) * a.steps
             out["weak_scaling" if a.scaling == "strong" else "strong_scaling"] = {
                 "value": o_total / other["dt"], "unit": "hypotheses/s", "ms_per_step": other["dt"] / a.steps * 1e3,
                 "models_per_step": int(sum(other["sizes"])), "kernel_ms": {"k_residual": other["res_ms"], "k_dlt4": other["dlt_ms"]},
                 "steps": a.steps, "warmup": a.warmup}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             sustained = {}
             cb, Hs, cs = cpu_baseline(sc, thr2, a.cpu_sample, a.seed, beside=lambda alive: sustained.update(run_sustained(alive)))
             out["cpu_baseline"] = cb
@@ -769,8 +857,6 @@ def main():
                 out["full_loop"] = full_loop_extra(a)
             except Exception as ex:
                 out["full_loop"] = {"error": repr(ex)}
-        else:
-            out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     eng.close()
     if native_comm is not None:

@@ -29,7 +29,7 @@ def _clean_env(**extra):
 
 def _bench(gpus, *args):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", *args]
+           "--full", "--no-cpu-baseline", *args]
     env = _clean_env(MH_BENCH_BACKEND="gloo", MH_BENCH_DEVICE="0")
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
