@@ -294,7 +294,15 @@ MH_API int mh_data_cost(mh_engine* e, int* cost);
 /* alpha-expansion over the current data cost and neighbour graph with the Potts term
  * round(100*lambda) (M/MultiH.cpp:506-511; GCoptimization.cpp:975-1058,1212-1289).
  * labels: in = initial labeling in GCO numbering 0..Nh (NULL = all zero), out = result in GCO
- * numbering.  energy: final int32 energy; cycles: executed cycles. */
+ * numbering.  energy: final int32 energy; cycles: executed cycles.
+ * Contract: any non-negative int32 cost table (mh_data_cost's, or a table written into MH_BUF_COST behind it) and any graph.
+ * Overflow bound: the call returns MH_ERR_OVERFLOW when the energy of the initial labeling exceeds 2^31 - 1, or when one
+ * n-link potts * w_pq (w_pq = hit multiplicity) does — there GCO's int EnergyType / EnergyTermType wrap and its result is
+ * not defined.  Below that bound every t-link and every move's total flow fit int32 (each is at most the energy of the
+ * labeling the move starts from, which never increases) and the result is GCO's.  Deviation: the push-relabel solver holds
+ * a site's excess and an arc's cumulative flow counter to 2^30 and refuses the call (MH_ERR_OVERFLOW) beyond, where GCO's
+ * int max-flow would still be exact; with an initial energy of at most 2^30 no excess can reach that, a flow counter could
+ * in principle (pushes back and forth over one arc).  The engine never returns MH_OK with a wrapped result. */
 MH_API int mh_expand(mh_engine* e, const int* init_labels, int* labels_out, int* energy, int* cycles);
 /* Counters of the last alpha-expansion: {0 cycles, 1 moves, 2 accepted moves, 3 push phases, 4 relaxation
  * intervals, 5 host synchronisations, 6 dominance-reduction launches, 7 moves that still needed
@@ -313,7 +321,8 @@ MH_API int mh_expand(mh_engine* e, const int* init_labels, int* labels_out, int*
 MH_API int mh_get_expand_stats(mh_engine* e, long long stats[24]);
 /* r06: the concurrent alpha-moves of the last expansion (csrc/expand.hip, k_commit): [0] batches launched, [1] moves kept out of a
  * batch (solved beside others on the same labeling and validated), [2] batches that ended at a move whose test failed (it heads the
- * next batch), [3] moves the host never launched because they were provably idempotent, [4] moves run alone, [5] reserved (0),
+ * next batch), [3] moves the host never launched because they were provably idempotent, [4] moves run alone, [5] failures injected by the test hook of key 40 whose move
+ * its batch threw away,
  * [6] moves per batch (mh_set_tuning key 37), [7] label count from which the first cycle is batched too (key 38). */
 MH_API int mh_get_expand_batch_stats(mh_engine* e, long long stats[8]);
 /* Per-move log of the last alpha-expansion's solver launches (diagnostic; enabled with mh_set_tuning key 8 = number of
@@ -403,6 +412,10 @@ MH_API int mh_profile_get(mh_engine* e, int kernel, int* launches, double* total
  *  38   S     16      ... from the first cycle on for label sets of at least this many labels (smaller sets from the second cycle)
  *  39   S     0       ... sites per wavefront in the setup and reduction launches of a batch of moves: 16 / 32 / 64, 0 = by the size of the
  *                     launch (moves x sites); a move alone takes 16, a batch's energy-difference launch 64
+ *  40   T     0       (g << 4) | k, g >= 1: in the NEXT expansion, the solve of context k (0..15) of the g-th group of moves it enqueues
+ *                     (a batch or a move alone, counted from 1) is marked as not converged.  A move that is kept reports it ("push-relabel
+ *                     did not converge", MH_ERR_HIP); a move its batch throws away (solved on a labeling an accepted predecessor has
+ *                     changed) is solved again, and mh_get_expand_batch_stats word 5 counts it
  * (34 and 35 are not assigned.) */
 MH_API int mh_set_tuning(mh_engine* e, int key, int value);
 

@@ -422,7 +422,7 @@ class Engine:
     def expand_batch_stats(self):
         st = (C.c_longlong * 8)()
         self._check(self.lib.mh_get_expand_batch_stats(self._h, st))
-        return dict(zip(("batches", "batch_committed", "batch_invalid", "host_skipped", "solo_moves", "reserved", "moves_per_batch",
+        return dict(zip(("batches", "batch_committed", "batch_invalid", "host_skipped", "solo_moves", "injected_discarded", "moves_per_batch",
                          "batch_min_labels"), list(st)))
 
     def expand_trace(self, moves: int):

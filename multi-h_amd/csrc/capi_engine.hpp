@@ -208,6 +208,7 @@ struct mh_engine {
     int last_solve_grid = 0;                 // workgroups of the solver launch in the attempt that completed
     int inject_select_failure = 0;           // test hook (key 18): the n-th scoring round of the coming greedy selections fails on this rank
     int inject_barrier_timeouts = 0;         // test hook: the next n expansions' first attempts count as timed out
+    int inject_solve_failure = 0;            // test hook (key 40): (group << 4) | context of the next expansion's solve marked failed
     DevBuf<long long> ew_acc;
     int* h_flags = nullptr;
     MeanShiftResultBlock* h_ms = nullptr;      // mapped pinned result block of the mean-shift climbs

@@ -172,6 +172,9 @@ int do_expand(mh_engine* e, const int* init_dev, long long* energy, int* cycles)
             w.barrier_first_timeout_ticks = last_attempt ? 300000000ll : (long long)(std::max(250.0, 10.0 * steady_ms) * 1e5);
             if (w.saved_flow) HIPCHK(hipMemsetAsync(e->ew_saved.p, 0, sizeof(int) * recycle_words, e->stream));
             HIPCHK(launch_init_labeling(e->cost.p, e->cost_L, e->n, init_dev, w.label, w.cur_cost, e->stream));
+            w.inject_group = e->inject_solve_failure >> 4;                     // test hook (mh_set_tuning key 40): first attempt only
+            w.inject_ctx = e->inject_solve_failure & 15;
+            e->inject_solve_failure = 0;
             he = run_expansion(g, e->cost.p, e->cost_L, potts, w, 1000, &st, e->stream);
             bool timed_out = he == hipErrorLaunchTimeOut && st.energy == -2;
             if (he == hipSuccess && e->inject_barrier_timeouts > 0) {           // test hook (mh_set_tuning key 14)
@@ -358,7 +361,7 @@ int mh_get_expand_batch_stats(mh_engine* e, long long stats[8])
     stats[2] = x.batch_invalid;
     stats[3] = x.host_skipped;
     stats[4] = x.solo_moves;
-    stats[5] = 0;
+    stats[5] = x.injected_discarded;
     stats[6] = expand_contexts(e);
     stats[7] = e->tune_batch_min_labels;
     return MH_OK;

@@ -317,7 +317,9 @@ k_move_setup(Graph g, const int* __restrict__ cost, int L, int potts, int reduce
         long long S = 0, out = 0, inn = 0;
         for (int k = k0 + sub; k < k1; k += LPN) {
             const int j = g.col[k];
-            const int wk = g.w[k] * potts;
+            const long long wk64 = (long long)g.w[k] * potts;
+            if (wk64 > 0x7fffffffll) atomicExch(&flags[C_ERROR], ERR_OVERFLOW);     // an n-link beyond int32 (GCO's EnergyTermType)
+            const int wk = wk64 > 0x7fffffffll ? 0x7fffffff : (int)wk64;
             int lj = label[j];
             if (pa >= 0 && took[j]) lj = pa;
             if (lj == alpha) { S += wk; cap[k] = 0; cap[g.rev[k]] = 0; }
@@ -1454,7 +1456,6 @@ k_batch_commit(const int* __restrict__ cost, int L, int* __restrict__ label, int
         for (int k = 0; k < b.count; ++k) {
             const MoveCtx& c = b.c[k];
             const int ek = s_ek[k];
-            if (ek) err = ek;
             const bool skipped = ek != 0 || (c.t >= L && tlast0 <= c.t - L);
             bool valid = true;
             if (accepted) {
@@ -1464,6 +1465,9 @@ k_batch_commit(const int* __restrict__ cost, int L, int* __restrict__ label, int
                         if ((accepted >> j & 1u) && (s_bad[j] >> k & 1u)) valid = false;
             }
             if (!valid) { first_invalid = k; break; }
+            // a move's error counts only when the move is kept: one that is thrown away was solved on a labeling the sequential
+            // order never offered it (its error is cleared below with the contexts behind it, and it heads the next batch)
+            if (ek) err = ek;
             if (!skipped && s_pend[k] >= 0) { accepted |= 1u << k; last_t = c.t; ++n_acc; }
         }
         s_first = first_invalid; s_err = err; s_acc = accepted; s_last_t = last_t; s_n_acc = n_acc;
@@ -1511,7 +1515,8 @@ k_batch_commit(const int* __restrict__ cost, int L, int* __restrict__ label, int
         __threadfence_system();
         __hip_atomic_store(&h_batch[HB_SEQ], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         // ... and what k_batch_prep would do in front of the NEXT batch, whatever that batch will hold (every context, not just the
-        // ones it uses): a batch that follows a commit directly needs no launch of its own for it
+        // ones it uses): a batch that follows a commit directly needs no launch of its own for it.  This also clears C_ERROR of the
+        // first invalid context and of those behind it: what their solves raised belongs to problems no longer posed
         bctl[B_TLAST0] = g_tlast;
         G[C_PEND] = -1;
         for (int k = 0; k < EXPAND_MAX_CTX; ++k) bctl[B_BAD + k] = 0;
@@ -1676,6 +1681,11 @@ hipError_t run_expansion(const Graph& g, const int* cost, int L, int potts, Expa
     RET_IF(fetch(w, stats, s));
     stats.launches += 1;
     energy = w.h_acc[A_ENERGY];
+    if (energy > 0x7fffffffll) {                       // GCO's EnergyType is int: it would compare wrapped energies from here on
+        stats.energy = -ERR_OVERFLOW;
+        if (st) *st = stats;
+        return hipErrorInvalidValue;
+    }
 
     SolveParams sp{ w.reduce_rounds, w.relax_rounds, w.push_cycles, w.push_phases, w.push_mult > 0 ? w.push_mult : 1, 1 << 20, w.cascade_iters,
                     w.barrier_timeout_ticks > 0 ? (unsigned long long)w.barrier_timeout_ticks : 300000000ull,
@@ -1693,6 +1703,8 @@ hipError_t run_expansion(const Graph& g, const int* cost, int L, int potts, Expa
     CtxFlags all_flags{};
     for (int k = 0; k < n_ctx; ++k) all_flags.p[k] = all.c[k].flags;
     bool prepared = false;       // the contexts beyond 0 hold the global control words as they stand (nothing but batches has run since)
+    int group = 0;               // groups of moves enqueued (batches and moves alone), for the test hook of key 40
+    int injected_ctx = -1;       // the context of the current group whose solve the hook marked failed, -1 none
     auto enqueue_moves = [&](int alpha0, int t0, int count, int cycle) -> hipError_t {
         MoveBatch b = all;
         b.count = count;
@@ -1722,6 +1734,11 @@ hipError_t run_expansion(const Graph& g, const int* cost, int L, int potts, Expa
             hipLaunchKernelGGL(k_core_components, dim3(1), dim3(1024), 0, s, g, L, t0, w.decided, w.flags, w.comp_scratch,
                                w.comp_scratch + g.n, w.comp_out + 16 * (size_t)t0);
         hipLaunchKernelGGL(k_solve, dim3((unsigned)solve_grid, (unsigned)count), dim3(SOLVE_THREADS), solve_lds, s, g, L, b, mslots, sp);
+        injected_ctx = -1;
+        if (++group == w.inject_group && w.inject_ctx < count) {        // test hook (mh_set_tuning key 40): the solve "did not converge"
+            RET_IF(hipMemsetD32Async((hipDeviceptr_t)(b.c[w.inject_ctx].flags + C_ERROR), ERR_NO_CONVERGENCE, 1, s));
+            injected_ctx = w.inject_ctx;
+        }
         hipLaunchKernelGGL(k_delta, grid_d, blk, 0, s, g, cost, L, potts, w.label, w.cur_cost, b, spw_d);
         if (count > 1) {
             hipLaunchKernelGGL(k_batch_check, dim3(32, (unsigned)count), blk, 0, s, g, cost, L, potts, w.label, w.cur_cost, b, w.bctl);
@@ -1799,6 +1816,7 @@ hipError_t run_expansion(const Graph& g, const int* cost, int L, int potts, Expa
             }
             if (w.h_batch[HB_ERROR]) break;                           // the cycle's end reports it
             const int j = w.h_batch[HB_FIRST_INVALID];
+            if (injected_ctx >= j) ++stats.injected_discarded;          // (key 40: the marked move was thrown away, not reported)
             host_tlast = w.h_batch[HB_TLAST];
             host_fresh = true;
             stats.moves += j; stats.batch_committed += j;

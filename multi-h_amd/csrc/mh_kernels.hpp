@@ -222,6 +222,10 @@ struct ExpandWork {         // scratch owned by the engine
     int* h_batch_dev = nullptr;   //     ... and its device address
     int batch_min_labels = 0;     // batches only when the label set has at least this many labels
     int batch_spw = 0;            // sites per wave in a batch's setup and reduction launches: 16 / 32 / 64, 0 = by the size of the launch (a move alone: 16)
+    // test hook (mh_set_tuning key 40): the solve of context inject_ctx in the inject_group-th group of moves this expansion
+    // enqueues (a batch or a move alone, counted from 1) is marked failed (ERR_NO_CONVERGENCE) behind its k_solve; 0 = off
+    int inject_group = 0;
+    int inject_ctx = 0;
 };
 constexpr int EXPAND_MAX_CTX = 16;
 static_assert(sizeof(ExpandWork::ctx) / sizeof(ExpandWork::Ctx) == EXPAND_MAX_CTX - 1, "one context is the work area itself");
@@ -247,10 +251,11 @@ struct ExpandStats {
     double tail_ms;                           // of which: relabel/push rounds that began with fewer than 64 rows still holding excess
     long long tail_rounds;
     double max_barrier_wait_ms;               // longest single wait of the leader workgroup at a grid barrier
-    // r06, concurrent moves: batches launched; moves committed out of a batch (solved beside others, results kept); moves whose
-    // validation against their predecessors' changes failed (re-run alone); moves the HOST did not launch at all because they
-    // were provably idempotent; moves run alone (no batch)
+    // r06, concurrent moves: batches launched; moves committed out of a batch (solved beside others, results kept); batches that
+    // ended at a move whose validation against its predecessors' changes failed (that move heads the next batch); moves the HOST
+    // did not launch at all because they were provably idempotent; moves run alone (no batch)
     long long batches, batch_committed, batch_invalid, host_skipped, solo_moves;
+    long long injected_discarded;             // test hook (key 40): injected failures whose move the commit threw away
 };
 
 // resident workgroups of the solver launch per CU, as the occupancy query sees k_solve
