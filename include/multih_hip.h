@@ -140,6 +140,11 @@ MH_API int mh_refine_correspondences(mh_engine* e, const double F[9], const doub
 #define MH_REFINE_TRIANGULATION 2        /* :815-817  OptimalTriangulation failed (optimum at infinity, :1170-1175) */
 #define MH_REFINE_AFFINE_TEST 3          /* :826  distanceError > 1 (a NaN is dropped here too) */
 MH_API int mh_get_refine_reasons(mh_engine* e, unsigned char* reason /* n */, int n);
+/* The point-only form of mh_refine_correspondences: the Hartley-Sturm correction (step 1) alone, the same kernel and the same
+ * bits as there; no affinity is read (they need not be set).  Every row that is triangulated is kept.  refined (n x 4):
+ * x1 y1 x2 y2 of survivors.  mh_get_refine_reasons reports its rows (KEPT, NOT_IN_MASK, TRIANGULATION). */
+MH_API int mh_refine_points(mh_engine* e, const double F[9], const double e1[2], const double e2[2],
+                            const unsigned char* in_mask, unsigned char* keep, double* refined);
 
 /* ---- reference-style initialisation ------------- */
 /* ComputeLocalHomographies (M/MultiH.cpp:696-717, GetHomographyHAF :850-911): one homography per
@@ -333,16 +338,26 @@ MH_API int mh_get_expand_trace(mh_engine* e, int* trace /* moves x 8 */, int mov
  * {core sites, components, largest, second largest, sites in components of <= 64 / 256 / 1024 / 2048 / 8192 sites, components of
  * those sizes, propagation rounds, 0}; zeros for skipped moves.  Never changes a result. */
 MH_API int mh_get_core_components(mh_engine* e, int* out /* moves x 16 */, int moves);
+/* The re-estimator of mh_reestimate, mh_labeling_step and the refitted winners of mh_select_greedy (mh_set_tuning key 30).
+ *   MH_ESTIMATOR_HAF  GetHomographyHAFNonminimal (M/MultiH.cpp:913-989): needs the affinities and the epipolar geometry (default)
+ *   MH_ESTIMATOR_3PT  GetHomography3PT without LM refinement (M/MultiH.cpp:995-1050) over each label's members: H = [e']x F + e' v^T
+ *                     by least squares from the points alone; needs the epipolar geometry, not the affinities.  A label with
+ *                     fewer than 3 members keeps its H (as does one whose fit is not finite).
+ * Sticky per engine; mh_set_correspondences does not reset it.  The ranks of a sharded mh_select_greedy must agree on it. */
+#define MH_ESTIMATOR_HAF 0
+#define MH_ESTIMATOR_3PT 1
+MH_API int mh_set_estimator(mh_engine* e, int estimator);
 /* GetHomographyHAFNonminimal for every label (M/MultiH.cpp:913-989 + the 1/lambda rescale of
- * Homography_RefineHAFCallback.h:33-34).  labels: -1..Nh-1 per point.  Updates the current
- * model set in place; H_out (nullable) receives a host copy. */
+ * Homography_RefineHAFCallback.h:33-34), or the 3-point fit under MH_ESTIMATOR_3PT.  labels: -1..Nh-1 per point.  Updates the
+ * current model set in place; H_out (nullable) receives a host copy. */
 MH_API int mh_reestimate(mh_engine* e, const int* labels, double* H_out);
 /* LabelingStep (M/MultiH.cpp:513-602): data cost -> expansion (warm start iff warm != 0, from
- * `labeling` + 1) -> labels - 1 -> re-estimation.  labeling: in/out n ints (-1..Nh-1). */
+ * `labeling` + 1) -> labels - 1 -> re-estimation (the engine's estimator).  labeling: in/out n ints (-1..Nh-1). */
 MH_API int mh_labeling_step(mh_engine* e, int warm, int* labeling, double* energy, int* cycles);
 
 /* ---- device-side access (bench / multi-GPU plumbing) --------------------- */
-enum { MH_BUF_COUNTS = 0, MH_BUF_MODELS = 1, MH_BUF_RESIDUALS = 2, MH_BUF_LABELS = 3, MH_BUF_COST = 4, MH_BUF_GATHERED_SCORES = 5 };
+enum { MH_BUF_COUNTS = 0, MH_BUF_MODELS = 1, MH_BUF_RESIDUALS = 2, MH_BUF_LABELS = 3, MH_BUF_COST = 4, MH_BUF_GATHERED_SCORES = 5,
+       MH_BUF_LABEL_COUNTS = 6 /* per label, its member count in the last re-estimation (mh_reestimate / mh_labeling_step) */ };
 /* Device pointer and size in bytes of a resident buffer (valid until the next call that
  * re-allocates it).  Used to wrap the per-model scores in a tensor for the RCCL all-gather. */
 MH_API int mh_device_buffer(mh_engine* e, int which, void** ptr_dev, unsigned long long* bytes);
@@ -398,7 +413,8 @@ MH_API int mh_profile_get(mh_engine* e, int kernel, int* launches, double* total
  *  28   X     0       cost-matrix kernel evaluates the near pairs of several models together (same matrix; slower)
  *  29   S     12      mean shift: at most this many running climbs of a batch finish in one persistent launch (0 = a launch per iteration)
  *  30   R     0       mh_select_greedy refits every round's winner to the correspondences of the support set it explains (the loop's
- *                     per-label HAF least squares, M/MultiH.cpp:913-989, one label; needs affinities and the epipolar geometry) before it
+ *                     per-label HAF least squares, M/MultiH.cpp:913-989, one label; needs affinities and the epipolar geometry; under
+ *                     MH_ESTIMATOR_3PT the 3-point least squares, which needs the epipolar geometry alone) before it
  *                     claims them; the refit takes the hypothesis' place when it is finite and explains at least as many.  Sticky per engine;
  *                     class MultiH sets it on every call (SetProposalRefit, default on).  The ranks of a sharded batch must agree on it
  *                     (their records carry it; r06).
@@ -416,7 +432,8 @@ MH_API int mh_profile_get(mh_engine* e, int kernel, int* launches, double* total
  *                     (a batch or a move alone, counted from 1) is marked as not converged.  A move that is kept reports it ("push-relabel
  *                     did not converge", MH_ERR_HIP); a move its batch throws away (solved on a labeling an accepted predecessor has
  *                     changed) is solved again, and mh_get_expand_batch_stats word 5 counts it
- * (34 and 35 are not assigned.) */
+ *  34   X     0       the 3-point re-estimator's member form (measurement libraries): 0 by size, 1 the match loop, 2 the compacted lists
+ * (35 is not assigned.) */
 MH_API int mh_set_tuning(mh_engine* e, int key, int value);
 
 #ifdef __cplusplus

@@ -16,7 +16,8 @@ LIB_PATH = os.environ.get("MH_LIB") or os.path.join(HERE, "libmultih_hip.so")
 MH_OK = 0
 ERR_NAMES = {-1: "MH_ERR_NO_DEVICE", -2: "MH_ERR_INVALID", -3: "MH_ERR_HIP", -4: "MH_ERR_NOT_SET",
              -5: "MH_ERR_OVERFLOW"}
-BUF_COUNTS, BUF_MODELS, BUF_RESIDUALS, BUF_LABELS, BUF_COST = 0, 1, 2, 3, 4
+BUF_COUNTS, BUF_MODELS, BUF_RESIDUALS, BUF_LABELS, BUF_COST, BUF_LABEL_COUNTS = 0, 1, 2, 3, 4, 6
+ESTIMATORS = {"haf": 0, "3pt": 1}      # MH_ESTIMATOR_HAF, MH_ESTIMATOR_3PT
 K_DLT4, K_RESIDUAL, K_SCORE, K_DATACOST, K_EXPAND, K_REESTIMATE, K_COSTMATRIX = 0, 1, 2, 3, 4, 5, 6
 
 # every symbol include/multih_hip.h declares (tests check the export table against this)
@@ -24,11 +25,11 @@ SYMBOLS = [
     "mh_abi_version", "mh_last_error", "mh_device_count", "mh_create", "mh_destroy", "mh_set_params",
     "mh_set_stream", "mh_synchronize", "mh_set_correspondences", "mh_set_epipolar",
     "mh_set_neighbors_csr", "mh_build_neighbors_knn", "mh_build_neighbors_knn_radius", "mh_build_neighbors_radius", "mh_get_sym_graph", "mh_set_fundamental_metric", "mh_propose_fund8",
-    "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons",
+    "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons", "mh_refine_points",
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
     "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_samples", "mh_set_residual_mode", "mh_score",
     "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_data_cost", "mh_expand",
-    "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
+    "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
     "mh_profile_get", "mh_set_tuning",
 ]
 
@@ -215,8 +216,22 @@ class Engine:
                                                        mp, _p(keep, C.c_ubyte), _p(out, C.c_double)))
         return keep, out
 
+    def refine_points(self, F, e1, e2, in_mask=None):
+        """mh_refine_points: the Hartley-Sturm correction alone, no affinities.  Returns (keep [n], refined [n, 4])."""
+        F, e1, e2 = _f64(F).reshape(9), _f64(e1).reshape(2), _f64(e2).reshape(2)
+        keep = np.empty(self.n, dtype=np.uint8)
+        out = np.empty((self.n, 4), dtype=np.float64)
+        mp = None
+        if in_mask is not None:
+            in_mask = np.ascontiguousarray(in_mask, dtype=np.uint8)
+            mp = _p(in_mask, C.c_ubyte)
+        self._check(self.lib.mh_refine_points(self._h, _p(F, C.c_double), _p(e1, C.c_double), _p(e2, C.c_double),
+                                              mp, _p(keep, C.c_ubyte), _p(out, C.c_double)))
+        return keep, out
+
     def refine_reasons(self):
-        """Per row of the last refine_correspondences call: 0 kept, 1 not in the mask, 2 triangulation, 3 affine test."""
+        """Per row of the last refine_correspondences / refine_points call: 0 kept, 1 not in the mask, 2 triangulation,
+        3 affine test."""
         r = np.empty(self.n, dtype=np.uint8)
         self._check(self.lib.mh_get_refine_reasons(self._h, _p(r, C.c_ubyte), int(self.n)))
         return r
@@ -434,6 +449,12 @@ class Engine:
         out = np.zeros((int(moves), 16), dtype=np.int32)
         self._check(self.lib.mh_get_core_components(self._h, _p(out, C.c_int), int(moves)))
         return out
+
+    def set_estimator(self, name: str):
+        """mh_set_estimator: "haf" (default) or "3pt" (point-only least squares)."""
+        if name not in ESTIMATORS:
+            raise ValueError(f"unknown estimator {name!r} (haf | 3pt)")
+        self._check(self.lib.mh_set_estimator(self._h, ESTIMATORS[name]))
 
     def reestimate(self, labels):
         labels = _i32(labels)

@@ -420,7 +420,7 @@ void mh_destroy(mh_engine* e)
     if (e->h_sel) (void)hipHostFree(e->h_sel);
     for (int b = 0; b < 2; ++b) { e->sel_orig[b].release(); e->sel_cand_H[b].release(); }
     e->sel_counts.release(); e->sel_rec.release(); e->sel_scores.release(); e->sel_gathered.release(); e->sel_out_H.release();
-    e->sel_records.release(); e->sel_counter.release(); e->sel_keys.release(); e->sel_refit.release(); e->sel_refit_ctr.release();
+    e->sel_records.release(); e->sel_counter.release(); e->sel_keys.release(); e->sel_refit.release(); e->sel_refit_ctr.release(); e->r3_scratch.release();
     e->ms_partial2.release(); e->ms_ctl.release(); e->ms_pcnt2.release(); e->ms_ticks.release();
     for (int q = 0; q < mh_engine::PF_DEPTH; ++q) { e->pf_H[q].release(); e->pf_samples[q].release(); if (e->pf_ev[q]) (void)hipEventDestroy(e->pf_ev[q]); }
     e->best_key.release(); e->H32.release(); e->fb_pairs.release();
@@ -703,6 +703,7 @@ int mh_device_buffer(mh_engine* e, int which, void** ptr_dev, unsigned long long
     case MH_BUF_LABELS: *ptr_dev = e->ew_label.p; *bytes = sizeof(int) * (size_t)e->n; break;
     case MH_BUF_COST: *ptr_dev = e->cost.p; *bytes = sizeof(int) * (size_t)e->n * e->cost_L; break;
     case MH_BUF_GATHERED_SCORES: *ptr_dev = e->sel_gathered.p; *bytes = sizeof(int) * e->sel_gathered.cap; break;
+    case MH_BUF_LABEL_COUNTS: *ptr_dev = e->label_counts.p; *bytes = sizeof(int) * std::min<size_t>(e->label_counts.cap, (size_t)e->m); break;
     default: return fail(MH_ERR_INVALID, "unknown buffer id");
     }
     if (!*ptr_dev) return fail(MH_ERR_NOT_SET, "buffer has not been produced yet");
@@ -800,9 +801,10 @@ int mh_set_tuning(mh_engine* e, int key, int value)
     if (key == 26 && value >= 0 && value <= 4096) { e->tune_sweep_slices = value; return MH_OK; }
     if (key == 27 && (value == 0 || value == 1)) { e->tune_cost32_slice_major = value; return MH_OK; }
     if (key == 28 && (value == 0 || value == 1)) { e->tune_cost32_batched = value; return MH_OK; }
+    if (key == 34 && value >= 0 && value <= 2) { e->tune_3pt_form = value; return MH_OK; }     // the 3-point fit's member form (0 by size)
 #else
-    if ((key == 26 || key == 27 || key == 28) && value == 0) return MH_OK;
-    if (key == 16 || key == 26 || key == 27 || key == 28)
+    if ((key == 26 || key == 27 || key == 28 || key == 34) && value == 0) return MH_OK;
+    if (key == 16 || key == 26 || key == 27 || key == 28 || key == 34)
         return fail(MH_ERR_INVALID, "this schedule variant exists only in a library built with -DMH_TUNING");
 #endif
     return fail(MH_ERR_INVALID, "unknown tuning key");

@@ -167,6 +167,9 @@ struct mh_engine {
     DevBuf<int> ms_ctl, ms_pcnt2;            // the persistent tail of a mean-shift batch (meanshift.hip, k_ms_persist)
     int ms_persist_per_cu = -1, ms_persist_per_cu6 = -1;   // workgroups of k_ms_persist<10> / <6> a compute unit holds (-1: not queried; a failed query is not kept)
     int tune_select_refine = 0;              // key 30: mh_select_greedy refits each round's winner to its inliers before the claim (0 = off)
+    int estimator = MH_ESTIMATOR_HAF;        // mh_set_estimator: the re-estimator of mh_reestimate, mh_labeling_step and the key-30 refit
+    DevBuf<int> r3_scratch;                  // member lists of the 3-point re-estimator (reestimate3pt.hip)
+    int tune_3pt_form = 0;                   // key 34 (measurement libraries): 0 by size, 1 the match loop, 2 the compacted member lists (reestimate3pt.hip)
     DevBuf<double> sel_refit;                // the refit (9 doubles) and its inlier count
     DevBuf<int> sel_refit_ctr;
     DevBuf<double> ms_rs;                    // the mean-shift index of one call (meanshift.hip, k_ms_indexed): rows in cell order,
@@ -303,6 +306,8 @@ int quiesce(mh_engine* e);
 int join_xchg(mh_engine* e);
 // inlier counts of m models over the points p: FP32 pre-test where its preconditions hold, the FP64 sweep otherwise (capi_score.hip)
 int score_models(mh_engine* e, const Points& p, const double* Hs, int m, double thr2, const unsigned char* dmask, int* counts_dev);
+// the engine's re-estimator over labels_dev (n ints) for models H_dev (Nh x 9, in place) — HAF or 3-point (capi_label.hip)
+int launch_estimator(mh_engine* e, const int* labels_dev, int Nh, double* H_dev, int* counts_dev);
 // the exchange's stream and events (capi_select.hip); the second stream of the prefetch queue (capi_score.hip)
 int ensure_xchg_stream(mh_engine* e);
 int ensure_side_stream(mh_engine* e);

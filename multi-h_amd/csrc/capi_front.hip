@@ -195,14 +195,42 @@ int mh_refine_correspondences(mh_engine* e, const double F[9], const double e1[2
     });
 }
 
+int mh_refine_points(mh_engine* e, const double F[9], const double e1[2], const double e2[2], const unsigned char* in_mask,
+                     unsigned char* keep, double* refined)
+{
+    return guarded([&]() -> int {
+    int rc = require_points(e);
+    if (rc) return rc;
+    if (!F || !e1 || !e2 || !keep || !refined) return fail(MH_ERR_INVALID, "null argument");
+    HIPCHK(e->ref_keep.reserve((size_t)e->n + 2));
+    HIPCHK(e->ref_out.reserve((size_t)e->n * 8));
+    HIPCHK(e->ref_reason.reserve((size_t)e->n + 2));
+    e->ref_reason_n = 0;
+    const unsigned char* dmask = nullptr;
+    if (in_mask) {
+        HIPCHK(e->ref_in.reserve((size_t)e->n + 2));
+        HIPCHK(hipMemcpyAsync(e->ref_in.p, in_mask, e->n, hipMemcpyHostToDevice, e->stream));
+        dmask = e->ref_in.p;
+    }
+    HIPCHK(hipMemsetAsync(e->ref_out.p, 0, sizeof(double) * 4 * (size_t)e->n, e->stream));
+    const Affines none{ nullptr, nullptr, nullptr, nullptr };
+    HIPCHK(launch_refine_points(e->pts(), none, F, e1, e2, dmask, e->ref_keep.p, e->ref_out.p, e->ref_reason.p, e->stream, 1));
+    HIPCHK(hipMemcpyAsync(keep, e->ref_keep.p, e->n, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(refined, e->ref_out.p, sizeof(double) * 4 * (size_t)e->n, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->ref_reason_n = e->n;
+    return MH_OK;
+    });
+}
+
 int mh_get_refine_reasons(mh_engine* e, unsigned char* reason, int n)
 {
     return guarded([&]() -> int {
     int rc = enter(e);
     if (rc) return rc;
     if (!reason) return fail(MH_ERR_INVALID, "null argument");
-    if (e->ref_reason_n <= 0) return fail(MH_ERR_NOT_SET, "no mh_refine_correspondences call to report on");
-    if (n != e->ref_reason_n) return fail(MH_ERR_INVALID, "the last mh_refine_correspondences call had another number of rows");
+    if (e->ref_reason_n <= 0) return fail(MH_ERR_NOT_SET, "no mh_refine_correspondences / mh_refine_points call to report on");
+    if (n != e->ref_reason_n) return fail(MH_ERR_INVALID, "the last mh_refine_correspondences / mh_refine_points call had another number of rows");
     HIPCHK(hipMemcpyAsync(reason, e->ref_reason.p, (size_t)n, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return MH_OK;

@@ -398,22 +398,52 @@ int mh_get_core_components(mh_engine* e, int* out, int moves)
     });
 }
 
+} // extern "C"
+
+namespace mhe {
+
+int launch_estimator(mh_engine* e, const int* labels_dev, int Nh, double* H_dev, int* counts_dev)
+{
+    ScopedTimer t(e, MH_K_REESTIMATE);
+    if (e->estimator == MH_ESTIMATOR_3PT) {
+        HIPCHK(e->r3_scratch.reserve(reestimate_3pt_scratch_ints(e->n, Nh)));
+        HIPCHK(launch_reestimate_3pt(e->pts(), labels_dev, Nh, e->epi, H_dev, counts_dev, e->r3_scratch.p, e->stream,
+                                     e->tune_3pt_form));
+        return MH_OK;
+    }
+    Affines a{ e->a11.p, e->a12.p, e->a21.p, e->a22.p };
+    HIPCHK(launch_reestimate(e->pts(), a, labels_dev, Nh, e->epi, H_dev, counts_dev, e->stream));
+    return MH_OK;
+}
+
+} // namespace mhe
+
+extern "C" {
+
+int mh_set_estimator(mh_engine* e, int estimator)
+{
+    return guarded([&]() -> int {
+    int rc = enter(e);
+    if (rc) return rc;
+    if (estimator != MH_ESTIMATOR_HAF && estimator != MH_ESTIMATOR_3PT) return fail(MH_ERR_INVALID, "unknown estimator");
+    e->estimator = estimator;
+    return MH_OK;
+    });
+}
+
 int mh_reestimate(mh_engine* e, const int* labels, double* H_out)
 {
     return guarded([&]() -> int {
     int rc = require_models(e);
     if (rc) return rc;
     if (!labels) return fail(MH_ERR_INVALID, "labels is null");
-    if (!e->have_aff) return fail(MH_ERR_NOT_SET, "affinities are not set");
+    if (e->estimator == MH_ESTIMATOR_HAF && !e->have_aff) return fail(MH_ERR_NOT_SET, "affinities are not set");
     if (!e->have_epi) return fail(MH_ERR_NOT_SET, "fundamental matrix / epipole are not set");
     HIPCHK(e->labels_pts.reserve(e->n));
     HIPCHK(e->label_counts.reserve(e->m));
     HIPCHK(hipMemcpyAsync(e->labels_pts.p, labels, sizeof(int) * e->n, hipMemcpyHostToDevice, e->stream));
-    Affines a{ e->a11.p, e->a12.p, e->a21.p, e->a22.p };
-    {
-        ScopedTimer t(e, MH_K_REESTIMATE);
-        HIPCHK(launch_reestimate(e->pts(), a, e->labels_pts.p, e->m, e->epi, e->H.p, e->label_counts.p, e->stream));
-    }
+    rc = launch_estimator(e, e->labels_pts.p, e->m, e->H.p, e->label_counts.p);
+    if (rc) return rc;
     e->cost_L = 0;
     if (H_out) {
         HIPCHK(hipMemcpyAsync(H_out, e->H.p, sizeof(double) * 9 * e->m, hipMemcpyDeviceToHost, e->stream));
@@ -429,7 +459,9 @@ int mh_labeling_step(mh_engine* e, int warm, int* labeling, double* energy, int*
     int rc = require_models(e);
     if (rc) return rc;
     if (!labeling) return fail(MH_ERR_INVALID, "labeling is null");
-    if (!e->have_aff || !e->have_epi) return fail(MH_ERR_NOT_SET, "affinities / epipolar geometry are not set");
+    if (e->estimator == MH_ESTIMATOR_HAF && (!e->have_aff || !e->have_epi))
+        return fail(MH_ERR_NOT_SET, "affinities / epipolar geometry are not set");
+    if (!e->have_epi) return fail(MH_ERR_NOT_SET, "epipolar geometry is not set");
     rc = do_data_cost(e);
     if (rc) return rc;
     const int* init_dev = nullptr;
@@ -449,11 +481,8 @@ int mh_labeling_step(mh_engine* e, int warm, int* labeling, double* energy, int*
     HIPCHK(e->labels_pts.reserve(e->n));
     HIPCHK(e->label_counts.reserve(e->m));
     hipLaunchKernelGGL(k_shift_labels, grid, blk, 0, e->stream, e->n, e->ew_label.p, -1, e->labels_pts.p); // :547-568
-    Affines a{ e->a11.p, e->a12.p, e->a21.p, e->a22.p };
-    {
-        ScopedTimer t(e, MH_K_REESTIMATE);
-        HIPCHK(launch_reestimate(e->pts(), a, e->labels_pts.p, e->m, e->epi, e->H.p, e->label_counts.p, e->stream));
-    }
+    rc = launch_estimator(e, e->labels_pts.p, e->m, e->H.p, e->label_counts.p);
+    if (rc) return rc;
     e->cost_L = 0;                                               // models changed
     HIPCHK(hipMemcpyAsync(labeling, e->labels_pts.p, sizeof(int) * e->n, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));

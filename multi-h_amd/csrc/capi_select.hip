@@ -95,14 +95,20 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
     // every other rank-local error (returning here would leave the peers waiting in the all-gather), and the setting itself
     // travels in the records' mode word (bit 1) beside the residual mode (bit 0): ranks that disagree about it would claim with
     // different models, so k_sel_claim raises error 3 on any mismatch of the word.
+    // Under the 3-point estimator (mh_set_estimator) the refit is the point-only fit and needs the epipolar geometry alone; the
+    // estimator of the refit travels in the mode word too (bit 2, set only when winners are refitted: an estimator no refit uses
+    // cannot make the ranks' claims differ).
     const bool refine = e->tune_select_refine != 0;
-    const bool refine_usable = refine && e->have_aff && e->have_epi;
+    const bool refit3 = e->estimator == MH_ESTIMATOR_3PT;
+    const bool refine_usable = refine && e->have_epi && (refit3 || e->have_aff);
     if (refine && !refine_usable)
-        local_failure(MH_ERR_NOT_SET, "mh_select_greedy with refitted winners (mh_set_tuning key 30) needs affinities and the epipolar geometry");
+        local_failure(MH_ERR_NOT_SET, refit3 ? "mh_select_greedy with refitted winners (mh_set_tuning key 30) needs the epipolar geometry"
+                                             : "mh_select_greedy with refitted winners (mh_set_tuning key 30) needs affinities and the epipolar geometry");
     if (refine) {
         HIPCHK(e->labels_pts.reserve((size_t)n));
         HIPCHK(e->sel_refit.reserve(10));
         HIPCHK(e->sel_refit_ctr.reserve(2));
+        if (refit3) HIPCHK(e->r3_scratch.reserve(reestimate_3pt_scratch_ints(n, 1)));
     }
     if (!sharded && M <= 0) local_failure(MH_ERR_NOT_SET, "model set is empty");
     else if (M != mine) local_failure(MH_ERR_INVALID, "the resident model set is not this rank's shard of total_m hypotheses");
@@ -206,7 +212,7 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
         const int local_err = local_rc != MH_OK ? 1 : 0;
         const bool gather_scores = sharded && first && longest > 0;      // north_star's exchange, once per batch
         HIPCHK(launch_sel_argmax(e->sel_counts.p, orig, Mc, my_off, key_local, gather_scores ? e->sel_scores.p : nullptr, s));
-        HIPCHK(launch_sel_record(e->sel_counts.p, orig, Hs, Mc, my_off, key_local, local_err, symmetric | (refine ? 2 : 0), my_record, s));
+        HIPCHK(launch_sel_record(e->sel_counts.p, orig, Hs, Mc, my_off, key_local, local_err, symmetric | (refine ? 2 : 0) | (refine && refit3 ? 4 : 0), my_record, s));
         if (sharded) {
             if (gather_scores) {
                 rc = exchange(e, e->sel_scores.p, e->sel_gathered.p, sizeof(int) * (size_t)longest, s);
@@ -223,7 +229,7 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
             // every rank holds all the points and the same records: the refit is computed redundantly, identically
             Affines aff{ e->a11.p, e->a12.p, e->a21.p, e->a22.p };
             HIPCHK(launch_sel_refit(e->pts(), aff, e->epi, records, world, thr2, need, e->mask.p, e->labels_pts.p, e->sel_refit.p,
-                                    e->sel_refit_ctr.p, e->sel_refit_ctr.p + 1, s, symmetric));
+                                    e->sel_refit_ctr.p, e->sel_refit_ctr.p + 1, s, symmetric, refit3 ? e->r3_scratch.p : nullptr));
             refit = e->sel_refit.p;
         }
         HIPCHK(launch_sel_claim(e->pts(), records, world, gather_scores && !local_err ? key_check : nullptr, thr2, need, e->mask.p, e->sel_rec.p,
@@ -236,7 +242,7 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
         if (e->h_sel[4] != 0)                            // every rank sees the same word, so every rank leaves here
             return fail(e->h_sel[4] == 3 ? MH_ERR_INVALID : MH_ERR_HIP,
                         e->h_sel[4] == 2 ? "greedy selection: the gathered score vector and the ranks' records disagree about the winner"
-                        : e->h_sel[4] == 3 ? "greedy selection: the ranks are not in the same residual mode (mh_set_residual_mode) or do not agree on refitted winners (mh_set_tuning key 30)"
+                        : e->h_sel[4] == 3 ? "greedy selection: the ranks are not in the same residual mode (mh_set_residual_mode) or do not agree on refitted winners (mh_set_tuning key 30) or the estimator (mh_set_estimator)"
                                            : "greedy selection: a rank reported an error");
         const int best = e->h_sel[0];
         if (best < need) break;

@@ -53,16 +53,6 @@ __device__ __forceinline__ void insert_large3(u64 (&tp)[3], u64 k)         // tp
 // ---------------------------------------------------------------------------
 namespace {
 
-__device__ __forceinline__ void mat3_mul_dev(const double* a, const double* b, double* c)
-{
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double s = 0.0;
-            for (int k = 0; k < 3; ++k) s = s + a[3 * i + k] * b[3 * k + j];
-            c[3 * i + j] = s;
-        }
-}
-
 __device__ __forceinline__ void normalize3_dev(const double* pts, double* out, double* T)
 {
     double cx = 0.0, cy = 0.0;
@@ -81,30 +71,12 @@ __device__ __forceinline__ void normalize3_dev(const double* pts, double* out, d
     T[0] = ratio; T[1] = 0; T[2] = -cx * ratio; T[3] = 0; T[4] = ratio; T[5] = -cy * ratio; T[6] = 0; T[7] = 0; T[8] = 1;
 }
 
-__device__ __forceinline__ void similarity_inverse_dev(const double* T, double* Ti)
-{
-    const double ir = 1.0 / T[0];
-    Ti[0] = ir; Ti[1] = 0; Ti[2] = -T[2] * ir; Ti[3] = 0; Ti[4] = ir; Ti[5] = -T[5] * ir; Ti[6] = 0; Ti[7] = 0; Ti[8] = 1;
-}
-
 __device__ inline bool homography_3pt_linear_dev(const double* pts1, const double* pts2, const double* F, double* H)
 {
-    double p1[6], p2[6], T1[9], T2[9], T1i[9], T2i[9], T2it[9], tmp[9], Fn[9];
+    double p1[6], p2[6], T1[9], T2[9], T2i[9], Fn[9], e0, e1;
     normalize3_dev(pts1, p1, T1);
     normalize3_dev(pts2, p2, T2);
-    similarity_inverse_dev(T1, T1i);
-    similarity_inverse_dev(T2, T2i);
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) T2it[3 * i + j] = T2i[3 * j + i];
-    mat3_mul_dev(T2it, F, tmp);
-    mat3_mul_dev(tmp, T1i, Fn);
-    double FFt[9], Fnt[9], v[9], d[3];
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Fnt[3 * i + j] = Fn[3 * j + i];
-    mat3_mul_dev(Fn, Fnt, FFt);
-    jacobi_sym_dev(3, FFt, v, d);
-    int jm = 0;
-    for (int j = 1; j < 3; ++j) if (d[j] < d[jm]) jm = j;
-    const double e0 = v[0 * 3 + jm] / v[2 * 3 + jm];
-    const double e1 = v[1 * 3 + jm] / v[2 * 3 + jm];
+    normalised_epipolar_dev(F, T1, T2, T2i, Fn, e0, e1);
     double A[18], rhs[6];
     for (int i = 0; i < 3; ++i) {
         const double x1 = p1[2 * i], y1 = p1[2 * i + 1], x2 = p2[2 * i], y2 = p2[2 * i + 1];
@@ -125,28 +97,9 @@ __device__ inline bool homography_3pt_linear_dev(const double* pts1, const doubl
         for (int i = 0; i < 6; ++i) s = s + A[3 * i + a] * rhs[i];
         Atb[a] = s;
     }
-    // sym_eig_solve3: x = pinv(AtA) Atb
-    double w[3], h3[3] = { 0.0, 0.0, 0.0 };
-    jacobi_sym_dev(3, AtA, v, w);
-    double cut = 0.0;
-    for (int k = 0; k < 3; ++k) cut = cut + fabs(w[k]);
-    cut = cut * (2.0 * 2.220446049250313e-16);
-    for (int k = 0; k < 3; ++k) {
-        if (fabs(w[k]) <= cut) continue;
-        double proj = 0.0;
-        for (int i = 0; i < 3; ++i) proj = proj + v[3 * i + k] * Atb[i];
-        proj = proj / w[k];
-        for (int i = 0; i < 3; ++i) h3[i] = h3[i] + proj * v[3 * i + k];
-    }
-    double Hn[9];
-    Hn[6] = h3[0]; Hn[7] = h3[1]; Hn[8] = h3[2];
-    Hn[3] = e1 * h3[0] - Fn[0]; Hn[4] = e1 * h3[1] - Fn[1]; Hn[5] = e1 * h3[2] - Fn[2];
-    Hn[0] = e0 * h3[0] + Fn[3]; Hn[1] = e0 * h3[1] + Fn[4]; Hn[2] = e0 * h3[2] + Fn[5];
-    mat3_mul_dev(T2i, Hn, tmp);
-    mat3_mul_dev(tmp, T1, H);
-    bool ok = true;
-    for (int i = 0; i < 9; ++i) if (!(fabs(H[i]) <= 1.7976931348623157e308)) ok = false;      // std::isfinite
-    return ok;
+    double h3[3];
+    sym_eig_solve3_dev(AtA, Atb, h3);                      // x = pinv(AtA) Atb
+    return assemble_3pt_dev(h3, e0, e1, Fn, T1, T2i, H);
 }
 
 } // namespace

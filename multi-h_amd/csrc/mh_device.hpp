@@ -225,4 +225,81 @@ __device__ inline void jacobi_sym_dev(int n, double* a, double* v, double* d)
     for (int i = 0; i < n; ++i) d[i] = a[i * n + i];
 }
 
+// ---------------------------------------------------------------------------
+// Pieces of GetHomography3PT without refinement (M/MultiH.cpp:995-1050) shared by the device's two 3-point fits — the
+// post-filter's trials (compat.hip) and the per-label point-only re-estimator (reestimate3pt.hip) — operation for operation the
+// host's Homography3PTLinear (host/merge_step.cpp: mat3_mul, similarity_inverse, jacobi3 = jacobi_sym_dev(3), sym_eig_solve3).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void mat3_mul_dev(const double* a, const double* b, double* c)
+{
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double s = 0.0;
+            for (int k = 0; k < 3; ++k) s = s + a[3 * i + k] * b[3 * k + j];
+            c[3 * i + j] = s;
+        }
+}
+
+// T.inv() of the similarity T = [r 0 tx; 0 r ty; 0 0 1], computed from T (:1009, :1054)
+__device__ __forceinline__ void similarity_inverse_dev(const double* T, double* Ti)
+{
+    const double ir = 1.0 / T[0];
+    Ti[0] = ir; Ti[1] = 0; Ti[2] = -T[2] * ir; Ti[3] = 0; Ti[4] = ir; Ti[5] = -T[5] * ir; Ti[6] = 0; Ti[7] = 0; Ti[8] = 1;
+}
+
+// Fn = T2^-T F T1^-1 (:1009) and the epipole (e0, e1, 1) of Fn: the eigenvector of Fn Fn^T with the smallest eigenvalue (:1013-1017);
+// T2i receives T2^-1
+__device__ inline void normalised_epipolar_dev(const double* F, const double* T1, const double* T2, double* T2i, double* Fn,
+                                               double& e0, double& e1)
+{
+    double T1i[9], T2it[9], tmp[9];
+    similarity_inverse_dev(T1, T1i);
+    similarity_inverse_dev(T2, T2i);
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) T2it[3 * i + j] = T2i[3 * j + i];
+    mat3_mul_dev(T2it, F, tmp);
+    mat3_mul_dev(tmp, T1i, Fn);
+    double FFt[9], Fnt[9], v[9], d[3];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Fnt[3 * i + j] = Fn[3 * j + i];
+    mat3_mul_dev(Fn, Fnt, FFt);
+    jacobi_sym_dev(3, FFt, v, d);
+    int jm = 0;
+    for (int j = 1; j < 3; ++j) if (d[j] < d[jm]) jm = j;
+    e0 = v[0 * 3 + jm] / v[2 * 3 + jm];
+    e1 = v[1 * 3 + jm] / v[2 * 3 + jm];
+}
+
+// h3 = pinv(AtA) Atb through the eigen-decomposition, eigenvalues within 2 eps sum|w| of zero dropped (sym_eig_solve3);
+// AtA (3 x 3, symmetric) is destroyed
+__device__ inline void sym_eig_solve3_dev(double* AtA, const double* Atb, double* h3)
+{
+    double v[9], w[3];
+    jacobi_sym_dev(3, AtA, v, w);
+    double cut = 0.0;
+    for (int k = 0; k < 3; ++k) cut = cut + fabs(w[k]);
+    cut = cut * (2.0 * 2.220446049250313e-16);
+    h3[0] = 0.0; h3[1] = 0.0; h3[2] = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        if (fabs(w[k]) <= cut) continue;
+        double proj = 0.0;
+        for (int i = 0; i < 3; ++i) proj = proj + v[3 * i + k] * Atb[i];
+        proj = proj / w[k];
+        for (int i = 0; i < 3; ++i) h3[i] = h3[i] + proj * v[3 * i + k];
+    }
+}
+
+// the rows of the normalised H from its third row (:1040-1050), H = T2^-1 Hn T1 (:1054); true when every entry is finite
+__device__ inline bool assemble_3pt_dev(const double* h3, double e0, double e1, const double* Fn, const double* T1,
+                                        const double* T2i, double* H)
+{
+    double Hn[9], tmp[9];
+    Hn[6] = h3[0]; Hn[7] = h3[1]; Hn[8] = h3[2];
+    Hn[3] = e1 * h3[0] - Fn[0]; Hn[4] = e1 * h3[1] - Fn[1]; Hn[5] = e1 * h3[2] - Fn[2];
+    Hn[0] = e0 * h3[0] + Fn[3]; Hn[1] = e0 * h3[1] + Fn[4]; Hn[2] = e0 * h3[2] + Fn[5];
+    mat3_mul_dev(T2i, Hn, tmp);
+    mat3_mul_dev(tmp, T1, H);
+    bool ok = true;
+    for (int i = 0; i < 9; ++i) if (!(fabs(H[i]) <= 1.7976931348623157e308)) ok = false;      // std::isfinite
+    return ok;
+}
+
 } // namespace mh

@@ -94,14 +94,24 @@ hipError_t launch_data_cost(const Points& p, const double* H, int Nh, double lam
 hipError_t launch_reestimate(const Points& p, const Affines& a, const int* labels, int Nh,
                              const Epipolar& ep, double* H, int* counts, hipStream_t s);
 
+// --- reestimate3pt.hip: the point-only re-estimator (GetHomography3PT without refinement over every label's members) ---
+// scratch: reestimate_3pt_scratch_ints(p.n, Nh) ints (member lists and their offsets); a label with < 3 members or a fit that
+// is not finite keeps its H; counts (nullable): member count per label
+size_t reestimate_3pt_scratch_ints(int n, int Nh);
+// form: 0 by size (the product's rule), 1 the match loop over the whole label array (scratch unused), 2 the compacted member lists
+hipError_t launch_reestimate_3pt(const Points& p, const int* labels, int Nh, const Epipolar& ep, double* H, int* counts,
+                                 int* scratch, hipStream_t s, int form = 0);
+
 hipError_t launch_haf_point(const Points& p, const Affines& a, const Epipolar& ep, double locality,
                             double* H_out /* n x 9, nullable */, double* feat_out /* n x 10, nullable */,
                             hipStream_t s);
 
 // --- refine.hip -------------------------------------------------------------
+// points_only: step 1 alone (no affinity is read, a may be null), out is n x 4 (x1 y1 x2 y2) and every triangulated row is kept
 hipError_t launch_refine_points(const Points& p, const Affines& a, const double F[9], const double e1[2],
                                 const double e2[2], const unsigned char* in_mask, unsigned char* keep,
-                                double* out /* n x 8 */, unsigned char* reason /* n: MH_REFINE_* */, hipStream_t s);
+                                double* out /* n x 8, points_only: n x 4 */, unsigned char* reason /* n: MH_REFINE_* */, hipStream_t s,
+                                int points_only = 0);
 
 // --- meanshift.hip ----------------------------------------------------------
 constexpr int MS_BATCH = 256;   // climbs per batch: part of the definition of the seed order (meanshift.hip; the oracle draws alike)
@@ -272,7 +282,7 @@ hipError_t launch_argmin_labels(const int* cost, int L, int n, int* label, long 
 hipError_t launch_sel_pack_points(const Points& p, const unsigned char* mask, double* cx1, double* cy1, double* cx2, double* cy2,
                                   int* count, hipStream_t s);
 // one rank's offer in a round of the greedy selection: 88 bytes, the unit of the sharded exchange
-struct SelRecord { unsigned long long key; double H[9]; int err; int mode; };      // mode: bit 0 the rank's residual mode, bit 1 refitted winners (key 30); the ranks' words must agree
+struct SelRecord { unsigned long long key; double H[9]; int err; int mode; };      // mode: bit 0 the rank's residual mode, bit 1 refitted winners (key 30), bit 2 those refits by the 3-point estimator (mh_set_estimator); the ranks' words must agree
 static_assert(sizeof(SelRecord) == 88, "the exchanged record is 88 bytes");
 hipError_t launch_sel_argmax(const int* counts, const int* orig, int Mc, unsigned int my_off, unsigned long long* key,
                              int* scores_full, hipStream_t s);
@@ -292,9 +302,10 @@ hipError_t launch_sel_claim(const Points& p, const SelRecord* records, int world
 // r05 (mh_set_tuning key 30): the round's winner refitted to its inliers in the support set by the per-label HAF least squares
 // (one label); refit = 9 doubles + the refit's inlier count; launch_sel_claim takes it in the winner's place when it is finite and
 // explains at least as many points.  labels: n ints, counter / label_count: one int each (scratch).
+// scratch3 non-null: the point-only 3-point fit instead (launch_reestimate_3pt, reestimate_3pt_scratch_ints(n, 1) ints; a unused)
 hipError_t launch_sel_refit(const Points& p, const Affines& a, const Epipolar& ep, const SelRecord* records, int world, double thr2,
                             int need, const unsigned char* mask, int* labels, double* refit, int* counter, int* label_count,
-                            hipStream_t s, int symmetric);
+                            hipStream_t s, int symmetric, int* scratch3 = nullptr);
 hipError_t launch_sel_publish(int* rec, unsigned long long* keys, SelRecord* my_record, int need, int* h_rec_dev, hipStream_t s);
 hipError_t launch_best_publish(unsigned long long* key, int* h_best_dev, hipStream_t s);
 hipError_t launch_best_fused(int* scores, int world, int longest, int base, int rem, int* h_best_dev, int* clear,

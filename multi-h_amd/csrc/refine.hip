@@ -16,6 +16,8 @@
 //      n1 onto beta*n2 — the reference inverts the 6x6 KKT matrix (:1211-1219); its closed form is
 //      used here (lambda_k = (n1_k - p.A_col_k) / (p.p), A' = A + p lambda^T, p = beta n2).
 // Outputs per point: keep flag, corrected x1 y1 x2 y2, optimal affinity a11 a12 a21 a22.
+// With points_only (mh_refine_points) step 1 alone runs: every triangulated row is kept, the output is x1 y1 x2 y2 and no
+// affinity is read.
 #include "mh_kernels.hpp"
 
 namespace mh {
@@ -68,7 +70,8 @@ k_refine_points(const double* __restrict__ x1, const double* __restrict__ y1,
                 const double* __restrict__ a21p, const double* __restrict__ a22p, int N, RefineGeom g,
                 const unsigned char* __restrict__ in_mask, unsigned char* __restrict__ keep,
                 double* __restrict__ out /* N x 8: x1 y1 x2 y2 a11 a12 a21 a22 */,
-                unsigned char* __restrict__ reason /* N: MH_REFINE_* — which stage of :807-838 a row left at */)
+                unsigned char* __restrict__ reason /* N: MH_REFINE_* — which stage of :807-838 a row left at */,
+                int points_only /* step 1 alone: out is N x 4, the affinities are not read */)
 {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
@@ -136,7 +139,6 @@ k_refine_points(const double* __restrict__ x1, const double* __restrict__ y1,
     }
     const double valInf = 1 / f12 + (c * c) / (a * a + f22 * c * c);
     if (valInf < bestS) return;                                // :1170-1175 -> dropped at :816-817
-    reason[n] = 3;                                             // MH_REFINE_AFFINE_TEST until it passes
     // point1 = (0, bestT, 1); line2 = F3 point1; point2 = (-l0 l2, -l1 l2, l0^2 + l1^2) / (l0^2 + l1^2)
     const double l0 = F3[1] * bestT + F3[2], l1 = F3[4] * bestT + F3[5], l2 = F3[7] * bestT + F3[8];
     const double w2 = l0 * l0 + l1 * l1;
@@ -149,6 +151,14 @@ k_refine_points(const double* __restrict__ x1, const double* __restrict__ y1,
     // R2^-1 = (1/s2) [-e2x e2y; -e2y -e2x]
     const double vx = (-g.e2x * p2x + g.e2y * p2y) / s2 + qx;
     const double vy = (-g.e2y * p2x - g.e2x * p2y) / s2 + qy;
+    if (points_only) {                                         // mh_refine_points: no affinity, no steps 2-3
+        double* o = out + 4 * (size_t)n;
+        o[0] = ux; o[1] = uy; o[2] = vx; o[3] = vy;
+        keep[n] = 1;
+        reason[n] = 0;                                         // MH_REFINE_KEPT
+        return;
+    }
+    reason[n] = 3;                                             // MH_REFINE_AFFINE_TEST until it passes
 
     // ---- 2. affine consistency ----
     const double A11 = a11p[n], A12 = a12p[n], A21 = a21p[n], A22 = a22p[n];
@@ -189,14 +199,14 @@ k_refine_points(const double* __restrict__ x1, const double* __restrict__ y1,
 
 hipError_t launch_refine_points(const Points& p, const Affines& a, const double F[9], const double e1[2],
                                 const double e2[2], const unsigned char* in_mask, unsigned char* keep,
-                                double* out, unsigned char* reason, hipStream_t s)
+                                double* out, unsigned char* reason, hipStream_t s, int points_only)
 {
     if (p.n <= 0) return hipSuccess;
     RefineGeom g;
     for (int i = 0; i < 9; ++i) g.F[i] = F[i];
     g.e1x = e1[0]; g.e1y = e1[1]; g.e2x = e2[0]; g.e2y = e2[1];
     hipLaunchKernelGGL(k_refine_points, dim3((p.n + 255) / 256), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2,
-                       a.a11, a.a12, a.a21, a.a22, p.n, g, in_mask, keep, out, reason);
+                       a.a11, a.a12, a.a21, a.a22, p.n, g, in_mask, keep, out, reason, points_only);
     return hipGetLastError();
 }
 

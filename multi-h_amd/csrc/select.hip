@@ -160,7 +160,7 @@ k_sel_claim(const double* __restrict__ x1, const double* __restrict__ y1, const 
         int err = 0;
         for (int r = 0; r < world; ++r) if (records[r].err) err = records[r].err;
         if (key_check && *key_check != kg) err = 2;
-        for (int r = 1; r < world; ++r) if (records[r].mode != records[0].mode) err = 3;      // forward on one rank, symmetric on another; or winners refitted on one only
+        for (int r = 1; r < world; ++r) if (records[r].mode != records[0].mode) err = 3;      // forward on one rank, symmetric on another; or winners refitted on one only, or by another estimator
         if (err) rec[4] = err;
     }
     if (!kg || best < need) return;
@@ -434,12 +434,13 @@ hipError_t launch_sel_claim(const Points& p, const SelRecord* records, int world
 // the round's winner refitted to its inliers: labels (n ints), refit (10 doubles), counter (1 int) are scratch of the caller
 hipError_t launch_sel_refit(const Points& p, const Affines& a, const Epipolar& ep, const SelRecord* records, int world, double thr2,
                             int need, const unsigned char* mask, int* labels, double* refit, int* counter, int* label_count,
-                            hipStream_t s, int symmetric)
+                            hipStream_t s, int symmetric, int* scratch3)
 {
     const dim3 grid((p.n + 255) / 256);
     hipLaunchKernelGGL(k_sel_winner_labels, grid, dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, records, world, thr2, need, mask,
                        labels, refit, symmetric);
-    hipError_t he = launch_reestimate(p, a, labels, 1, ep, refit, label_count, s);
+    hipError_t he = scratch3 ? launch_reestimate_3pt(p, labels, 1, ep, refit, label_count, scratch3, s)
+                             : launch_reestimate(p, a, labels, 1, ep, refit, label_count, s);
     if (he != hipSuccess) return he;
     he = hipMemsetAsync(counter, 0, sizeof(int), s);
     if (he != hipSuccess) return he;

@@ -16,6 +16,13 @@
 #include "merge_step.h"
 #include "multih_hip.h"
 
+// The entry points of the point-only route are referenced weakly because the class is also linked against the suite's
+// stand-in engine (tests/fake_engine.cpp, the host-boundary test under AddressSanitizer), which defines the ABI up to
+// mh_set_tuning and not these two.  Against libmultih_hip.so they always resolve; where they do not, the HAF route runs
+// unchanged and the point-only route fails with a message instead of a link error.
+#pragma weak mh_set_estimator
+#pragma weak mh_refine_points
+
 namespace {
 
 // A matrix that OWNS its storage, filled from a raw array: allocate, then copy.  (cv::Mat(rows, cols, type, ptr) would
@@ -138,6 +145,20 @@ bool MultiH::Process(std::vector<cv::Point2d> _srcPoints, std::vector<cv::Point2
     return Process();
 }
 
+bool MultiH::Process(std::vector<cv::Point2d> _srcPoints, std::vector<cv::Point2d> _dstPoints)
+{
+    printf("[Multi-H] Processing has been started.\n");
+    src_points_original = _srcPoints;
+    dst_points_original = _dstPoints;
+    affinities_original.clear();
+    return Run(true);
+}
+
+bool MultiH::Process()
+{
+    return Run(false);
+}
+
 bool MultiH::EnsureEngine()
 {
     if (!engine && engine_tuning.empty() && engine_pool_enabled()) {
@@ -190,7 +211,8 @@ bool multih::FilterCorrespondencesByEpipolarGeometry(std::vector<cv::Point2d>& s
                                                      int hypotheses, int metric, int device, std::vector<unsigned char>* mask_out)
 {
     const size_t n = srcPoints.size();
-    if (n < 8 || dstPoints.size() != n || affines.size() != n) return false;
+    const bool points_only = affines.empty();              // no affinities: filter the points alone
+    if (n < 8 || dstPoints.size() != n || (!points_only && affines.size() != n)) return false;
     mh_engine* e = BorrowEngine(device);
     if (!e) return false;
     std::vector<double> s(2 * n), d(2 * n);
@@ -210,20 +232,26 @@ bool multih::FilterCorrespondencesByEpipolarGeometry(std::vector<cv::Point2d>& s
     size_t k = 0;
     for (size_t i = 0; i < n; ++i)
         if (mask[i]) {
-            if (k != i) { srcPoints[k] = srcPoints[i]; dstPoints[k] = dstPoints[i]; affines[k] = affines[i]; }
+            if (k != i) { srcPoints[k] = srcPoints[i]; dstPoints[k] = dstPoints[i]; if (!points_only) affines[k] = affines[i]; }
             ++k;
         }
-    srcPoints.resize(k); dstPoints.resize(k); affines.resize(k);
+    srcPoints.resize(k); dstPoints.resize(k);
+    if (!points_only) affines.resize(k);
     return true;
 }
 
-bool MultiH::Process()
+bool MultiH::Run(bool points_only)
 {
     if (src_points_original.size() < 8 || dst_points_original.size() != src_points_original.size() ||
-        affinities_original.size() != src_points_original.size()) {
+        (!points_only && affinities_original.size() != src_points_original.size())) {
         std::cerr << "Error: Features are not set!\n";                       // M/MultiH.cpp:48
         return false;
     }
+    if (points_only && initial_homographies.empty() && init_mode == INIT_STABLE_SETS) {
+        std::cerr << "Error: the stable point sets (INIT_STABLE_SETS) need affinities; the point-only Process() cannot use them\n";
+        return false;
+    }
+    point_only_run = points_only;
     const bool timing = std::getenv("MULTIH_TIMING") != nullptr;          // diagnostic: where Process() spends its time
     const auto t_process = std::chrono::system_clock::now();
     auto stage = [&](const char* what) {
@@ -231,6 +259,16 @@ bool MultiH::Process()
                            std::chrono::duration<double, std::milli>(std::chrono::system_clock::now() - t_process).count());
     };
     if (!EnsureEngine()) return false;
+    // the re-estimator of the loop and of the proposal refit (sticky on the engine, and engines are reused)
+    const int est = points_only ? MH_ESTIMATOR_3PT : estimator;
+    if (!mh_set_estimator || !mh_refine_points) {
+        if (est != MH_ESTIMATOR_HAF) {
+            std::cerr << "Error: the engine library has no point-only entry points (mh_set_estimator, mh_refine_points)\n";
+            return false;
+        }
+    } else if (!Check(mh_set_estimator(engine, est), "mh_set_estimator")) {
+        return false;
+    }
     stage("engine");
 
     // GetFundamentalMatrixAndRefineData (M/MultiH.cpp:52, :770-848; §8(f) row 4): with
@@ -250,11 +288,12 @@ bool MultiH::Process()
     for (int i = 0; i < N; ++i) {
         s[2 * i] = src_points[i].x; s[2 * i + 1] = src_points[i].y;
         d[2 * i] = dst_points[i].x; d[2 * i + 1] = dst_points[i].y;
+        if (points_only) continue;
         const cv::Mat& A = affinities[i];
         a[4 * i] = A.at<double>(0, 0); a[4 * i + 1] = A.at<double>(0, 1);
         a[4 * i + 2] = A.at<double>(1, 0); a[4 * i + 3] = A.at<double>(1, 1);
     }
-    if (!Check(mh_set_correspondences(engine, s.data(), d.data(), a.data(), N), "mh_set_correspondences"))
+    if (!Check(mh_set_correspondences(engine, s.data(), d.data(), points_only ? nullptr : a.data(), N), "mh_set_correspondences"))
         return false;
     stage("correspondences on the device");
 
@@ -275,14 +314,19 @@ bool MultiH::Process()
         if (degenerate_case) {
             printf("[Multi-H] Degenerate case, the fundamental matrix cannot be estimated.\n");
         } else {
-            // :807-838 on the GPU: Hartley-Sturm correction, affine consistency filter, optimal affinity
+            // :807-838 on the GPU: Hartley-Sturm correction, affine consistency filter, optimal affinity (the point-only
+            // route: the correction alone, mh_refine_points)
             double e1[2];
             std::vector<unsigned char> keep(N, 0);
-            std::vector<double> refined(8 * (size_t)N);
-            if (!Check(mh_epipoles(engine, fundamental_matrix, e1, epipole_2), "mh_epipoles") ||
-                !Check(mh_refine_correspondences(engine, fundamental_matrix, e1, epipole_2, mask.data(), keep.data(),
-                                                 refined.data()),
-                       "mh_refine_correspondences"))
+            const int stride = points_only ? 4 : 8;
+            std::vector<double> refined(stride * (size_t)N);
+            if (!Check(mh_epipoles(engine, fundamental_matrix, e1, epipole_2), "mh_epipoles"))
+                return false;
+            if (points_only ? !Check(mh_refine_points(engine, fundamental_matrix, e1, epipole_2, mask.data(), keep.data(), refined.data()),
+                                     "mh_refine_points")
+                            : !Check(mh_refine_correspondences(engine, fundamental_matrix, e1, epipole_2, mask.data(), keep.data(),
+                                                               refined.data()),
+                                     "mh_refine_correspondences"))
                 return false;
             std::vector<unsigned char> reason(N, 0);
             if (!Check(mh_get_refine_reasons(engine, reason.data(), N), "mh_get_refine_reasons")) return false;
@@ -296,10 +340,10 @@ bool MultiH::Process()
             std::vector<cv::Mat> a2;
             for (int i = 0; i < N; ++i)
                 if (keep[i]) {
-                    const double* r = &refined[8 * (size_t)i];
+                    const double* r = &refined[stride * (size_t)i];
                     s2.push_back(cv::Point2d(r[0], r[1]));
                     d2.push_back(cv::Point2d(r[2], r[3]));
-                    a2.push_back(OwnedMat(2, 2, r + 4));
+                    if (!points_only) a2.push_back(OwnedMat(2, 2, r + 4));
                 }
             printf("[Multi-H] %d points kept from the initial %d after filtering.\n", (int)s2.size(), N);   // :840
             if (log_to_console)
@@ -315,11 +359,12 @@ bool MultiH::Process()
                 for (int i = 0; i < K; ++i) {
                     ss[2 * i] = src_points[i].x; ss[2 * i + 1] = src_points[i].y;
                     dd[2 * i] = dst_points[i].x; dd[2 * i + 1] = dst_points[i].y;
+                    if (points_only) continue;
                     const cv::Mat& A = affinities[i];
                     aa[4 * i] = A.at<double>(0, 0); aa[4 * i + 1] = A.at<double>(0, 1);
                     aa[4 * i + 2] = A.at<double>(1, 0); aa[4 * i + 3] = A.at<double>(1, 1);
                 }
-                if (!Check(mh_set_correspondences(engine, ss.data(), dd.data(), aa.data(), K), "mh_set_correspondences"))
+                if (!Check(mh_set_correspondences(engine, ss.data(), dd.data(), points_only ? nullptr : aa.data(), K), "mh_set_correspondences"))
                     return false;
             }
         }
@@ -802,11 +847,12 @@ void MultiH::HandleDegenerateCase()
         for (int i = 0; i < N; ++i) {
             s[2 * i] = src_points_original[i].x; s[2 * i + 1] = src_points_original[i].y;
             d[2 * i] = dst_points_original[i].x; d[2 * i + 1] = dst_points_original[i].y;
+            if (point_only_run) continue;                                      // (affinities_original is empty)
             const cv::Mat& A = affinities_original[i];
             a[4 * i] = A.at<double>(0, 0); a[4 * i + 1] = A.at<double>(0, 1);
             a[4 * i + 2] = A.at<double>(1, 0); a[4 * i + 3] = A.at<double>(1, 1);
         }
-        if (!Check(mh_set_correspondences(engine, s.data(), d.data(), a.data(), N), "mh_set_correspondences")) return;
+        if (!Check(mh_set_correspondences(engine, s.data(), d.data(), point_only_run ? nullptr : a.data(), N), "mh_set_correspondences")) return;
     }
     const int M = std::max(proposal_hypotheses, 1000);
     if (!Check(mh_propose_dlt4(engine, proposal_seed ^ 0xdeadull, 0, M), "mh_propose_dlt4")) return;

@@ -46,6 +46,13 @@ public:
     bool Process(std::vector<cv::Point2d> _srcPoints, std::vector<cv::Point2d> _dstPoints,
                  std::vector<cv::Mat> _affines);
     bool Process();
+    // The point-only route (no affinities; the reference has no such route): the same stages as Process() with the
+    // per-correspondence refinement reduced to the Hartley-Sturm correction (mh_refine_points) and every homography refit —
+    // the loop's re-estimation and the proposal refit — by the 3-point least squares GetHomography3PT without LM refinement
+    // (MH_ESTIMATOR_3PT), which needs only the points and F.  GetAffinities() then returns an empty vector.  The stable point
+    // sets (INIT_STABLE_SETS) need per-point HAF homographies: with that initialisation this call prints an error and
+    // returns false.
+    bool Process(std::vector<cv::Point2d> _srcPoints, std::vector<cv::Point2d> _dstPoints);
 
     // M/MultiH.h:61-75
     int GetLabel(int idx) { return labeling[idx]; }
@@ -120,6 +127,10 @@ public:
     // explains at least as many (mh_set_tuning key 30).  A hypothesis fitted to four matches explains 60-70 % of its plane;
     // what it leaves behind used to feed models that sit between two planes.  Default on.
     void SetProposalRefit(bool on) { proposal_refit = on; }
+    // The re-estimator of Process() with affinities (the point-only Process() always takes ESTIMATOR_3PT): the HAF
+    // non-minimal fit (M/MultiH.cpp:913-989, the reference's; default) or the 3-point least squares from the points alone.
+    enum { ESTIMATOR_HAF = 0, ESTIMATOR_3PT = 1 };
+    void SetEstimator(int e) { estimator = e; }
     // Multi-GPU propose stage (BASELINE configs[3] and [4]): one process per GPU, every rank holds all
     // correspondences and owns a contiguous shard of each hypothesis batch (the hypotheses are a pure function of
     // (seed, counter), so the union over ranks is the single-GPU batch).  In the first greedy round the ranks all-gather
@@ -196,6 +207,8 @@ protected:
     int proposal_hypotheses = 10000;
     int proposal_max_models = 32;
     bool proposal_refit = true;
+    int estimator = ESTIMATOR_HAF;
+    bool point_only_run = false;                 // the last Process() was the point-only one
     int fixed_iterations = 0;
     int iter_hypotheses = 0, iter_max_new = 4;
     int fundamental_hypotheses = 4000;
@@ -214,6 +227,7 @@ protected:
     void* shard_ctx = nullptr;
 
     bool EnsureEngine();
+    bool Run(bool points_only);           // Process() with or without affinities
     bool UploadModels();
     bool DownloadModels(int count);
     bool ProposeInitialModels();          // north_star propose: DLT batch + greedy selection

@@ -16,6 +16,10 @@
 //                  [--f-metric opencv|sampson]   what the two F estimations compare with their thresholds (MultiH::SetFundamentalMetric)
 //                  [--stages <file>]   write the stage table as one JSON object: rows loaded, after the load filter, in
 //                                Process()'s RANSAC mask, after OptimalTriangulation, after distanceError <= 1 (M/MultiH.cpp:807-838)
+//                  [--points]   point-only correspondences: 4 numbers per input row (x1 y1 x2 y2, no affinity) and 5 per output
+//                                row (x1 y1 x2 y2 label); runs MultiH::Process(src, dst), the point-only route (3-point refits)
+//                  [--estimator haf|3pt]   the re-estimator of the route with affinities (MultiH::SetEstimator; haf, the default,
+//                                is the reference's); --points always takes 3pt
 //                  [--ranks N]   one process per GPU (rank r on device r), the hypothesis batches sharded over the ranks and
 //                                exchanged by RCCL (host/rccl_transport.cpp: ncclAllGather on the engine's stream); this
 //                                process becomes rank 0 and starts the others before anything touches the GPU.  Every rank
@@ -44,12 +48,17 @@
 // multih::FilterCorrespondencesByEpipolarGeometry); *loaded = rows read from the file.
 static bool LoadPointsFromFile(std::vector<cv::Point2d>& srcPoints, std::vector<cv::Point2d>& dstPoints,
                                std::vector<cv::Mat>& affines, const char* file, double filter_threshold,
-                               unsigned long long seed, int metric, int device, int* loaded)
+                               unsigned long long seed, int metric, int device, int* loaded, bool points_only)
 {
     std::ifstream infile(file);
     if (!infile.is_open()) return false;
     double x1, y1, x2, y2, a1, a2, a3, a4;
-    while (infile >> x1 >> y1 >> x2 >> y2 >> a1 >> a2 >> a3 >> a4) {
+    if (points_only)                                                 // --points: x1 y1 x2 y2 per row, affines stays empty
+        while (infile >> x1 >> y1 >> x2 >> y2) {
+            srcPoints.push_back(cv::Point2d(x1, y1));
+            dstPoints.push_back(cv::Point2d(x2, y2));
+        }
+    else while (infile >> x1 >> y1 >> x2 >> y2 >> a1 >> a2 >> a3 >> a4) {
         srcPoints.push_back(cv::Point2d(x1, y1));
         dstPoints.push_back(cv::Point2d(x2, y2));
         const double a[4] = { a1, a2, a3, a4 };
@@ -70,6 +79,12 @@ static bool SavePointsToFile(std::vector<cv::Point2d>& srcPoints, std::vector<cv
 {
     std::ofstream outfile(file, std::ios::out);
     if (!outfile.is_open()) return false;
+    if (affines.empty()) {                                           // the point-only route: x1 y1 x2 y2 label
+        for (size_t i = 0; i < srcPoints.size(); ++i)
+            outfile << srcPoints[i].x << " " << srcPoints[i].y << " " << dstPoints[i].x << " " << dstPoints[i].y << " " << labels[i]
+                    << std::endl;
+        return true;
+    }
     for (size_t i = 0; i < srcPoints.size(); ++i)
         outfile << srcPoints[i].x << " " << srcPoints[i].y << " " << dstPoints[i].x << " " << dstPoints[i].y << " "
                 << affines[i].at<double>(0, 0) << " " << affines[i].at<double>(0, 1) << " "
@@ -83,7 +98,7 @@ int main(int argc, char** argv)
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
                      "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] "
-                     "[--stages file] [--ranks n]\n";
+                     "[--stages file] [--points] [--estimator haf|3pt] [--ranks n]\n";
         return 2;
     }
     double thrF = 2.6, thrH = 2.2, locality = 0.005, lambda = 0.5;     // M/main.cpp:55-59
@@ -93,10 +108,19 @@ int main(int argc, char** argv)
     double load_filter = 2.0;                                          // M/main.cpp:400
     int f_metric = MultiH::FUND_EPIPOLAR_MAX;
     std::string epi, neighbourhood = "knn", stages_path;
-    for (int i = 3; i + 1 < argc; i += 2) {
+    bool points_only = false;
+    int estimator = MultiH::ESTIMATOR_HAF;
+    for (int i = 3; i < argc; ++i) {
         const std::string k = argv[i];
-        const char* v = argv[i + 1];
+        if (k == "--points") { points_only = true; continue; }      // the one option without a value
+        if (i + 1 >= argc) break;
+        const char* v = argv[++i];
         if (k == "--epipolar") epi = v;
+        else if (k == "--estimator") {
+            if (std::string(v) == "haf") estimator = MultiH::ESTIMATOR_HAF;
+            else if (std::string(v) == "3pt") estimator = MultiH::ESTIMATOR_3PT;
+            else { std::cerr << "--estimator: haf or 3pt\n"; return 2; }
+        }
         else if (k == "--thrF") thrF = atof(v);
         else if (k == "--thrH") thrH = atof(v);
         else if (k == "--locality") locality = atof(v);
@@ -209,7 +233,7 @@ int main(int argc, char** argv)
     std::vector<cv::Mat> origAffines;
     int rows_loaded = 0;
     if (!LoadPointsFromFile(srcPointsOrig, dstPointsOrig, origAffines, argv[1], epi.empty() ? load_filter : 0.0, seed, f_metric,
-                            comm ? rank : 0, &rows_loaded)) {
+                            comm ? rank : 0, &rows_loaded, points_only)) {
         std::cerr << "cannot read " << argv[1] << " (or the load filter failed)\n";
         return finish(1);
     }
@@ -235,7 +259,10 @@ int main(int argc, char** argv)
     }
     if (neighbourhood == "radius") multiH->SetNeighbourRadius(1.0 / locality);        // the complete list of M/MultiH.cpp:252-253 (see MultiH.h)
     else if (neighbourhood == "approx") multiH->SetNeighbourApprox(4, 32, 0x464c414e4eull + seed);   // ... as FLANN's default search answers it
-    if (!multiH->Process(srcPointsOrig, dstPointsOrig, origAffines)) { delete multiH; return finish(1); }
+    multiH->SetEstimator(estimator);
+    const bool processed = points_only ? multiH->Process(srcPointsOrig, dstPointsOrig)
+                                       : multiH->Process(srcPointsOrig, dstPointsOrig, origAffines);
+    if (!processed) { delete multiH; return finish(1); }
     const std::string out_path = rank == 0 ? std::string(argv[2]) : std::string(argv[2]) + ".rank" + std::to_string(rank);
     {
         // the stage table: where the rows of the input file go before the loop sees them
