@@ -77,7 +77,11 @@ MH_API int mh_set_epipolar(mh_engine* e, const double F[9], const double e2[2]);
  * M/MultiH.cpp:537).  Multiplicity semantics of setNeighbors are reproduced (SURVEY A-2). */
 MH_API int mh_set_neighbors_csr(mh_engine* e, const int* rowptr, const int* col, int n);
 /* Exact k-NN hit list built on the GPU in float32 (x1,y1,x2,y2) space — the engine's own
- * replacement for the FLANN radius search (deviation documented). */
+ * replacement for the FLANN radius search (deviation documented).
+ * k in [1, 32], k < n.  Query i's hits are the first k candidates j != i by (d(i, j), j), d the float32
+ * squared distance.  Only a finite d makes a hit: if some query has fewer than k candidates at finite
+ * float32 distance (coordinates so far apart that d overflows), the call fails with MH_ERR_INVALID and
+ * leaves the current graph untouched — through the grid as through the exhaustive pass. */
 MH_API int mh_build_neighbors_knn(mh_engine* e, int k);
 /* The same k nearest hits, but only those within `radius` of the query (radius <= 0: no cut): the reference's
  * radius (1/locality_lambda) with the list bounded the way FLANN's default search bounds it in practice

@@ -281,7 +281,7 @@ static int device_sym_graph(mh_engine* e, const int* rowptr_dev, int stride, con
     HIPCHK(hipMemcpyAsync(&total, e->gb_start.p + n, sizeof(int), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     if (info[2] == 2) return fail(MH_ERR_INVALID, "rowptr must be non-decreasing");
-    if (info[2]) return fail(MH_ERR_INVALID, "neighbour index out of range (non-finite coordinates?)");
+    if (info[2]) return fail(MH_ERR_INVALID, "neighbour index out of range (non-finite coordinates, or fewer than k neighbours at finite float32 distance?)");
     if (info[0]) return fail(MH_ERR_OVERFLOW, "too many neighbour entries");
     if (info[1] > SYM_MAX_ROW) {
         // a very dense neighbourhood: build on the host (any row length)

@@ -117,7 +117,8 @@ k_knn_merge(int N, int k, int splits, const float* __restrict__ part_d, const in
 // or more cells away in x or in y is at least (r - 0.01) c away in the plane (0.01 c covers the float32 rounding of the
 // cell index, 5 10^-5 cells at most), hence in the 4-D space, so once the k-th best squared distance is below
 // ((r - 0.01) c)^2 (1 - 10^-5) the walk ends.  Same float32 distance, same (distance, index) order, same self-exclusion:
-// the same table as k_knn, entry for entry (tests: grid against the exhaustive pass on ties, duplicates, clusters).
+// the same table as k_knn, entry for entry (tests: grid against the exhaustive pass on ties, duplicates, clusters).  A query
+// with fewer than k candidates at finite distance keeps (+inf, 0x7fffffff) pads in both; k_hits_filter rejects the table.
 struct KnnGrid { float x0, y0, inv_c, c; int G; };
 
 __device__ __forceinline__ int grid_coord(float v, float v0, float inv_c, int G)
@@ -207,7 +208,9 @@ k_knn_grid(int N, int k, KnnGrid g, const int* __restrict__ start, const float4*
                 const int j = orig[valid ? t : s];
                 const float dx = me.x - o.x, dy = me.y - o.y, dz = me.z - o.z, dw = me.w - o.w;
                 const float d = ((dx * dx + dy * dy) + dz * dz) + dw * dw;
-                unsigned long long pass = __ballot(valid && (d < kd || (d == kd && j < ki)));
+                // d < +inf: a candidate at infinite (overflowed) float32 distance is no hit, as in k_knn, where it never beats
+                // the pads; without it (+inf, j) ties with the pads (+inf, 0x7fffffff) and the index lets it in
+                unsigned long long pass = __ballot(valid && d < __builtin_inff() && (d < kd || (d == kd && j < ki)));
                 while (pass) {
                     const int b = (int)__builtin_ctzll(pass);
                     pass &= pass - 1;
