@@ -208,9 +208,14 @@ int mh_residual_matrix(mh_engine* e, double thr2, double* R_host, int* counts)
     if (e->pf_count == 1 && e->tune_dlt_first && e->ev_side_pre) HIPCHK(hipStreamWaitEvent(e->stream, e->ev_side_pre, 0));
     {
         ScopedTimer t(e, MH_K_RESIDUAL);
+        SweepLaunch how;
+        how.slices = e->tune_sweep_slices;
+        how.slice_major = e->tune_sweep_slices > 0 ? 1 : 0;
+        how.counts_zeroed = e->counts_zeroed;
+        how.resident_grid = resident;
+        how.resident_ctl = e->sweep_ctl.p;
         HIPCHK(launch_residual(e->pts(), e->H.p, e->m, thr2, e->R.p, e->ldr, e->counts.p,
-                               e->residual_mode == MH_RESIDUAL_SYMMETRIC ? -1 : e->tune_residual_variant,
-                               e->stream, e->counts_zeroed, resident, e->sweep_ctl.p, e->tune_sweep_slices, e->tune_sweep_slices > 0 ? 1 : 0));
+                               e->residual_mode == MH_RESIDUAL_SYMMETRIC ? -1 : e->tune_residual_variant, e->stream, how));
     }
     e->counts_zeroed = false;
     e->counts_fresh = true;

@@ -34,11 +34,19 @@ struct Epipolar {           // passed by value to kernels
 inline long long residual_ld(int n) { return ((long long)n + 15) & ~15ll; }
 
 // --- residual.hip -----------------------------------------------------------
+// How a sweep is laid out on the chip; the defaults are the launcher's own choices.
+struct SweepLaunch {
+    int slices = 0;                 // point slices; 0 = the launcher's rule
+    bool contiguous = false;        // with slices > 0 (tuning): each slice a contiguous run of tiles instead of every slices-th tile
+    int swapxy = 0;                 // tuning: the slice index as the fastest grid dimension
+    bool counts_zeroed = false;     // the caller has cleared counts already
+    int resident_grid = 0;          // > 0: that many workgroups walk the work items as a resident grid (needs resident_ctl) ...
+    int* resident_ctl = nullptr;    // ... through these two ints, zero between launches
+    int slice_major = 0;            // resident grid: consecutive items = the slices of one model block
+};
 // variant: 0 default; tuning knob for bench sweeps (see residual.hip).
 hipError_t launch_residual(const Points& p, const double* H, int M, double thr2, double* R,
-                           long long ldr, int* counts, int variant, hipStream_t s, bool counts_zeroed = false,
-                           int resident_grid = 0, int* resident_ctl = nullptr, int slices = 0 /* 0: the launcher's rule */,
-                           int slice_major = 0 /* resident grid: consecutive items = the slices of one model block */);
+                           long long ldr, int* counts, int variant, hipStream_t s, const SweepLaunch& how);
 // workgroups of the product's materialising sweep that one compute unit holds at a time (occupancy query)
 int residual_workgroups_per_cu();
 hipError_t launch_score(const Points& p, const double* H, int M, double thr2,

@@ -8,7 +8,9 @@
 //     u  = ((h0*x + h1*y) + h2) / s        v = ((h3*x + h4*y) + h5) / s
 //     d2 = (x2-u)^2 + (y2-v)^2             inlier  <=>  d2 < thr^2   (strict)
 //
-// k_residual — the HBM-bound kernel of the roofline run.
+// k_residual<Cfg> — one kernel template over a configuration type (namespace cfg below: a base with every switch at its
+// default, and the six product forms as named types that state only what they set).  cfg::Sweep is the HBM-bound
+// kernel of the roofline run.
 //   Work split: one workgroup (256 threads = 4 waves) owns MC consecutive
 //   models and sweeps ALL points, so the per-model inlier count is finished
 //   inside the workgroup (ballot + s_bcnt1 per wave, 4-way LDS add at the end)
@@ -21,7 +23,7 @@
 //   per workgroup from the XCD's 4 MiB L2, where it stays resident on every
 //   XCD; HBM sees the 8 B/pair store stream only.
 //   Algorithmic bytes per launch: 8*N*M (R) + 32*N + 72*M + 4*M.
-// k_score — same sweep without the stores (FP64-VALU/division bound).
+// cfg::Score / cfg::ScoreSym (and their masked forms) — the same sweep without the stores (FP64-VALU/division bound).
 
 #include <type_traits>
 
@@ -35,18 +37,49 @@ namespace mh {
 typedef double __attribute__((address_space(1))) gdouble;
 typedef char __attribute__((address_space(1))) gchar;
 
-// PPL = points per lane (even), MC = models per workgroup.
-// WRITE_R: materialise the matrix.  MASK: per-point activity mask (score only).
-// NT: non-temporal stores for the R stream.  FAST: shared-reciprocal division (mh_device.hpp).
+// What a sweep is compiled for: one type whose members are the switches.  A form derives from Base and states what it sets;
+// PPL = points per lane (even) and MC = models per workgroup have no default.
+// WRITE_R: materialise the matrix.  MASK: per-point activity mask (score only).  SYM: + the backward transfer through adj(H).
+// NT: non-temporal stores for the R stream.  FAST: shared-reciprocal division (mh_device.hpp), else the compiler's.
+// HSGPR: the current model's coefficients through the scalar unit instead of LDS broadcasts.
 // LEAN: per tile and wave, a wave-uniform test — every lane holds real points (a full tile), every point meets the
 // fast division's precondition, no point is masked out — selects, for the models whose own preconditions hold
 // (model_pre, model_far), a sweep without any per-pair bookkeeping: no fallback branch, no exec masking around the stores,
 // no validity mask on the inlier ballot.  Same arithmetic, same bits; what goes is scalar and branch work.
-// TILED (tuning): R stored tile-major — [model block][point tile][MC][TILE] — so that a workgroup writes one contiguous
-// 128-KiB block per tile instead of MC row segments.
+// SEMI: LEAN also for models not provably `far`, behind one wave-wide range test per model.
+// Measurement switches, off in every product form — CALIB: stores without the arithmetic.  CONTRACT: fused multiply-adds,
+// NOT bit-exact.  TILED: R stored tile-major — [model block][point tile][MC][TILE] — so that a workgroup writes one contiguous
+// 128-KiB block per tile instead of MC row segments.  SF: the lean store's cache-policy bits in asm.  MINW: waves per SIMD
+// the registers are capped for (__launch_bounds__).
+namespace cfg {
+struct Base {
+    static constexpr bool WRITE_R = false, MASK = false, SYM = false, NT = false, FAST = true, HSGPR = false, LEAN = false, SEMI = true;
+    static constexpr bool CALIB = false, CONTRACT = false, TILED = false;
+    static constexpr int SF = 0, MINW = 1;
+};
+// PPL 4, MC 64 (r05; 16 before: same-box A/B 7.21 / 7.11 / 7.06 ms for 16 / 32 / 64 models per work item — the per-tile work is
+// shared by more models), the lean sweep wherever a tile and a model allow it, non-temporal 16-B stores (r03: the kernel runs at
+// the board's power cap, its time is its energy; nt stores — nothing of R is ever re-read — cost 2.7 % less energy
+// per launch than plain ones, profiles/archive/r03_energy.json)
+// ... and the nine coefficients of the current model through the scalar unit (s_load from H, uniform address) instead
+// of LDS broadcasts into VGPRs: the twelve linear-form operations then read one operand from SGPRs; 2.5 % less energy.
+struct Sweep : Base { static constexpr int PPL = 4, MC = 64; static constexpr bool WRITE_R = true, NT = true, HSGPR = true, LEAN = true; };
+struct SweepSym : Base { static constexpr int PPL = 4, MC = 16; static constexpr bool WRITE_R = true, NT = true, HSGPR = true, SYM = true; };
+struct Score : Base { static constexpr int PPL = 4, MC = 16; static constexpr bool HSGPR = true, LEAN = true; };
+struct ScoreMasked : Score { static constexpr bool MASK = true; };
+struct ScoreSym : Base { static constexpr int PPL = 4, MC = 16; static constexpr bool SYM = true; };
+struct ScoreSymMasked : ScoreSym { static constexpr bool MASK = true; };
+template <class... C> constexpr bool no_measurement_switch = ((!C::CALIB && !C::CONTRACT && !C::TILED && C::SF == 0 && C::MINW == 1 && C::FAST && C::PPL == 4) && ...);
+static_assert(no_measurement_switch<Sweep, SweepSym, Score, ScoreMasked, ScoreSym, ScoreSymMasked>, "a measurement switch in a product form");
+} // namespace cfg
+using ProductSweep = cfg::Sweep;    // what mh_residual_matrix launches; the occupancy query that sizes its resident grid asks about the same type
+
+// Which configurations launch_rs may run on the resident grid (k_residual_resident is instantiated for these alone).
+template <class Cfg> constexpr bool on_resident_grid = false;
+template <> constexpr bool on_resident_grid<ProductSweep> = true;
+
 // residual_wg: the work of ONE workgroup — model block bx (MC models), point slice by.
-template <int PPL, int MC, bool WRITE_R, bool MASK, bool NT, bool FAST, bool CALIB, bool HSGPR,
-          bool SYM, bool CONTRACT, bool LEAN, bool TILED, int SF, bool SEMI>
+template <class Cfg>
 __device__ __forceinline__ void
 residual_wg(const double* __restrict__ x1, const double* __restrict__ y1,
             const double* __restrict__ x2, const double* __restrict__ y2, int N,
@@ -54,6 +87,9 @@ residual_wg(const double* __restrict__ x1, const double* __restrict__ y1,
             long long ldr, int* __restrict__ counts, const unsigned char* __restrict__ mask,
             int psplit, double bx0, double bx1, double by0, double by1, const int bx, const int by)
 {
+    constexpr int PPL = Cfg::PPL, MC = Cfg::MC, SF = Cfg::SF;
+    constexpr bool WRITE_R = Cfg::WRITE_R, MASK = Cfg::MASK, NT = Cfg::NT, FAST = Cfg::FAST, CALIB = Cfg::CALIB, HSGPR = Cfg::HSGPR,
+                   SYM = Cfg::SYM, CONTRACT = Cfg::CONTRACT, LEAN = Cfg::LEAN, TILED = Cfg::TILED, SEMI = Cfg::SEMI;
     constexpr int CH = PPL / 2;                 // 16-B chunks per lane
     constexpr int WAVE_PTS = 64 * PPL;          // points per wave per tile
     constexpr int TILE = 4 * WAVE_PTS;          // points per workgroup per tile
@@ -302,9 +338,8 @@ residual_wg(const double* __restrict__ x1, const double* __restrict__ y1,
 }
 
 // One workgroup per (model block, point slice), placed by the hardware dispatcher.
-template <int PPL, int MC, bool WRITE_R, bool MASK, bool NT, bool FAST, bool CALIB = false, bool HSGPR = false,
-          bool SYM = false, bool CONTRACT = false, bool LEAN = false, bool TILED = false, int SF = 0, bool SEMI = true, int MINW = 1>
-__global__ void __launch_bounds__(256, MINW)
+template <class Cfg>
+__global__ void __launch_bounds__(256, Cfg::MINW)
 k_residual(const double* __restrict__ x1, const double* __restrict__ y1,
            const double* __restrict__ x2, const double* __restrict__ y2, int N,
            const double* __restrict__ H, int M, double thr2, double* __restrict__ R,
@@ -315,8 +350,7 @@ k_residual(const double* __restrict__ x1, const double* __restrict__ y1,
     // chunks of the same rows of R
     const int bx = swapxy ? blockIdx.y : blockIdx.x;
     const int by = swapxy ? blockIdx.x : blockIdx.y;
-    residual_wg<PPL, MC, WRITE_R, MASK, NT, FAST, CALIB, HSGPR, SYM, CONTRACT, LEAN, TILED, SF, SEMI>(
-        x1, y1, x2, y2, N, H, M, thr2, R, ldr, counts, mask, psplit, bx0, bx1, by0, by1, bx, by);
+    residual_wg<Cfg>(x1, y1, x2, y2, N, H, M, thr2, R, ldr, counts, mask, psplit, bx0, bx1, by0, by1, bx, by);
 }
 
 // The same work items walked by a RESIDENT grid (r04): as many workgroups as the chip holds at this kernel's occupancy
@@ -325,9 +359,8 @@ k_residual(const double* __restrict__ x1, const double* __restrict__ y1,
 // Measured against one hardware-dispatched workgroup per item at 50k x 100k: 7.27-7.31 ms vs 7.48-7.70 (the launch and
 // retirement of 37 500 workgroups, and a dispatcher that refills every slot the moment it frees, cost more than the
 // counter).  Holding the kernel to 80 registers for a sixth wave does not work: the scalar spills need the 81st.
-template <int PPL, int MC, bool WRITE_R, bool MASK, bool NT, bool FAST, bool CALIB = false, bool HSGPR = false,
-          bool SYM = false, bool CONTRACT = false, bool LEAN = false, bool TILED = false, int SF = 0, bool SEMI = true, int MINW = 1>
-__global__ void __launch_bounds__(256, MINW) __attribute__((amdgpu_num_vgpr(88)))      // 5 waves per SIMD and 72 registers left for k_dlt4_lds
+template <class Cfg>
+__global__ void __launch_bounds__(256, Cfg::MINW) __attribute__((amdgpu_num_vgpr(88)))      // 5 waves per SIMD and 72 registers left for k_dlt4_lds
 k_residual_resident(const double* __restrict__ x1, const double* __restrict__ y1,
                     const double* __restrict__ x2, const double* __restrict__ y2, int N,
                     const double* __restrict__ H, int M, double thr2, double* __restrict__ R,
@@ -351,8 +384,7 @@ k_residual_resident(const double* __restrict__ x1, const double* __restrict__ y1
         int bx, by;
         if (slice_major) { bx = item / psplit; by = item - bx * psplit; }
         else { by = item / gx; bx = item - by * gx; }
-        residual_wg<PPL, MC, WRITE_R, MASK, NT, FAST, CALIB, HSGPR, SYM, CONTRACT, LEAN, TILED, SF, SEMI>(
-            x1, y1, x2, y2, N, H, M, thr2, R, ldr, counts, mask, psplit, bx0, bx1, by0, by1, bx, by);
+        residual_wg<Cfg>(x1, y1, x2, y2, N, H, M, thr2, R, ldr, counts, mask, psplit, bx0, bx1, by0, by1, bx, by);
         __syncthreads();                        // the item's LDS (coefficients, flags, counts) and s_item are rewritten by the next one
     }
     if (threadIdx.x == 0 && atomicAdd(&ctl[1], 1) == (int)gridDim.x - 1) {
@@ -361,19 +393,17 @@ k_residual_resident(const double* __restrict__ x1, const double* __restrict__ y1
     }
 }
 
-template <int PPL, int MC, bool WRITE_R, bool MASK, bool NT, bool FAST = true, bool CALIB = false, bool HSGPR = false,
-          bool SYM = false, bool CONTRACT = false, bool LEAN = false, bool TILED = false, int SF = 0, bool SEMI = true, int MINW = 1>
+template <class Cfg>
 static hipError_t launch_rs(const Points& p, const double* H, int M, double thr2, double* R,
-                            long long ldr, int* counts, const unsigned char* mask, hipStream_t s,
-                            int force_psplit = 0, int swapxy = 0, bool counts_zeroed = false, int resident_grid = 0,
-                            int* resident_ctl = nullptr, int slice_major = 0)
+                            long long ldr, int* counts, const unsigned char* mask, hipStream_t s, const SweepLaunch& how = {})
 {
+    constexpr int PPL = Cfg::PPL, MC = Cfg::MC;
     if (M <= 0 || p.n <= 0) return hipSuccess;
     const int gx = (M + MC - 1) / MC;
     const int tile = 256 * PPL;
     const int ntiles = (p.n + tile - 1) / tile;
     int psplit = 1;
-    if (WRITE_R) {
+    if (Cfg::WRITE_R) {
         // The materialising sweep: aim at ~37 500 workgroups whatever the batch size (at least 4 point slices for a long
         // sweep).  r04, tools/shard_proxy.py on the per-rank shards of BASELINE configs[3]: with the r03 rule (2 048
         // workgroups below 1 024 model blocks, else 4 slices) the 12 500-hypothesis shard of an 8-GPU run ran 2 346
@@ -394,136 +424,76 @@ static hipError_t launch_rs(const Points& p, const double* H, int M, double thr2
         // that tail (measured 7.95 -> 7.79 ms at 50k x 100k, tools/kernel_sweep.py RV=104)
         psplit = 4;
     }
-    if (force_psplit > 0) psplit = force_psplit < ntiles ? force_psplit : ntiles;
-    bool contiguous = false;
-    if (force_psplit < 0) { psplit = -force_psplit < ntiles ? -force_psplit : ntiles; contiguous = true; }
-    if (psplit > 1 && !counts_zeroed) {
+    const bool forced = how.slices > 0, contiguous = forced && how.contiguous;
+    if (forced) psplit = how.slices < ntiles ? how.slices : ntiles;
+    if (psplit > 1 && !how.counts_zeroed) {
         hipError_t e = hipMemsetAsync(counts, 0, sizeof(int) * (size_t)M, s);
         if (e != hipSuccess) return e;
     }
-    constexpr bool PRODUCT_SWEEP = WRITE_R && !MASK && NT && FAST && !CALIB && HSGPR && !SYM && !CONTRACT && LEAN && !TILED && SF == 0 && SEMI && MINW == 1 && PPL == 4 && (MC == 16 || MC == 32 || MC == 64);
-    if constexpr (PRODUCT_SWEEP)
-    if (resident_grid > 0 && resident_ctl && !contiguous && !swapxy && gx * psplit > resident_grid) {
-        hipLaunchKernelGGL((k_residual_resident<PPL, MC, WRITE_R, MASK, NT, FAST, CALIB, HSGPR, SYM, CONTRACT, LEAN, TILED, SF, SEMI, MINW>),
-                           dim3(resident_grid), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, M, thr2, R, ldr, counts, mask, psplit, gx,
-                           gx * psplit, resident_ctl, p.xmin, p.xmax, p.ymin, p.ymax, slice_major);
+    if constexpr (on_resident_grid<Cfg>)
+    if (how.resident_grid > 0 && how.resident_ctl && !contiguous && !how.swapxy && gx * psplit > how.resident_grid) {
+        hipLaunchKernelGGL(k_residual_resident<Cfg>, dim3(how.resident_grid), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, M, thr2, R,
+                           ldr, counts, mask, psplit, gx, gx * psplit, how.resident_ctl, p.xmin, p.xmax, p.ymin, p.ymax, how.slice_major);
         return hipGetLastError();
     }
     dim3 grid(gx, psplit);
-    if (swapxy) grid = dim3(psplit, gx);
-    hipLaunchKernelGGL((k_residual<PPL, MC, WRITE_R, MASK, NT, FAST, CALIB, HSGPR, SYM, CONTRACT, LEAN, TILED, SF, SEMI, MINW>), grid, dim3(256), 0, s, p.x1, p.y1,
-                       p.x2, p.y2, p.n, H, M, thr2, R, ldr, counts, mask, contiguous ? -psplit : psplit, swapxy,
-                       p.xmin, p.xmax, p.ymin, p.ymax);
+    if (how.swapxy) grid = dim3(psplit, gx);
+    // (the kernel takes contiguous slices as a negative slice count)
+    hipLaunchKernelGGL(k_residual<Cfg>, grid, dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, M, thr2, R, ldr, counts, mask,
+                       contiguous ? -psplit : psplit, how.swapxy, p.xmin, p.xmax, p.ymin, p.ymax);
     return hipGetLastError();
 }
+
+#ifdef MH_TUNING
+namespace tune {    // residual_variants.hpp, included behind the product's launchers: the product's configurations are instantiated first
+static hipError_t launch_residual_variant(const Points& p, const double* H, int M, double thr2, double* R, long long ldr, int* counts,
+                                          int variant, hipStream_t s, const SweepLaunch& how);
+static hipError_t launch_score_variant(const Points& p, const double* H, int M, double thr2, int* counts, int variant, hipStream_t s);
+}
+#endif
 
 // variant: 0 = the reference's forward transfer error, -1 = north_star's symmetric transfer error (extension).
 // Everything else is a tuning / measurement build of the same kernel (other PPL / MC, nt stores, compiler division,
 // coefficients in SGPRs, store-only calibration, forced slices, fused multiply-adds — the last one NOT bit-exact) and
-// exists only in libraries compiled with -DMH_TUNING (multi-h_amd/build.py --tuning) for tools/kernel_sweep.py.
+// exists only in libraries compiled with -DMH_TUNING (multi-h_amd/build.py --tuning) for tools/kernel_sweep.py:
+// residual_variants.hpp.
 hipError_t launch_residual(const Points& p, const double* H, int M, double thr2, double* R,
-                           long long ldr, int* counts, int variant, hipStream_t s, bool counts_zeroed, int resident_grid,
-                           int* resident_ctl, int slices, int slice_major)
+                           long long ldr, int* counts, int variant, hipStream_t s, const SweepLaunch& how)
 {
-    // PPL 4, MC 64 (r05; 16 before: same-box A/B 7.21 / 7.11 / 7.06 ms for 16 / 32 / 64 models per work item — the per-tile work is
-    // shared by more models), the lean sweep wherever a tile and a model allow it, non-temporal 16-B stores (r03: the kernel runs at
-    // the board's power cap, its time is its energy; nt stores — nothing of R is ever re-read — cost 2.7 % less energy
-    // per launch than plain ones, profiles/archive/r03_energy.json)
-    // ... and the nine coefficients of the current model through the scalar unit (s_load from H, uniform address) instead
-    // of LDS broadcasts into VGPRs: the twelve linear-form operations then read one operand from SGPRs; 2.5 % less energy.
-    if (variant == 0) return launch_rs<4, 64, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s, slices, 0, counts_zeroed, resident_grid, resident_ctl, slice_major);
-    if (variant == -1) return launch_rs<4, 16, true, false, true, true, false, true, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);   // nt stores, forward coefficients through the scalar unit
+    auto run = [&](auto form, const SweepLaunch& o = {}) { return launch_rs<decltype(form)>(p, H, M, thr2, R, ldr, counts, nullptr, s, o); };
+    if (variant == 0) return run(ProductSweep{}, how);
+    if (variant == -1) return run(cfg::SweepSym{});     // (the caller's layout is the forward sweep's: not taken)
 #ifdef MH_TUNING
-    if (variant == -2)          // symmetric mode at PPL 2 (PPL 4 measured 3 % faster)
-        return launch_rs<2, 16, true, false, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);
-    if (variant >= 700)         // 700 + psplit: store-only calibration with nt stores (the product's store instruction) and a forced point split
-        return launch_rs<4, 16, true, false, true, true, true>(p, H, M, thr2, R, ldr, counts, nullptr, s, variant - 700);
-    if (variant >= 600)         // 600 + psplit: fused multiply-adds (NOT bit-exact) with a forced point split
-        return launch_rs<4, 16, true, false, false, true, false, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s, variant - 600);
-    if (variant >= 500)         // 500 + psplit: store-only calibration (plain stores) with a forced point split
-        return launch_rs<4, 16, true, false, false, true, true>(p, H, M, thr2, R, ldr, counts, nullptr, s, variant - 500);
-    if (variant >= 400)         // 400 + psplit: the product kernel with a forced point split (tools/shard_proxy.py)
-        return launch_rs<4, 16, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s, variant - 400);
-    if (variant >= 300)         // 300 + s: s interleaved slices with the slice index as the fastest grid dimension
-        return launch_rs<4, 16, true, false, false>(p, H, M, thr2, R, ldr, counts, nullptr, s, variant - 300, 1);
-    if (variant >= 200)         // 200 + s: s contiguous point slices instead of interleaved tiles
-        return launch_rs<4, 16, true, false, false>(p, H, M, thr2, R, ldr, counts, nullptr, s, -(variant - 200));
-    if (variant >= 100)         // 100 + psplit: default kernel with a forced point split
-        return launch_rs<4, 16, true, false, false>(p, H, M, thr2, R, ldr, counts, nullptr, s, variant - 100);
-    switch (variant) {
-    // 50 / 51 / 52: the product sweep with 16 / 32 / 64 models per work item (the product: 64 since r05), resident grid and all
-    case 50: return launch_rs<4, 16, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s, slices, 0, counts_zeroed, resident_grid, resident_ctl, slice_major);
-    case 51: return launch_rs<4, 32, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s, slices, 0, counts_zeroed, resident_grid, resident_ctl, slice_major);
-    case 52: return launch_rs<4, 64, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s, slices, 0, counts_zeroed, resident_grid, resident_ctl, slice_major);
-    case 1: return launch_rs<2, 16, true, false, false>(p, H, M, thr2, R, ldr, counts, nullptr, s);                // PPL 2
-    case 2: return launch_rs<4, 16, true, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);                 // nt stores
-    case 3: return launch_rs<4, 16, true, false, false, false>(p, H, M, thr2, R, ldr, counts, nullptr, s);         // compiler IEEE division
-    case 4: return launch_rs<4, 16, true, false, false, true, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);  // coefficients in SGPRs
-    case 5: return launch_rs<4, 8, true, false, false>(p, H, M, thr2, R, ldr, counts, nullptr, s);                 // MC 8
-    case 6: return launch_rs<4, 32, true, false, false>(p, H, M, thr2, R, ldr, counts, nullptr, s);                // MC 32
-    case 7: return launch_rs<4, 16, true, false, false, true, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);    // store-only calibration
-    case 8: return launch_rs<8, 16, true, false, false>(p, H, M, thr2, R, ldr, counts, nullptr, s);                // PPL 8
-    case 9: return launch_rs<6, 16, true, false, false>(p, H, M, thr2, R, ldr, counts, nullptr, s);                // PPL 6
-    case 10: return launch_rs<4, 16, true, false, false, true, false, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);   // fused multiply-adds: NOT bit-exact
-    case 20: return launch_rs<4, 16, true, false, false, true, false, false, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);         // lean sweep on clean tiles, plain stores
-    case 32: return launch_rs<4, 16, true, false, false>(p, H, M, thr2, R, ldr, counts, nullptr, s);                                                 // the r02 product kernel: checked sweep everywhere
-    case 21: return launch_rs<4, 16, true, false, false, true, false, false, false, false, true, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);   // lean + tile-major R
-    case 22: return launch_rs<4, 16, true, false, true, true, false, false, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);          // lean + nt stores, coefficients from LDS
-    case 23: return launch_rs<4, 16, true, false, false, true, false, false, false, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);  // tile-major R alone
-    case 24: return launch_rs<4, 16, true, false, false, true, true, false, false, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);   // store-only calibration, tile-major R
-    case 25: return launch_rs<6, 16, true, false, false, true, false, false, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);         // lean, PPL 6
-    case 26: return launch_rs<8, 16, true, false, false, true, false, false, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);         // lean, PPL 8
-    case 28: return launch_rs<4, 16, true, false, false, true, false, false, false, false, true, false, 2>(p, H, M, thr2, R, ldr, counts, nullptr, s);  // lean, sc1 stores
-    case 29: return launch_rs<4, 16, true, false, false, true, false, false, false, false, true, false, 3>(p, H, M, thr2, R, ldr, counts, nullptr, s);  // lean, sc0 sc1 stores
-    case 30: return launch_rs<4, 16, true, false, false, true, false, false, false, false, true, false, 4>(p, H, M, thr2, R, ldr, counts, nullptr, s);  // lean, sc1 nt stores
-    case 31: return launch_rs<4, 16, true, false, false, true, false, false, false, false, true, false, 5>(p, H, M, thr2, R, ldr, counts, nullptr, s);  // lean, sc0 sc1 nt stores
-    case 33: return launch_rs<4, 16, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);           // lean + nt, coefficients through the scalar unit (= the product since r03)
-    case 34: return launch_rs<4, 16, true, false, true, true, false, true, false, false, true, false, 0, false>(p, H, M, thr2, R, ldr, counts, nullptr, s);  // as the product, but models that are not `far` take the checked sweep
-    case 35: return launch_rs<4, 16, true, false, true, true, false, true, false, false, true, false, 0, true, 8>(p, H, M, thr2, R, ldr, counts, nullptr, s);   // product, registers capped for 8 waves per SIMD
-    case 36: return launch_rs<4, 16, true, false, true, true, false, true, false, false, true, false, 0, true, 7>(p, H, M, thr2, R, ldr, counts, nullptr, s);   // ... 7 waves per SIMD
-    case 37: return launch_rs<6, 16, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);                     // product at PPL 6
-    case 38: return launch_rs<2, 16, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);                     // product at PPL 2
-    case 39: return launch_rs<4, 32, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);                     // product at MC 32
-    case 40: return launch_rs<4, 8, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);                      // product at MC 8
-    case 41: return launch_rs<4, 32, true, false, true, true, false, true, false, false, true, false, 0, true, 7>(p, H, M, thr2, R, ldr, counts, nullptr, s);   // MC 32, 7 waves per SIMD
-    case 42: return launch_rs<4, 64, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);                      // MC 64
-    case 43: return launch_rs<6, 32, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);                      // MC 32, PPL 6
-    case 44: return launch_rs<4, 64, true, false, true, true, false, true, false, false, true, false, 0, true, 7>(p, H, M, thr2, R, ldr, counts, nullptr, s);   // MC 64, 7 waves per SIMD
-    case 45: return launch_rs<4, 32, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s, 8);                   // MC 32, 8 point slices
-    case 46: return launch_rs<4, 32, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s, 2);                   // MC 32, 2 point slices
-    case 47: return launch_rs<4, 64, true, false, true, true, false, true, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s, 8);                   // MC 64, 8 point slices
-    case 27: return launch_rs<2, 16, true, false, false, true, false, false, false, false, true>(p, H, M, thr2, R, ldr, counts, nullptr, s);         // lean, PPL 2
-    default: break;
-    }
-#endif
+    return tune::launch_residual_variant(p, H, M, thr2, R, ldr, counts, variant, s, how);
+#else
     return hipErrorInvalidValue;
+#endif
 }
 
 int residual_workgroups_per_cu()
 {
     int n = 0;
-    const hipError_t he = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &n, (const void*)k_residual_resident<4, 64, true, false, true, true, false, true, false, false, true>, 256, 0);
+    const hipError_t he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_residual_resident<ProductSweep>, 256, 0);
     return he == hipSuccess && n > 0 ? n : 0;
 }
 
 hipError_t launch_score(const Points& p, const double* H, int M, double thr2,
                         const unsigned char* mask, int* counts, int variant, hipStream_t s)
 {
-    if (variant == -1) {
-        if (mask) return launch_rs<4, 16, false, true, false, true, false, false, true>(p, H, M, thr2, nullptr, 0, counts, mask, s);
-        return launch_rs<4, 16, false, false, false, true, false, false, true>(p, H, M, thr2, nullptr, 0, counts, nullptr, s);
-    }
-    if (mask) return launch_rs<4, 16, false, true, false, true, false, true, false, false, true>(p, H, M, thr2, nullptr, 0, counts, mask, s);
-    if (variant == 0) return launch_rs<4, 16, false, false, false, true, false, true, false, false, true>(p, H, M, thr2, nullptr, 0, counts, nullptr, s);
+    auto run = [&](auto form) { return launch_rs<decltype(form)>(p, H, M, thr2, nullptr, 0, counts, mask, s); };
+    if (variant == -1) return mask ? run(cfg::ScoreSymMasked{}) : run(cfg::ScoreSym{});
+    if (mask) return run(cfg::ScoreMasked{});
+    if (variant == 0) return run(cfg::Score{});
 #ifdef MH_TUNING
-    if (variant == 1) return launch_rs<2, 16, false, false, false>(p, H, M, thr2, nullptr, 0, counts, nullptr, s);           // PPL 2
-    if (variant == 32) return launch_rs<4, 16, false, false, false>(p, H, M, thr2, nullptr, 0, counts, nullptr, s);          // the r02 score kernel
-    if (variant == 20) return launch_rs<4, 16, false, false, false, true, false, false, false, false, true>(p, H, M, thr2, nullptr, 0, counts, nullptr, s);   // lean, coefficients from LDS
-    if (variant == 3) return launch_rs<4, 16, false, false, false, false>(p, H, M, thr2, nullptr, 0, counts, nullptr, s);    // compiler IEEE division
-#endif
+    return tune::launch_score_variant(p, H, M, thr2, counts, variant, s);
+#else
     return hipErrorInvalidValue;
+#endif
 }
+
+#ifdef MH_TUNING
+#include "residual_variants.hpp"
+#endif
 
 // ComputeInliersOfHomography, M/MultiH.cpp:743-768.
 __global__ void __launch_bounds__(256)

@@ -94,24 +94,22 @@ def test_product_tree_never_touches_the_oracle():
 
 
 def test_product_library_kernels_are_the_product_instantiations_only(mh, engine_lib):
-    """the kernel templates carry measurement switches (residual_wg: CALIB = store-only calibration,
-    CONTRACT = fused multiply-adds — not bit-exact —, TILED = tile-major R, SF = asm store flavours; k_cost32: BATCH;
-    k_score32: tilings) — none of them may be instantiated in the product library.  The kernel names the host side
-    registers are strings of the .so: demangle them and look at the template arguments."""
+    """the kernel templates carry measurement switches (the residual sweep's configuration: CALIB =
+    store-only calibration, CONTRACT = fused multiply-adds — not bit-exact —, TILED = tile-major R, SF = asm store flavours,
+    MINW = capped registers, FAST = false the compiler's division; k_cost32: BATCH; k_score32: tilings) — none of them may be
+    instantiated in the product library.  The kernel names the host side registers are strings of the .so: demangle them.
+    A residual kernel is named after its configuration type: the product's are the six named forms of mh::cfg (each without a
+    measurement switch: the static_assert beside them in residual.hip), the materialising sweep also on the resident grid; a
+    measurement variant is a wrapper of mh::tune around one of them."""
     raw = subprocess.run(["strings", mh.LIB_PATH], capture_output=True, text=True).stdout
     names = sorted({l for l in raw.splitlines() if re.match(r"^_ZN2mh\d+k_", l)})
     assert len(names) > 40
     dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
     kernels = sorted({re.sub(r"\(.*", "", d).replace("void ", "") for d in dem})
-    res = [k for k in kernels if k.startswith("mh::k_residual")]
-    assert 5 <= len(res) <= 8, res
-    for k in res:
-        a = [x.strip() for x in k[k.index("<") + 1:k.rindex(">")].split(",")]
-        # <PPL, MC, WRITE_R, MASK, NT, FAST, CALIB, HSGPR, SYM, CONTRACT, LEAN, TILED, SF, SEMI, MINW>
-        # (MC: 64 models per work item in the materialising sweep since r05, 16 in the store-free and symmetric forms)
-        assert len(a) == 15 and a[0] == "4" and a[1] in ("16", "64"), k
-        assert a[6] == "false" and a[9] == "false" and a[11] == "false" and a[12] == "0" and a[14] == "1", f"measurement variant in the product library: {k}"
-        assert a[5] == "true", f"compiler division in the product library: {k}"
+    res = {k for k in kernels if k.startswith("mh::k_residual")}
+    forms = ("Sweep", "SweepSym", "Score", "ScoreMasked", "ScoreSym", "ScoreSymMasked")
+    assert res == {f"mh::k_residual<mh::cfg::{f}>" for f in forms} | {"mh::k_residual_resident<mh::cfg::Sweep>"}, sorted(res)
+    assert not any("tune" in k for k in res), f"measurement variant in the product library: {sorted(res)}"
     cost = [k for k in kernels if k.startswith("mh::k_cost32")]
     assert sorted(cost) == ["mh::k_cost32<32, 8, false>", "mh::k_cost32_resident<32, 8, false>"], cost
     score = [k for k in kernels if k.startswith("mh::k_score32")]

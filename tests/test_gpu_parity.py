@@ -731,6 +731,63 @@ def test_shared_reciprocal_precondition_boundaries(engine, oracle, symmetric):
     assert 0.05 < np.isfinite(R_ref).mean() < 0.9999 and ref_cnt.sum() > 0     # both regimes present
 
 
+_FORMS = ("sweep", "sweep_sym", "score", "score_masked", "score_sym", "score_sym_masked")
+_form_inputs = {}
+
+
+def _form_edge_inputs(synth, n):
+    """65 models on n points, off the lean path in every way it can be left: a source coordinate outside the fast
+    division's precondition (its wave tile takes the checked sweep), a model whose horizon runs through the data (not
+    `far`) and a model that fails model_pre (the fallback division).  Made once per n, never modified."""
+    if n not in _form_inputs:
+        sc = synth.make_scene(n, 3, seed=n, with_neighbours=False)
+        rng = np.random.default_rng(n)
+        src, dst = sc.src.copy(), sc.dst.copy()
+        src[17, 0] = 1e100
+        H = _models(sc, rng, extra=62)
+        H[3] = [1, 0, 0, 0, 1, 0, 1e-3, -1e-3, 0]
+        H[5] = [1e150, 0, 0, 0, 1e150, 0, 0, 0, 1e150]
+        mask = (rng.random(n) < 0.6).astype(np.uint8)
+        mask[-1] = 1                                    # the odd tail point counts
+        assert H.shape[0] == 65
+        for a in (src, dst, H, mask):
+            a.setflags(write=False)
+        _form_inputs[n] = (src, dst, H, mask)
+    return _form_inputs[n]
+
+
+@pytest.mark.parametrize("n", [1023, 2049])
+@pytest.mark.parametrize("form", _FORMS)
+def test_every_product_form_of_the_sweep_at_partial_shapes(engine, synth, oracle, form, n):
+    """The six product configurations of the residual sweep (residual.hip, namespace cfg: Sweep, SweepSym, Score,
+    ScoreMasked, ScoreSym, ScoreSymMasked), each against the oracle, bit for bit, where every loop has a partial last
+    trip: n = 1023 is an odd tail inside the last 16-byte chunk of ONE partial 1 024-point tile (one point slice: counts are
+    written directly), n = 2049 three tiles, the last holding one point (three slices: counts through the atomic path);
+    65 models leave a one-model block behind 64 (Sweep) and behind 4 x 16 (the others)."""
+    src, dst, H, mask = _form_edge_inputs(synth, n)
+    sym = "sym" in form
+    m = mask if form.endswith("masked") else None
+    engine.set_correspondences(src, dst)
+    engine.set_models(H)
+    engine.set_residual_mode(sym)
+    engine.set_tuning(15, 0)                # the forward score through the FP64 sweep, not the FP32 pre-test
+    try:
+        with np.errstate(all="ignore"):
+            if form.startswith("sweep"):
+                R, cnt = engine.residual_matrix(THR2)
+                R_ref = (oracle.residual_matrix_sym if sym else oracle.residual_matrix)(src, dst, H)
+                assert R.shape == R_ref.shape == (65, n)
+                assert np.array_equal(R.view(np.uint64), R_ref.view(np.uint64))
+            else:
+                cnt = engine.score(THR2, mask=m)
+            cnt_ref = (oracle.score_sym if sym else oracle.score)(src, dst, H, THR2, mask=m)
+    finally:
+        engine.set_tuning(15, 1)
+        engine.set_residual_mode(False)
+    assert np.array_equal(cnt, cnt_ref)
+    assert cnt_ref.max() > n // 8 and cnt_ref[5] < n
+
+
 def test_product_library_carries_no_measurement_variants(mh, engine, synth, oracle):
     """The residual / score kernel variants used for the A/B evidence of HISTORY.md section 7 — one of them, fused
     multiply-adds, is not bit-exact — live only in the measurement library (build.py --tuning).  The product library

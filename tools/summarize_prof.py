@@ -10,9 +10,12 @@ print("== source: HEAD", os.environ.get("HEAD_SHA", "unknown"), " bench_py_sha16
 KEEP = [k for k in os.environ.get("KERNELS", "k_residual,k_dlt4").split(",") if k]
 ROWS = int(os.environ.get("STAT_ROWS", "14"))
 def materialising(name):
-    """the residual kernel with WRITE_R = true (third template argument), demangled or mangled — the hardware-dispatched
-    form (k_residual, r01-r03) or the resident grid (k_residual_resident, r04)"""
-    return any(k in name for k in ("k_residual<4, 16, true", "k_residualILi4ELi16ELb1", "k_residual_resident<4, 16, true",
+    """the product's materialising residual sweep, demangled or mangled: the kernel over the configuration mh::cfg::Sweep, on
+    the resident grid or hardware-dispatched; in archived traces (r01-r05) the kernel with WRITE_R = true as its third
+    template argument, at 16 or 64 models per work item"""
+    return any(k in name for k in ("k_residual<mh::cfg::Sweep>", "k_residual_resident<mh::cfg::Sweep>",
+                                   "k_residualINS_3cfg5SweepEEE", "k_residual_residentINS_3cfg5SweepEEE",
+                                   "k_residual<4, 16, true", "k_residualILi4ELi16ELb1", "k_residual_resident<4, 16, true",
                                    "k_residual_residentILi4ELi16ELb1", "k_residual<4, 64, true", "k_residualILi4ELi64ELb1",
                                    "k_residual_resident<4, 64, true", "k_residual_residentILi4ELi64ELb1"))
 def find(sub, pat):
