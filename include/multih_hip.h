@@ -127,6 +127,24 @@ MH_API int mh_estimate_fundamental(mh_engine* e, unsigned long long seed, int hy
                             double F[9], double e2[2], unsigned char* inlier_mask /* n, nullable */,
                             int* inliers);
 
+/* ---- the caller's estimator: minimal 7-point samples with a confidence stop and no refit — what
+ * cv::findFundamentalMat(CV_FM_RANSAC, thr, confidence) does at M/main.cpp:399-409 and M/MultiH.cpp:775 (its draws and its
+ * un-normalised arithmetic are not reproduced).  Additive: mh_estimate_fundamental above stays the default route. */
+/* m samples from counter-RNG 7-tuples (n >= 7), up to three F each: fills the F-hypothesis set with 3 m slots, slot 3 s + j
+ * = solution j of sample `first + s` in ascending order of its root; the finite ones first, the others nine NaNs (they
+ * score 0).  mh_score_sampson and mh_get_fund_hypotheses(F, NULL) work on the set unchanged; mh_get_fund_hypotheses with a
+ * non-NULL idx fails with MH_ERR_INVALID until the next mh_propose_fund8. */
+MH_API int mh_propose_fund7(mh_engine* e, unsigned long long seed, long long first, int m);
+MH_API int mh_get_fund7_samples(mh_engine* e, int* idx /* m x 7, nullable */, int* nvalid /* m, nullable: finite slots per sample */);
+/* propose(max_samples) -> score under the engine's metric -> the sequential stop rule on the device: after sample s the
+ * best count so far gives N = ceil(log(1 - confidence) / log(1 - (best / n)^7)) clamped to [1, max_samples], and the first s
+ * with s + 1 >= N ends the run (samples_used = s + 1).  F is the best slot of the samples used, bit for bit (ties: the
+ * lowest slot index), mask / inliers are those of F, e2 as mh_epipoles gives it.  MH_ERR_INVALID when no slot is finite,
+ * the best count is 0, max_samples < 1 or confidence is outside (0, 1). */
+MH_API int mh_estimate_fundamental_minimal(mh_engine* e, unsigned long long seed, int max_samples, double confidence, double thr,
+                                    double F[9], double e2[2], unsigned char* inlier_mask /* n, nullable */,
+                                    int* inliers, int* samples_used /* nullable */);
+
 /* Epipoles of F with third coordinate 1: e1 = eigenvector of F^T F, e2 = eigenvector of F F^T with the
  * smallest eigenvalue (M/MultiH.cpp:786-799).  Host arithmetic only; e may be NULL. */
 MH_API int mh_epipoles(mh_engine* e, const double F[9], double e1[2], double e2[2]);

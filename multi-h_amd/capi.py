@@ -25,7 +25,7 @@ SYMBOLS = [
     "mh_abi_version", "mh_last_error", "mh_device_count", "mh_create", "mh_destroy", "mh_set_params",
     "mh_set_stream", "mh_synchronize", "mh_set_correspondences", "mh_set_epipolar",
     "mh_set_neighbors_csr", "mh_build_neighbors_knn", "mh_build_neighbors_knn_radius", "mh_build_neighbors_radius", "mh_get_sym_graph", "mh_set_fundamental_metric", "mh_propose_fund8",
-    "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons", "mh_refine_points",
+    "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_propose_fund7", "mh_get_fund7_samples", "mh_estimate_fundamental_minimal", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons", "mh_refine_points",
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
     "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_samples", "mh_set_residual_mode", "mh_score",
     "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_data_cost", "mh_expand",
@@ -170,6 +170,24 @@ class Engine:
         self._check(self.lib.mh_get_fund_hypotheses(self._h, _p(F, C.c_double), _p(idx, C.c_int)))
         return F, idx
 
+    def propose_fund7(self, seed: int, first: int, m: int):
+        """m minimal 7-point samples, up to three F each: the hypothesis set then has 3 m slots (NaN where there is no solution)."""
+        self._check(self.lib.mh_propose_fund7(self._h, C.c_ulonglong(seed), C.c_longlong(first), int(m)))
+        self._fm = 3 * int(m)
+        self._f7m = int(m)
+
+    def get_fund7_hypotheses(self):
+        """The 3 m slots of the last propose_fund7 as an (m, 3, 9) array."""
+        F = np.empty((self._fm, 9), dtype=np.float64)
+        self._check(self.lib.mh_get_fund_hypotheses(self._h, _p(F, C.c_double), None))
+        return F.reshape(-1, 3, 9)
+
+    def get_fund7_samples(self):
+        idx = np.empty((self._f7m, 7), dtype=np.int32)
+        nvalid = np.empty(self._f7m, dtype=np.int32)
+        self._check(self.lib.mh_get_fund7_samples(self._h, _p(idx, C.c_int), _p(nvalid, C.c_int)))
+        return idx, nvalid
+
     def score_sampson(self, thr2: float):
         cnt = np.empty(self._fm, dtype=np.int32)
         self._check(self.lib.mh_score_sampson(self._h, C.c_double(thr2), _p(cnt, C.c_int)))
@@ -197,6 +215,18 @@ class Engine:
                                                      _p(F, C.c_double), _p(e2, C.c_double), _p(mask, C.c_ubyte),
                                                      C.byref(inl)))
         return F, e2, mask, inl.value
+
+    def estimate_fundamental_minimal(self, seed: int, max_samples: int, confidence: float, thr: float):
+        """7-point samples, confidence stop, no refit (cv::findFundamentalMat's scheme): F, e2, mask, inliers, samples_used."""
+        F = np.empty(9, dtype=np.float64)
+        e2 = np.empty(2, dtype=np.float64)
+        mask = np.empty(self.n, dtype=np.uint8)
+        inl, used = C.c_int(0), C.c_int(0)
+        self._fm, self._f7m = 3 * int(max_samples), int(max_samples)      # (the proposal stands even where the estimate fails)
+        self._check(self.lib.mh_estimate_fundamental_minimal(self._h, C.c_ulonglong(seed), int(max_samples), C.c_double(confidence),
+                                                             C.c_double(thr), _p(F, C.c_double), _p(e2, C.c_double),
+                                                             _p(mask, C.c_ubyte), C.byref(inl), C.byref(used)))
+        return F, e2, mask, inl.value, used.value
 
     def epipoles(self, F):
         F = _f64(F).reshape(9)

@@ -393,7 +393,7 @@ void mh_destroy(mh_engine* e)
     e->H.release(); e->samples.release(); e->counts.release(); e->R.release(); e->C.release(); e->mask.release();
     e->moments.release(); e->min_eig.release();
     e->cp_pts.release(); e->cp_H.release(); e->cp_out.release(); e->cp_begin.release(); e->cp_tri.release(); e->cp_ok.release();
-    e->fund.release(); e->fund_one.release(); e->fund_samples.release(); e->fund_counts.release();
+    e->fund.release(); e->fund_one.release(); e->fund_samples.release(); e->fund_counts.release(); e->fund_nvalid.release(); e->fund_stop.release();
     e->fund_inl.release(); e->fund_mask.release(); e->ref_keep.release(); e->ref_in.release(); e->ref_out.release();
     e->loc_H.release(); e->loc_feat.release(); e->ms_data.release(); e->ms_mean.release();
     e->ms_votes.release(); e->ms_out.release(); e->ms_list.release(); e->ms_pcnt.release(); e->ms_heads.release(); e->ms_tickets.release(); e->ms_partial.release();
@@ -512,7 +512,7 @@ int mh_set_correspondences(mh_engine* e, const double* src_xy, const double* dst
     if (n != e->n) {
         // everything sized by the previous point set is stale: the residual matrix and its pitch, the sampled batch,
         // the fundamental-matrix hypotheses
-        e->m = 0; e->ldr = 0; e->have_samples = false; e->fm = 0;
+        e->m = 0; e->ldr = 0; e->have_samples = false; e->fm = 0; e->f7_m = 0;
         e->counts_fresh = false; ++e->models_seq;
     }
     {

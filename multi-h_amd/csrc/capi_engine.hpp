@@ -155,6 +155,9 @@ struct mh_engine {
     int fund_metric = 0;                       // mh_set_fundamental_metric: MH_FUND_SAMPSON / MH_FUND_EPIPOLAR_MAX (changes results: not a tuning key)
     DevBuf<double> fund, fund_one;
     DevBuf<int> fund_samples, fund_counts, fund_inl;
+    int fund_tuple = 8;                        // indices per sample in fund_samples: 8 after mh_propose_fund8, 7 after mh_propose_fund7
+    int f7_m = 0;                              // samples of the last mh_propose_fund7 (fm = 3 * f7_m slots)
+    DevBuf<int> fund_nvalid, fund_stop;        // k_fund7: finite slots per sample; k_ransac_stop: its four words
     DevBuf<unsigned char> fund_mask, ref_keep, ref_in, ref_reason;
     int ref_reason_n = 0;                      // rows of the last mh_refine_correspondences (mh_get_refine_reasons)
     DevBuf<double> ref_out;

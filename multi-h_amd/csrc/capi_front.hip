@@ -48,6 +48,40 @@ int mh_propose_fund8(mh_engine* e, unsigned long long seed, long long first, int
     HIPCHK(e->fund_counts.reserve(m));
     HIPCHK(launch_fund8(e->pts(), seed, first, m, e->fund_samples.p, e->fund.p, e->stream));
     e->fm = m;
+    e->fund_tuple = 8;
+    e->f7_m = 0;
+    return MH_OK;
+    });
+}
+
+int mh_propose_fund7(mh_engine* e, unsigned long long seed, long long first, int m)
+{
+    return guarded([&]() -> int {
+    int rc = require_points(e);
+    if (rc) return rc;
+    if (m <= 0 || m > 0x7fffffff / 27) return fail(MH_ERR_INVALID, "m must be positive (and 27 m below 2^31)");
+    if (e->n < 7) return fail(MH_ERR_INVALID, "need at least 7 correspondences");
+    HIPCHK(e->fund.reserve((size_t)m * 27));
+    HIPCHK(e->fund_samples.reserve((size_t)m * 7));
+    HIPCHK(e->fund_nvalid.reserve(m));
+    HIPCHK(e->fund_counts.reserve((size_t)m * 3));
+    HIPCHK(launch_fund7(e->pts(), seed, first, m, e->fund_samples.p, e->fund.p, e->fund_nvalid.p, e->stream));
+    e->fm = 3 * m;
+    e->fund_tuple = 7;
+    e->f7_m = m;
+    return MH_OK;
+    });
+}
+
+int mh_get_fund7_samples(mh_engine* e, int* idx, int* nvalid)
+{
+    return guarded([&]() -> int {
+    int rc = require_points(e);
+    if (rc) return rc;
+    if (e->f7_m <= 0 || e->fund_tuple != 7) return fail(MH_ERR_NOT_SET, "no 7-point hypotheses; call mh_propose_fund7");
+    if (idx) HIPCHK(hipMemcpyAsync(idx, e->fund_samples.p, sizeof(int) * 7 * e->f7_m, hipMemcpyDeviceToHost, e->stream));
+    if (nvalid) HIPCHK(hipMemcpyAsync(nvalid, e->fund_nvalid.p, sizeof(int) * e->f7_m, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
     return MH_OK;
     });
 }
@@ -58,6 +92,8 @@ int mh_get_fund_hypotheses(mh_engine* e, double* F, int* idx)
     int rc = require_points(e);
     if (rc) return rc;
     if (e->fm <= 0) return fail(MH_ERR_NOT_SET, "no fundamental-matrix hypotheses; call mh_propose_fund8");
+    if (idx && e->fund_tuple != 8)
+        return fail(MH_ERR_INVALID, "the hypotheses come from 7-point samples: pass idx = NULL and read them with mh_get_fund7_samples");
     if (F) HIPCHK(hipMemcpyAsync(F, e->fund.p, sizeof(double) * 9 * e->fm, hipMemcpyDeviceToHost, e->stream));
     if (idx) HIPCHK(hipMemcpyAsync(idx, e->fund_samples.p, sizeof(int) * 8 * e->fm, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -163,6 +199,41 @@ int mh_estimate_fundamental(mh_engine* e, unsigned long long seed, int hypothese
     if (rc) return rc;
     double e1[2];
     return mh_epipoles(e, F, e1, e2);                  // M/MultiH.cpp:786-799
+    });
+}
+
+int mh_estimate_fundamental_minimal(mh_engine* e, unsigned long long seed, int max_samples, double confidence, double thr,
+                                    double F[9], double e2[2], unsigned char* inlier_mask, int* inliers, int* samples_used)
+{
+    return guarded([&]() -> int {
+    if (!F || !e2) return fail(MH_ERR_INVALID, "null output");
+    if (max_samples < 1) return fail(MH_ERR_INVALID, "max_samples < 1");
+    if (!(confidence > 0.0 && confidence < 1.0)) return fail(MH_ERR_INVALID, "confidence must lie inside (0, 1)");
+    int rc = mh_propose_fund7(e, seed, 0, max_samples);
+    if (rc) return rc;
+    rc = mh_score_sampson(e, thr * thr, nullptr);                     // the counts stay on the device
+    if (rc) return rc;
+    HIPCHK(e->fund_stop.reserve(4));
+    HIPCHK(e->fund_one.reserve(18));
+    HIPCHK(e->fund_inl.reserve(1));
+    HIPCHK(e->fund_mask.reserve((size_t)e->n + 2));
+    // the stop rule picks the winner and copies its F to fund_one[0..8]; k_fund_mask then gives the mask and the count of
+    // that F — the test of k_fund_refit's first pass, which is where mh_estimate_fundamental takes its own from, with no refit behind it
+    HIPCHK(launch_ransac_stop(e->fund_counts.p, e->fund_nvalid.p, max_samples, e->n, confidence, e->fund.p, e->fund_one.p,
+                              e->fund_stop.p, e->stream));
+    HIPCHK(launch_fund_mask(e->pts(), e->fund_one.p, thr * thr, e->fund_mask.p, e->fund_inl.p, e->stream, e->fund_metric));
+    int word[4] = { 0, 0, 0, 0 }, inl = 0;
+    HIPCHK(hipMemcpyAsync(word, e->fund_stop.p, sizeof(word), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(F, e->fund_one.p, sizeof(double) * 9, hipMemcpyDeviceToHost, e->stream));
+    if (inlier_mask) HIPCHK(hipMemcpyAsync(inlier_mask, e->fund_mask.p, e->n, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(&inl, e->fund_inl.p, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (samples_used) *samples_used = word[2];
+    if (inliers) *inliers = inl;
+    if (word[3] <= 0) return fail(MH_ERR_INVALID, "no 7-point sample gave a finite fundamental matrix");
+    if (word[1] <= 0) return fail(MH_ERR_INVALID, "no fundamental-matrix hypothesis has an inlier");
+    double e1[2];
+    return mh_epipoles(e, F, e1, e2);
     });
 }
 

@@ -594,6 +594,237 @@ k_fund8(const double* __restrict__ x1, const double* __restrict__ y1,
 #undef WE
 }
 
+// ---------------------------------------------------------------------------
+// k_fund7 — batched normalised 7-point (minimal-sample) fundamental-matrix hypotheses: what cv::findFundamentalMat(RANSAC)
+// draws (M/main.cpp:399-409, M/MultiH.cpp:775).  k_fund8's mapping and machinery: counter-RNG 7-tuples
+// (sample_tuple<7, 256>), Hartley normalisation over the seven points (sums in index order, divided by 7.0), the design
+// matrix with rows 0-6 = [u x, u y, u, v x, v y, v, x, y, 1] and row 7 = 0, so A stays 8 x 9 and null9_sweeps runs
+// unchanged.  Up to three models per sample:
+//   null space   G2 = the I-part column under the A-part column of smallest norm (null9_vector's scan: first minimum
+//                wins), G1 = the same scan with that column left out.
+//   cubic        p(t) = det(G2 + t D), D = G1 - G2, p(t) = c0 + c1 t + c2 t^2 + c3 t^3 with
+//                  c0 = det(G2)                                     c3 = det(D)
+//                  c1 = (det[D0;G2_1;G2_2] + det[G2_0;D1;G2_2]) + det[G2_0;G2_1;D2]       (row i of G2 replaced by row i of D)
+//                  c2 = (det[G2_0;D1;D2] + det[D0;G2_1;D2]) + det[D0;D1;G2_2]             (row i of D replaced by row i of G2)
+//                every 3 x 3 determinant by cofactors along its first row,
+//                  det[r0;r1;r2] = (r0[0] (r1[1] r2[2] - r1[2] r2[1]) - r0[1] (r1[0] r2[2] - r1[2] r2[0])) + r0[2] (r1[0] r2[1] - r1[1] r2[0])
+//   roots        closed form on the monic cubic t^3 + a t^2 + b t + c (a = c2/c3, b = c1/c3, c = c0/c3; a, b, c or disc not finite: no root):
+//                  Q = (a a - 3 b) / 9,  R = ((2 a a a - 9 a b) + 27 c) / 54,  disc = R R - Q Q Q
+//                the RULE FOR "REAL": disc < 0: three real roots, -2 sqrt(Q) cos((theta + 2 pi k) / 3) - a / 3, theta =
+//                acos(R / sqrt(Q Q Q)), k = 0, +1, -1; otherwise one, (A + B) - a / 3 with A = -sign(R) cbrt(|R| + sqrt(disc)),
+//                B = Q / A (0 when A = 0); disc == 0 with Q > 0 adds the double root -(A + B) / 2 - a / 3 ONCE.
+//                Each root then takes up to four Newton steps on c0..c3 (Horner), a step being kept only while it is
+//                finite and does not increase |p|; the roots are sorted ascending in t, a NaN counting as the largest.
+//   per root     lane slot j (0..2) of the hypothesis finishes root j: Fn = G2 + t D (no rank-2 projection: the root is
+//                the constraint), F = T2^T Fn T1 by k_fund8's steps, unit Frobenius norm, F[8] >= 0.
+//   output       F_out[(m 3 + j) 9 ..]: the finite F of the sample in ascending t, then quiet NaNs (a root whose F is not
+//                finite gives its place to the next one); nvalid[m] = the number of finite ones; idx_out[7 m ..].
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ double det3_rows(const double* r0, const double* r1, const double* r2)
+{
+    return (r0[0] * (r1[1] * r2[2] - r1[2] * r2[1]) - r0[1] * (r1[0] * r2[2] - r1[2] * r2[0])) +
+           r0[2] * (r1[0] * r2[1] - r1[1] * r2[0]);
+}
+
+__device__ __forceinline__ double cubic_newton(double c0, double c1, double c2, double c3, double t)
+{
+    double p = ((c3 * t + c2) * t + c1) * t + c0;
+    for (int it = 0; it < 4; ++it) {
+        const double dp = (3.0 * c3 * t + 2.0 * c2) * t + c1;
+        const double tn = t - p / dp;
+        const double pn = ((c3 * tn + c2) * tn + c1) * tn + c0;
+        if (!(fabs(pn) <= fabs(p)) || !(fabs(tn) < 1e300)) break;       // (false for NaN too)
+        t = tn; p = pn;
+    }
+    return t;
+}
+
+// real roots of c0 + c1 t + c2 t^2 + c3 t^3 by the rule in the header, ascending; n = their number (0..3)
+struct CubicRoots { double t0, t1, t2; int n; };
+
+__device__ __forceinline__ CubicRoots cubic_real_roots(double c0, double c1, double c2, double c3)
+{
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    const double a = c2 / c3, b = c1 / c3, c = c0 / c3;
+    const double Q = (a * a - 3.0 * b) / 9.0;
+    const double R = ((2.0 * a * a * a - 9.0 * a * b) + 27.0 * c) / 54.0;
+    const double Q3 = Q * Q * Q;
+    const double disc = R * R - Q3;
+    const double a3 = a / 3.0;
+    const bool usable = (fabs(a) < 1e300) && (fabs(b) < 1e300) && (fabs(c) < 1e300) && (fabs(disc) < 1e300);   // (false for NaN)
+    const bool three = disc < 0.0;
+    // three real roots
+    const double theta = acos(R / sqrt(Q3));
+    const double sq = -2.0 * sqrt(Q);
+    const double two_pi = 6.283185307179586476925286766559;
+    const double u0 = sq * cos(theta / 3.0) - a3;
+    const double u1 = sq * cos((theta + two_pi) / 3.0) - a3;
+    const double u2 = sq * cos((theta - two_pi) / 3.0) - a3;
+    // one real root (and the double root of disc == 0)
+    double A = cbrt(fabs(R) + sqrt(disc));
+    if (R >= 0.0) A = -A;
+    const double B = (A == 0.0) ? 0.0 : Q / A;
+    const double w0 = (A + B) - a3;
+    const double w1 = -0.5 * (A + B) - a3;
+    const int nr = !usable ? 0 : three ? 3 : (disc == 0.0 && Q > 0.0) ? 2 : 1;
+    double r0 = nr == 0 ? qnan : cubic_newton(c0, c1, c2, c3, three ? u0 : w0);
+    double r1 = nr < 2 ? qnan : cubic_newton(c0, c1, c2, c3, three ? u1 : w1);
+    double r2 = nr < 3 ? qnan : cubic_newton(c0, c1, c2, c3, u2);
+    // ascending, a NaN root (its F is not finite and its slot is dropped) counting as the largest
+    { const bool sw = (r1 < r0) || (r0 != r0 && r1 == r1); const double lo = sw ? r1 : r0, hi = sw ? r0 : r1; r0 = lo; r1 = hi; }
+    { const bool sw = (r2 < r1) || (r1 != r1 && r2 == r2); const double lo = sw ? r2 : r1, hi = sw ? r1 : r2; r1 = lo; r2 = hi; }
+    { const bool sw = (r1 < r0) || (r0 != r0 && r1 == r1); const double lo = sw ? r1 : r0, hi = sw ? r0 : r1; r0 = lo; r1 = hi; }
+    return CubicRoots{ r0, r1, r2, nr };
+}
+
+__global__ void __launch_bounds__(256)
+k_fund7(const double* __restrict__ x1, const double* __restrict__ y1,
+        const double* __restrict__ x2, const double* __restrict__ y2, int N,
+        unsigned long long seed, long long first, int M, int* __restrict__ idx_out,
+        double* __restrict__ F_out, int* __restrict__ nvalid_out)
+{
+    __shared__ double sW[4][WROWS * WCOLS][HPW];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int hs = lane & (HPW - 1);
+    const int slot = lane >> 4;
+    const int m = (blockIdx.x * 4 + wave) * HPW + hs;
+    const bool live = m < M;
+    double (*W)[HPW] = sW[wave];
+#define WE(r, c) W[(r) * WCOLS + (c)][hs]
+
+    int id[7] = { 0, 0, 0, 0, 0, 0, 0 };
+    if (live) sample_tuple<7, 256>(seed, (unsigned long long)(first + m), (unsigned int)N, id);
+    double sx[7], sy[7], dx[7], dy[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) { sx[k] = x1[id[k]]; sy[k] = y1[id[k]]; dx[k] = x2[id[k]]; dy[k] = y2[id[k]]; }
+    if (live && slot == 0 && idx_out) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) idx_out[7 * (size_t)m + k] = id[k];
+    }
+    double cx1 = sx[0], cy1 = sy[0], cx2 = dx[0], cy2 = dy[0];
+#pragma unroll
+    for (int k = 1; k < 7; ++k) { cx1 = cx1 + sx[k]; cy1 = cy1 + sy[k]; cx2 = cx2 + dx[k]; cy2 = cy2 + dy[k]; }
+    cx1 = cx1 / 7.0; cy1 = cy1 / 7.0; cx2 = cx2 / 7.0; cy2 = cy2 / 7.0;
+    double d1 = 0.0, d2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        const double ax = sx[k] - cx1, ay = sy[k] - cy1, bx = dx[k] - cx2, by = dy[k] - cy2;
+        d1 = d1 + sqrt(ax * ax + ay * ay);
+        d2 = d2 + sqrt(bx * bx + by * by);
+    }
+    const double s1 = sqrt(2.0) / (d1 / 7.0), s2 = sqrt(2.0) / (d2 / 7.0);
+
+    // lane `slot` writes rows 2*slot and 2*slot+1 (correspondences 2*slot, 2*slot+1; row 7 is the zero row)
+#pragma unroll
+    for (int k = 0; k < 7; ++k)
+        if ((k >> 1) == slot) {
+            const double x = (sx[k] - cx1) * s1, y = (sy[k] - cy1) * s1;
+            const double u = (dx[k] - cx2) * s2, v = (dy[k] - cy2) * s2;
+            WE(k, 0) = u * x; WE(k, 1) = u * y; WE(k, 2) = u;
+            WE(k, 3) = v * x; WE(k, 4) = v * y; WE(k, 5) = v;
+            WE(k, 6) = x; WE(k, 7) = y; WE(k, 8) = 1.0;
+        }
+    if (slot == 3)
+        for (int j = 0; j < 9; ++j) WE(7, j) = 0.0;
+    if (slot < 3)
+        for (int i = 3 * slot; i < 3 * slot + 3; ++i)
+            for (int j = 0; j < 9; ++j) WE(8 + i, j) = (i == j) ? 1.0 : 0.0;
+    __syncthreads();
+
+    null9_sweeps(W, hs, slot, live);
+
+    // ---- the two null vectors and the cubic: all four lanes of a hypothesis, redundantly (the same operations on the same
+    // values: the same bits), so that lane slots 0..2 each hold the roots and finish one of them ----
+    int j2 = 0, j1 = -1;
+    {
+        double best2 = 0.0, best1 = 0.0;
+        for (int j = 0; j < 9; ++j) {
+            double a = 0.0;
+            for (int i = 0; i < 8; ++i) a = a + WE(i, j) * WE(i, j);
+            if (j == 0 || a < best2) { best2 = a; j2 = j; }
+        }
+        for (int j = 0; j < 9; ++j) {
+            if (j == j2) continue;
+            double a = 0.0;
+            for (int i = 0; i < 8; ++i) a = a + WE(i, j) * WE(i, j);
+            if (j1 < 0 || a < best1) { best1 = a; j1 = j; }
+        }
+    }
+    double G2[9], D[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) { G2[j] = WE(8 + j, j2); D[j] = WE(8 + j, j1) - G2[j]; }
+    const double c0 = det3_rows(G2, G2 + 3, G2 + 6);
+    const double c3 = det3_rows(D, D + 3, D + 6);
+    const double c1 = (det3_rows(D, G2 + 3, G2 + 6) + det3_rows(G2, D + 3, G2 + 6)) + det3_rows(G2, G2 + 3, D + 6);
+    const double c2 = (det3_rows(G2, D + 3, D + 6) + det3_rows(D, G2 + 3, D + 6)) + det3_rows(D, D + 3, G2 + 6);
+    const CubicRoots roots = cubic_real_roots(c0, c1, c2, c3);
+    const int nroots = roots.n;
+
+    // ---- lane slot j finishes root j ----
+    const double t = slot == 0 ? roots.t0 : slot == 1 ? roots.t1 : roots.t2;
+    double Fo[9];
+    bool ok = live && slot < nroots;
+    {
+        double B[9];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const double f0 = G2[3 * r] + t * D[3 * r], f1 = G2[3 * r + 1] + t * D[3 * r + 1], f2 = G2[3 * r + 2] + t * D[3 * r + 2];
+            const double a = f0 * s1, b = f1 * s1;
+            B[3 * r] = a; B[3 * r + 1] = b;
+            B[3 * r + 2] = (f2 - a * cx1) - b * cy1;
+        }
+        double Fh[9];
+        const double tx = s2 * cx2, ty = s2 * cy2;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            Fh[j] = s2 * B[j];
+            Fh[3 + j] = s2 * B[3 + j];
+            Fh[6 + j] = (B[6 + j] - tx * B[j]) - ty * B[3 + j];
+        }
+        double fro = 0.0;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) fro = fro + Fh[j] * Fh[j];
+        double sc = 1.0 / sqrt(fro);
+        if (Fh[8] < 0.0) sc = -sc;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            Fo[j] = Fh[j] * sc;
+            ok = ok && (fabs(Fo[j]) < 1e300);                            // (false for NaN and infinity)
+        }
+    }
+    // the finite ones first, in ascending t: slot j's place = the finite slots below it
+    const unsigned long long okb = __ballot(ok);
+    const int ok0 = (int)((okb >> hs) & 1ull), ok1 = (int)((okb >> (HPW + hs)) & 1ull), ok2 = (int)((okb >> (2 * HPW + hs)) & 1ull);
+    const int nv = ok0 + ok1 + ok2;
+    if (live && slot < 3) {
+        const int place = slot == 0 ? 0 : slot == 1 ? ok0 : ok0 + ok1;
+        if (ok) {
+            double* out = F_out + (3 * (size_t)m + place) * 9;
+#pragma unroll
+            for (int j = 0; j < 9; ++j) out[j] = Fo[j];
+        }
+        if (slot >= nv) {
+            const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+            double* out = F_out + (3 * (size_t)m + slot) * 9;
+#pragma unroll
+            for (int j = 0; j < 9; ++j) out[j] = qnan;
+        }
+        if (slot == 0 && nvalid_out) nvalid_out[m] = nv;
+    }
+#undef WE
+}
+
+hipError_t launch_fund7(const Points& p, unsigned long long seed, long long first, int M,
+                        int* idx_out, double* F_out, int* nvalid_out, hipStream_t s)
+{
+    if (M <= 0) return hipSuccess;
+    const int per_block = 4 * HPW;
+    hipLaunchKernelGGL(k_fund7, dim3((M + per_block - 1) / per_block), dim3(256), 0, s, p.x1, p.y1,
+                       p.x2, p.y2, p.n, seed, first, M, idx_out, F_out, nvalid_out);
+    return hipGetLastError();
+}
+
 hipError_t launch_fund8(const Points& p, unsigned long long seed, long long first, int M,
                         int* idx_out, double* F_out, hipStream_t s)
 {

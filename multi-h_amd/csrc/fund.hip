@@ -103,6 +103,147 @@ hipError_t launch_sampson_score(const Points& p, const double* F, int M, double 
 }
 
 // ---------------------------------------------------------------------------
+// k_ransac_stop — the stop rule of cv::findFundamentalMat(CV_FM_RANSAC, thr, confidence) (at most S samples, a confidence
+// stop, no refit), replayed over a batch of S 7-point samples that was proposed and scored whole (k_fund7: 3 slots per
+// sample; k_sampson).  One workgroup; the counts never leave the device.
+//   best(s)  = the largest count over the slots of samples 0..s, ties to the lowest (sample, slot)
+//   N(s)     = ceil(log(1 - c) / log(1 - w^7)), w = best(s) / n, w^7 = (((((w w) w) w) w) w) w, clamped to [1, S];
+//              log(1 - w^7) is taken as log1p(-w^7): below w = 0.0048 the difference 1 - w^7 rounds to 1 in FP64 and
+//              its logarithm to 0, where N is in truth ~ 4.6 / w^7.  S when best(s) = 0, when log1p(-w^7) is not
+//              negative, and whenever the quotient is not a positive number below S (NaN included); 1 when best(s) >= n
+//   samples_used = 1 + min{ s : s + 1 >= N(s) }       (exists: N <= S)
+//   winner   = best(samples_used - 1) with its slot index
+// Chunks of 256 samples: the key (count << 32 | ~slot index) of a sample's best slot, an inclusive prefix maximum over the
+// chunk (plus the carry of the chunks before), a ballot for the first sample that stops.
+// out[0] winning slot index, out[1] its count, out[2] samples_used, out[3] valid slots (nvalid) among the samples used;
+// F_win (nullable): the winning slot's F.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int ransac_samples_needed(int best, int n, double log1mc, int S)
+{
+    if (best <= 0) return S;
+    if (best >= n) return 1;
+    const double w = (double)best / (double)n;
+    const double w7 = (((((w * w) * w) * w) * w) * w) * w;
+    const double den = log1p(-w7);             // log(1 - w^7) without losing a small w^7 to the rounding of 1 - w^7
+    if (!(den < 0.0)) return S;                // w^7 underflowed to 0 (or NaN): no confidence is ever reached
+    const double need = ceil(log1mc / den);
+    if (!(need > 0.0) || !(need < (double)S)) return S;      // (a quotient that is not positive cannot come from c in (0, 1))
+    return need < 1.0 ? 1 : (int)need;
+}
+
+__global__ void __launch_bounds__(256)
+k_ransac_stop(const int* __restrict__ counts, const int* __restrict__ nvalid, int S, int n, double confidence,
+              const double* __restrict__ F, double* __restrict__ F_win, int* __restrict__ out)
+{
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    __shared__ unsigned long long s_key[256];
+    __shared__ int s_first[4];
+    __shared__ unsigned long long s_win;
+    __shared__ int s_used;
+    __shared__ int s_sum[256];
+    const double log1mc = log(1.0 - confidence);
+    unsigned long long carry = 0;
+    for (int base = 0; base < S; base += 256) {
+        const int s = base + t;
+        unsigned long long key = 0;
+        if (s < S) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const int c = counts[3 * (size_t)s + j];
+                const unsigned long long k = ((unsigned long long)(unsigned int)(c > 0 ? c : 0) << 32) |
+                                             (unsigned long long)(0xffffffffu - (unsigned int)(3 * s + j));
+                key = k > key ? k : key;
+            }
+        }
+        s_key[t] = key;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {
+            unsigned long long v = s_key[t];
+            if (t >= off) { const unsigned long long o = s_key[t - off]; v = o > v ? o : v; }
+            __syncthreads();
+            s_key[t] = v;
+            __syncthreads();
+        }
+        const unsigned long long pk = s_key[t] > carry ? s_key[t] : carry;
+        const bool stop = s < S && s + 1 >= ransac_samples_needed((int)(pk >> 32), n, log1mc, S);
+        const unsigned long long b = __ballot(stop);
+        if (lane == 0) s_first[wave] = b ? wave * 64 + (__ffsll((long long)b) - 1) : 256;
+        __syncthreads();
+        int f = s_first[0];
+        for (int w = 1; w < 4; ++w) f = s_first[w] < f ? s_first[w] : f;
+        if (f < 256) {                       // (the same for every thread)
+            if (t == f) { s_win = pk; s_used = s + 1; }
+            break;
+        }
+        carry = s_key[255] > carry ? s_key[255] : carry;
+        __syncthreads();
+    }
+    __syncthreads();
+    const int used = s_used;
+    int v = 0;
+    for (int s = t; s < used; s += 256) v += nvalid[s];
+    s_sum[t] = v;
+    __syncthreads();
+    for (int h = 128; h >= 1; h >>= 1) {
+        if (t < h) s_sum[t] += s_sum[t + h];
+        __syncthreads();
+    }
+    const unsigned long long win = s_win;
+    const unsigned int slot = 0xffffffffu - (unsigned int)(win & 0xffffffffull);
+    if (t == 0) {
+        out[0] = (int)slot;
+        out[1] = (int)(win >> 32);
+        out[2] = used;
+        out[3] = s_sum[0];
+    }
+    if (F_win && t < 9) F_win[t] = F[9 * (size_t)slot + t];
+}
+
+hipError_t launch_ransac_stop(const int* counts, const int* nvalid, int S, int n, double confidence, const double* F,
+                              double* F_win, int* out, hipStream_t s)
+{
+    if (S <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ransac_stop, dim3(1), dim3(256), 0, s, counts, nvalid, S, n, confidence, F, F_win, out);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_fund_mask — inlier flags and inlier count of ONE F over all points (d < thr^2, strict, under METRIC): what pass 1 of
+// k_fund_refit reports, without the refit behind it.  For the estimator that returns its winner unrefitted
+// (mh_estimate_fundamental_minimal).  count must be zero at launch; integer adds, so the order does not matter.
+// ---------------------------------------------------------------------------
+template <int METRIC>
+__global__ void __launch_bounds__(256)
+k_fund_mask(const double* __restrict__ x1, const double* __restrict__ y1,
+            const double* __restrict__ x2, const double* __restrict__ y2, int N,
+            const double* __restrict__ F_in, double thr2, unsigned char* __restrict__ mask_out, int* __restrict__ count)
+{
+    double f[9];
+    for (int i = 0; i < 9; ++i) f[i] = F_in[i];
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    bool in = false;
+    if (n < N) {
+        in = epipolar_d<METRIC>(f, x1[n], y1[n], x2[n], y2[n]) < thr2;
+        mask_out[n] = in ? 1 : 0;
+    }
+    const int c = __builtin_popcountll(__builtin_amdgcn_ballot_w64(in));
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
+}
+
+hipError_t launch_fund_mask(const Points& p, const double* F_in, double thr2, unsigned char* mask_out, int* count,
+                            hipStream_t s, int metric)
+{
+    hipError_t he = hipMemsetAsync(count, 0, sizeof(int), s);
+    if (he != hipSuccess || p.n <= 0) return he;
+    const dim3 grid((p.n + 255) / 256);
+    if (metric == 0)
+        hipLaunchKernelGGL(k_fund_mask<0>, grid, dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, F_in, thr2, mask_out, count);
+    else
+        hipLaunchKernelGGL(k_fund_mask<1>, grid, dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, F_in, thr2, mask_out, count);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // Refit: normalised least-squares 8-point on the inliers of F_in.  One workgroup, three strided
 // passes over the points, every FP64 sum in the engine's deterministic order (thread t of 256 adds
 // its points t, t+256, ... then a binary tree), so the oracle reproduces it bit for bit:

@@ -82,7 +82,19 @@ hipError_t launch_dlt4(const Points& p, unsigned long long seed, long long first
 hipError_t launch_fund8(const Points& p, unsigned long long seed, long long first, int M,
                         int* idx_out /* M x 8 */, double* F_out, hipStream_t s);
 
+// 7-point minimal samples: up to three F per sample, F_out[(m*3 + j)*9 ..] (the finite ones first, then quiet NaNs)
+hipError_t launch_fund7(const Points& p, unsigned long long seed, long long first, int M,
+                        int* idx_out /* M x 7 */, double* F_out /* 3M x 9 */, int* nvalid_out /* M */, hipStream_t s);
+
 // --- fund.hip ---------------------------------------------------------------
+// The stop rule of a sequential RANSAC over 7-point samples, replayed on the counts of S samples scored whole (3 slots each,
+// sample order; one workgroup).  out[4]: winning slot index, its count, samples used, valid slots among the samples used.
+// F_win (nullable): receives the winning slot's nine doubles of F.
+hipError_t launch_ransac_stop(const int* counts /* 3S */, const int* nvalid /* S */, int S, int n, double confidence,
+                              const double* F /* 3S x 9 */, double* F_win, int* out, hipStream_t s);
+// inlier flags (n bytes) and inlier count of one F on the device: pass 1 of launch_fund_refit without the refit
+hipError_t launch_fund_mask(const Points& p, const double* F_in, double thr2, unsigned char* mask_out, int* count,
+                            hipStream_t s, int metric);
 // metric: MH_FUND_SAMPSON (0) or MH_FUND_EPIPOLAR_MAX (1), see fund.hip
 hipError_t launch_sampson_score(const Points& p, const double* F, int M, double thr2, int* counts,
                                 hipStream_t s, int metric);

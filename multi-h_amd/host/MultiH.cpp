@@ -19,9 +19,11 @@
 // The entry points of the point-only route are referenced weakly because the class is also linked against the suite's
 // stand-in engine (tests/fake_engine.cpp, the host-boundary test under AddressSanitizer), which defines the ABI up to
 // mh_set_tuning and not these two.  Against libmultih_hip.so they always resolve; where they do not, the HAF route runs
-// unchanged and the point-only route fails with a message instead of a link error.
+// unchanged and the point-only route fails with a message instead of a link error.  The same holds for the minimal-sample
+// F estimator (SetFundamentalEstimator): without its entry point that mode fails with a message, the default runs unchanged.
 #pragma weak mh_set_estimator
 #pragma weak mh_refine_points
+#pragma weak mh_estimate_fundamental_minimal
 
 namespace {
 
@@ -208,11 +210,21 @@ void ReturnEngine(int device, mh_engine* e)
 
 bool multih::FilterCorrespondencesByEpipolarGeometry(std::vector<cv::Point2d>& srcPoints, std::vector<cv::Point2d>& dstPoints,
                                                      std::vector<cv::Mat>& affines, double threshold, uint64_t seed,
-                                                     int hypotheses, int metric, int device, std::vector<unsigned char>* mask_out)
+                                                     int hypotheses, int metric, int device, std::vector<unsigned char>* mask_out,
+                                                     const MultiH::FundEstimator& estimator)
 {
     const size_t n = srcPoints.size();
     const bool points_only = affines.empty();              // no affinities: filter the points alone
     if (n < 8 || dstPoints.size() != n || (!points_only && affines.size() != n)) return false;
+    if (estimator.mode != MultiH::FUND_ESTIMATOR_LS8 && estimator.mode != MultiH::FUND_ESTIMATOR_MINIMAL7) {
+        std::cerr << "Error: unknown F estimator " << estimator.mode << " (FUND_ESTIMATOR_LS8 or FUND_ESTIMATOR_MINIMAL7)\n";
+        return false;
+    }
+    const bool minimal = estimator.mode == MultiH::FUND_ESTIMATOR_MINIMAL7;
+    if (minimal && !mh_estimate_fundamental_minimal) {
+        std::cerr << "Error: the engine library has no minimal-sample F estimator (mh_estimate_fundamental_minimal)\n";
+        return false;
+    }
     mh_engine* e = BorrowEngine(device);
     if (!e) return false;
     std::vector<double> s(2 * n), d(2 * n);
@@ -225,7 +237,9 @@ bool multih::FilterCorrespondencesByEpipolarGeometry(std::vector<cv::Point2d>& s
     int inl = 0;
     const bool ok = Check(mh_set_fundamental_metric(e, metric), "mh_set_fundamental_metric") &&
                     Check(mh_set_correspondences(e, s.data(), d.data(), nullptr, (int)n), "mh_set_correspondences") &&
-                    Check(mh_estimate_fundamental(e, seed, hypotheses, threshold, F, e2, mask.data(), &inl), "mh_estimate_fundamental");
+                    (minimal ? Check(mh_estimate_fundamental_minimal(e, seed, estimator.max_samples, estimator.confidence, threshold, F, e2,
+                                                                     mask.data(), &inl, nullptr), "mh_estimate_fundamental_minimal")
+                             : Check(mh_estimate_fundamental(e, seed, hypotheses, threshold, F, e2, mask.data(), &inl), "mh_estimate_fundamental"));
     ReturnEngine(device, e);
     if (!ok) return false;
     if (mask_out) *mask_out = mask;
@@ -303,10 +317,23 @@ bool MultiH::Run(bool points_only)
         // per-correspondence refinement of :807-838.
         std::vector<unsigned char> mask(N, 0);
         int inl = 0;
-        const bool ok = Check(mh_estimate_fundamental(engine, proposal_seed ^ 0xf00dull, fundamental_hypotheses,
-                                                      threshold_fundamental_matrix, fundamental_matrix, epipole_2,
-                                                      mask.data(), &inl),
-                              "mh_estimate_fundamental");
+        if (fundamental_estimator.mode != FUND_ESTIMATOR_LS8 && fundamental_estimator.mode != FUND_ESTIMATOR_MINIMAL7) {
+            std::cerr << "Error: unknown F estimator " << fundamental_estimator.mode << " (FUND_ESTIMATOR_LS8 or FUND_ESTIMATOR_MINIMAL7)\n";
+            return false;
+        }
+        const bool minimal = fundamental_estimator.mode == FUND_ESTIMATOR_MINIMAL7;
+        if (minimal && !mh_estimate_fundamental_minimal) {
+            std::cerr << "Error: the engine library has no minimal-sample F estimator (mh_estimate_fundamental_minimal)\n";
+            return false;
+        }
+        const bool ok = minimal ? Check(mh_estimate_fundamental_minimal(engine, proposal_seed ^ 0xf00dull, fundamental_estimator.max_samples,
+                                                                        fundamental_estimator.confidence, threshold_fundamental_matrix,
+                                                                        fundamental_matrix, epipole_2, mask.data(), &inl, nullptr),
+                                        "mh_estimate_fundamental_minimal")
+                                : Check(mh_estimate_fundamental(engine, proposal_seed ^ 0xf00dull, fundamental_hypotheses,
+                                                                threshold_fundamental_matrix, fundamental_matrix, epipole_2,
+                                                                mask.data(), &inl),
+                                        "mh_estimate_fundamental");
         double nrm = 0.0;
         for (double f : fundamental_matrix) nrm += f * f;
         degenerate_case = !ok || !(std::sqrt(nrm) >= 1e-5) || !std::isfinite(epipole_2[0]) ||
@@ -935,6 +962,14 @@ static int g_fund_metric = -1;
 static int g_front_stages[4] = { 0, 0, 0, 0 };
 extern "C" __attribute__((visibility("default")))
 void mhh_set_fundamental_metric(int metric) { g_fund_metric = metric; }
+// MultiH::SetFundamentalEstimator for the next mhh_run_process and mhh_filter_correspondences calls (mode < 0: the class default)
+static int g_fund_estimator = -1, g_fund_max_samples = 1000;
+static double g_fund_confidence = 0.99;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_fundamental_estimator(int mode, int max_samples, double confidence)
+{
+    g_fund_estimator = mode; g_fund_max_samples = max_samples; g_fund_confidence = confidence;
+}
 extern "C" __attribute__((visibility("default")))
 void mhh_get_front_stages(int out[4]) { for (int i = 0; i < 4; ++i) out[i] = g_front_stages[i]; }
 // multih::FilterCorrespondencesByEpipolarGeometry on plain arrays: mask (n flags) out; returns the number kept, -1 on failure
@@ -949,7 +984,9 @@ int mhh_filter_correspondences(const double* src_xy, const double* dst_xy, int n
         d[i] = cv::Point2d(dst_xy[2 * i], dst_xy[2 * i + 1]);
     }
     std::vector<unsigned char> m;
-    if (!multih::FilterCorrespondencesByEpipolarGeometry(s, d, a, threshold, seed, hypotheses, metric, device, &m)) return -1;
+    MultiH::FundEstimator est;
+    if (g_fund_estimator >= 0) { est.mode = g_fund_estimator; est.max_samples = g_fund_max_samples; est.confidence = g_fund_confidence; }
+    if (!multih::FilterCorrespondencesByEpipolarGeometry(s, d, a, threshold, seed, hypotheses, metric, device, &m, est)) return -1;
     for (int i = 0; i < n; ++i) mask[i] = m[i];
     return (int)s.size();
 }
@@ -1006,6 +1043,7 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     mh.SetCompatibilityCheck(g_post_filter != 0);
     mh.SetProposalRefit(g_proposal_refit != 0);
     if (g_fund_metric >= 0) mh.SetFundamentalMetric(g_fund_metric);
+    if (g_fund_estimator >= 0) mh.SetFundamentalEstimator(g_fund_estimator, g_fund_max_samples, g_fund_confidence);
     for (const auto& kv : g_tuning) mh.SetEngineTuning(kv.first, kv.second);
     if (g_radius > 0.0 && g_max_hits > 0) { mh.SetNeighbourRadius(g_radius, g_max_hits); if (g_knn > 0) mh.SetFallbackK(g_knn); }
     else if (g_radius > 0.0) mh.SetNeighbourRadius(g_radius);

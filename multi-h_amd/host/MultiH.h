@@ -158,6 +158,18 @@ public:
     // reference's call rejects from 1.84 px on).  include/multih_hip.h, mh_set_fundamental_metric.
     enum { FUND_SAMPSON = 0, FUND_EPIPOLAR_MAX = 1 };
     void SetFundamentalMetric(int m) { fundamental_metric = m; }
+    // Which estimator the F estimation runs.  FUND_ESTIMATOR_LS8 (default): `fundamental_hypotheses` normalised 8-point
+    // fits, the best-supported one refitted twice to its inliers (mh_estimate_fundamental).  FUND_ESTIMATOR_MINIMAL7: the
+    // scheme of the reference's cv::findFundamentalMat(CV_FM_RANSAC, thr, 0.99) (M/MultiH.cpp:775, M/main.cpp:399-409): at
+    // most max_samples minimal 7-point samples with up to three F each, the confidence stop, the best one returned WITHOUT
+    // a refit (mh_estimate_fundamental_minimal; OpenCV's own draws and un-normalised arithmetic are not reproduced).
+    // Any other mode makes Process() (and FilterCorrespondencesByEpipolarGeometry) fail with a message.
+    enum { FUND_ESTIMATOR_LS8 = 0, FUND_ESTIMATOR_MINIMAL7 = 1 };
+    struct FundEstimator { int mode = FUND_ESTIMATOR_LS8; int max_samples = 1000; double confidence = 0.99; };
+    void SetFundamentalEstimator(int mode, int max_samples = 1000, double confidence = 0.99)
+    {
+        fundamental_estimator.mode = mode; fundamental_estimator.max_samples = max_samples; fundamental_estimator.confidence = confidence;
+    }
     // r06: how many correspondences each stage of GetFundamentalMatrixAndRefineData (M/MultiH.cpp:770-848) let through in
     // the last Process(): the input, the RANSAC mask (:809), OptimalTriangulation (:815-817), distanceError <= 1 (:826).
     // All equal to the input when the caller supplied F (SetEpipolarGeometry): the points are then taken as they are.
@@ -213,6 +225,7 @@ protected:
     int iter_hypotheses = 0, iter_max_new = 4;
     int fundamental_hypotheses = 4000;
     int fundamental_metric = FUND_EPIPOLAR_MAX;
+    FundEstimator fundamental_estimator;
     FrontStages front_stages;
     int init_mode = INIT_DLT;
     bool run_compatibility_check = true;
@@ -249,10 +262,13 @@ namespace multih {
 // 1 000 of them, its own RNG, no refit — is outside /root/reference and not reproduced).  `metric` as
 // MultiH::SetFundamentalMetric.  Erases the rejected rows from all three vectors (order kept, as the reference's backward
 // erase loop keeps it) and returns false — leaving them untouched — when there are fewer than 8 rows, the sizes differ or the
-// engine fails.  mask_out (nullable): one flag per INPUT row.
+// engine fails.  mask_out (nullable): one flag per INPUT row.  `estimator` as MultiH::SetFundamentalEstimator: with
+// FUND_ESTIMATOR_MINIMAL7 the filter runs the caller's own scheme (7-point samples, confidence stop, no refit) and
+// `hypotheses` is not used.
 bool FilterCorrespondencesByEpipolarGeometry(std::vector<cv::Point2d>& srcPoints, std::vector<cv::Point2d>& dstPoints,
                                              std::vector<cv::Mat>& affines, double threshold = 2.0,
                                              uint64_t seed = 1234, int hypotheses = 4000,
                                              int metric = MultiH::FUND_EPIPOLAR_MAX, int device = 0,
-                                             std::vector<unsigned char>* mask_out = nullptr);
+                                             std::vector<unsigned char>* mask_out = nullptr,
+                                             const MultiH::FundEstimator& estimator = MultiH::FundEstimator());
 }

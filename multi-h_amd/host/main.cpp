@@ -14,6 +14,9 @@
 //                                (multih::FilterCorrespondencesByEpipolarGeometry); the value is the threshold in pixels, 0 switches
 //                                the filter off (what the harness did until r05)
 //                  [--f-metric opencv|sampson]   what the two F estimations compare with their thresholds (MultiH::SetFundamentalMetric)
+//                  [--f-estimator ls8|minimal]   which estimator the two F estimations run (MultiH::SetFundamentalEstimator): ls8, the
+//                                default, scores 8-point fits and refits the best twice; minimal is the scheme of the reference's
+//                                findFundamentalMat call: at most 1 000 7-point samples, confidence 0.99, no refit
 //                  [--stages <file>]   write the stage table as one JSON object: rows loaded, after the load filter, in
 //                                Process()'s RANSAC mask, after OptimalTriangulation, after distanceError <= 1 (M/MultiH.cpp:807-838)
 //                  [--points]   point-only correspondences: 4 numbers per input row (x1 y1 x2 y2, no affinity) and 5 per output
@@ -48,7 +51,8 @@
 // multih::FilterCorrespondencesByEpipolarGeometry); *loaded = rows read from the file.
 static bool LoadPointsFromFile(std::vector<cv::Point2d>& srcPoints, std::vector<cv::Point2d>& dstPoints,
                                std::vector<cv::Mat>& affines, const char* file, double filter_threshold,
-                               unsigned long long seed, int metric, int device, int* loaded, bool points_only)
+                               unsigned long long seed, int metric, int device, int* loaded, bool points_only,
+                               const MultiH::FundEstimator& estimator)
 {
     std::ifstream infile(file);
     if (!infile.is_open()) return false;
@@ -69,7 +73,7 @@ static bool LoadPointsFromFile(std::vector<cv::Point2d>& srcPoints, std::vector<
     if (loaded) *loaded = (int)srcPoints.size();
     if (filter_threshold > 0.0 && srcPoints.size() >= 8 &&
         !multih::FilterCorrespondencesByEpipolarGeometry(srcPoints, dstPoints, affines, filter_threshold,
-                                                         seed ^ 0x10adf117e4ull, 4000, metric, device))
+                                                         seed ^ 0x10adf117e4ull, 4000, metric, device, nullptr, estimator))
         return false;
     return true;
 }
@@ -97,7 +101,7 @@ int main(int argc, char** argv)
     if (argc < 3) {
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
-                     "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] "
+                     "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] [--f-estimator ls8|minimal] "
                      "[--stages file] [--points] [--estimator haf|3pt] [--ranks n]\n";
         return 2;
     }
@@ -107,6 +111,7 @@ int main(int argc, char** argv)
     int ranks = 0;
     double load_filter = 2.0;                                          // M/main.cpp:400
     int f_metric = MultiH::FUND_EPIPOLAR_MAX;
+    MultiH::FundEstimator f_estimator;
     std::string epi, neighbourhood = "knn", stages_path;
     bool points_only = false;
     int estimator = MultiH::ESTIMATOR_HAF;
@@ -137,6 +142,11 @@ int main(int argc, char** argv)
             if (std::string(v) == "sampson") f_metric = MultiH::FUND_SAMPSON;
             else if (std::string(v) == "opencv") f_metric = MultiH::FUND_EPIPOLAR_MAX;
             else { std::cerr << "--f-metric: opencv or sampson\n"; return 2; }
+        }
+        else if (k == "--f-estimator") {
+            if (std::string(v) == "ls8") f_estimator.mode = MultiH::FUND_ESTIMATOR_LS8;
+            else if (std::string(v) == "minimal") f_estimator.mode = MultiH::FUND_ESTIMATOR_MINIMAL7;
+            else { std::cerr << "--f-estimator: ls8 or minimal\n"; return 2; }
         }
         else if (k == "--stages") stages_path = v;
         else { std::cerr << "unknown option " << k << "\n"; return 2; }
@@ -233,7 +243,7 @@ int main(int argc, char** argv)
     std::vector<cv::Mat> origAffines;
     int rows_loaded = 0;
     if (!LoadPointsFromFile(srcPointsOrig, dstPointsOrig, origAffines, argv[1], epi.empty() ? load_filter : 0.0, seed, f_metric,
-                            comm ? rank : 0, &rows_loaded, points_only)) {
+                            comm ? rank : 0, &rows_loaded, points_only, f_estimator)) {
         std::cerr << "cannot read " << argv[1] << " (or the load filter failed)\n";
         return finish(1);
     }
@@ -251,6 +261,7 @@ int main(int argc, char** argv)
         multiH->SetEpipolarGeometry(F, e2);
     }
     multiH->SetFundamentalMetric(f_metric);
+    multiH->SetFundamentalEstimator(f_estimator.mode, f_estimator.max_samples, f_estimator.confidence);
     multiH->SetProposal(seed, hypotheses, max_models);
     multiH->SetFixedIterations(iterations);
     if (comm) {
@@ -277,7 +288,8 @@ int main(int argc, char** argv)
                << ", \"load_filter_px\": " << (epi.empty() ? load_filter : 0.0) << ", \"in_ransac_mask\": " << st.in_ransac_mask
                << ", \"ransac_px\": " << thrF << ", \"after_optimal_triangulation\": " << st.triangulated
                << ", \"after_distance_error\": " << st.affine_consistent << ", \"f_metric\": \""
-               << (f_metric == MultiH::FUND_SAMPSON ? "sampson" : "opencv") << "\"}\n";
+               << (f_metric == MultiH::FUND_SAMPSON ? "sampson" : "opencv") << "\", \"f_estimator\": \""
+               << (f_estimator.mode == MultiH::FUND_ESTIMATOR_MINIMAL7 ? "minimal" : "ls8") << "\"}\n";
         }
     }
 
