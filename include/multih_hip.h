@@ -194,6 +194,29 @@ MH_API int mh_set_models(mh_engine* e, const double* H, int m);
 MH_API int mh_get_models(mh_engine* e, double* H /* m x 9 */);
 MH_API int mh_get_model_count(mh_engine* e, int* m);
 MH_API int mh_get_samples(mh_engine* e, int* idx /* m x 4, valid after mh_propose_dlt4 */);
+/* The sampler of mh_propose_dlt4 and mh_prefetch_dlt4.  Sticky per engine; mh_set_correspondences does not reset it.
+ *   MH_SAMPLER_UNIFORM  every index uniform over all correspondences (default; uniform_per_16 is ignored).
+ *   MH_SAMPLER_LOCAL    neighbourhood-guided: needs the sampling table (mh_build_sample_neighbours); both entry points answer
+ *                       MH_ERR_NOT_SET without one.  Hypothesis c = first + s, draws r_j = splitmix64(seed + (c << 8) + j)
+ *                       (64-bit wrap-around) as under the uniform sampler:
+ *                         (c & 15) < uniform_per_16: the uniform tuple of c, unchanged;
+ *                         otherwise i0 = ((r_0 >> 32) n) >> 32 (the uniform tuple's first index), then for j = 1 .. 63 the
+ *                         candidate nbr[i0 k + (((r_j >> 32) k) >> 32)] is taken unless it is already in the tuple, until there
+ *                         are four; slots still empty after draw 63 take the first index.
+ *                       uniform_per_16 in [0, 16]; with 16 the batch is the uniform batch.  The estimator is the same 4-point
+ *                       DLT, bit for bit: only the tuple changes.  The ranks of a sharded mh_select_greedy must agree on the
+ *                       sampler, k and uniform_per_16: their records carry the engine's SETTING at the time of the selection
+ *                       (not what the resident batch was proposed with: a caller who changes the sampler between propose and
+ *                       select, or loads models with mh_set_models, is compared on the setting alone). */
+#define MH_SAMPLER_UNIFORM 0
+#define MH_SAMPLER_LOCAL 1
+MH_API int mh_set_sampler(mh_engine* e, int sampler, int uniform_per_16);
+/* The local sampler's table: the dense n x k table of mh_build_neighbors_knn (same kernels, same rule: float32 distance in
+ * (x1,y1,x2,y2), hits ordered by (d, j), j != i, grid or exhaustive pass by key 31, MH_ERR_INVALID when a query lacks k finite
+ * hits), 3 <= k <= 32, k < n, kept in a device buffer of the sampler's own: the labeling graph is neither built, replaced nor
+ * read.  mh_set_correspondences drops the table.  mh_get_sample_neighbours copies it out (MH_ERR_NOT_SET without one). */
+MH_API int mh_build_sample_neighbours(mh_engine* e, int k);
+MH_API int mh_get_sample_neighbours(mh_engine* e, int* nbr /* n x k, nullable */, int* k_out /* nullable */);
 
 /* ---- score -------------------------------------------------------------- */
 /* Residual definition used by mh_score / mh_residual_matrix / mh_get_residual_rows:

@@ -12,6 +12,7 @@ so import it with importlib:
     import importlib; mh = importlib.import_module("multi-h_amd")
 """
 from . import synth  # noqa: F401
-from .capi import Engine, MultiHError, device_count, load_library, LIB_PATH, SYMBOLS  # noqa: F401
+from .capi import Engine, MultiHError, device_count, load_library, LIB_PATH, SYMBOLS, SAMPLER_UNIFORM, SAMPLER_LOCAL  # noqa: F401
 
-__all__ = ["Engine", "MultiHError", "device_count", "load_library", "synth", "LIB_PATH", "SYMBOLS"]
+__all__ = ["Engine", "MultiHError", "device_count", "load_library", "synth", "LIB_PATH", "SYMBOLS",
+           "SAMPLER_UNIFORM", "SAMPLER_LOCAL"]

@@ -18,6 +18,7 @@ ERR_NAMES = {-1: "MH_ERR_NO_DEVICE", -2: "MH_ERR_INVALID", -3: "MH_ERR_HIP", -4:
              -5: "MH_ERR_OVERFLOW"}
 BUF_COUNTS, BUF_MODELS, BUF_RESIDUALS, BUF_LABELS, BUF_COST, BUF_LABEL_COUNTS = 0, 1, 2, 3, 4, 6
 ESTIMATORS = {"haf": 0, "3pt": 1}      # MH_ESTIMATOR_HAF, MH_ESTIMATOR_3PT
+SAMPLER_UNIFORM, SAMPLER_LOCAL = 0, 1  # MH_SAMPLER_UNIFORM, MH_SAMPLER_LOCAL
 K_DLT4, K_RESIDUAL, K_SCORE, K_DATACOST, K_EXPAND, K_REESTIMATE, K_COSTMATRIX = 0, 1, 2, 3, 4, 5, 6
 
 # every symbol include/multih_hip.h declares (tests check the export table against this)
@@ -27,7 +28,7 @@ SYMBOLS = [
     "mh_set_neighbors_csr", "mh_build_neighbors_knn", "mh_build_neighbors_knn_radius", "mh_build_neighbors_radius", "mh_get_sym_graph", "mh_set_fundamental_metric", "mh_propose_fund8",
     "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_propose_fund7", "mh_get_fund7_samples", "mh_estimate_fundamental_minimal", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons", "mh_refine_points",
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
-    "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_samples", "mh_set_residual_mode", "mh_score",
+    "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_set_residual_mode", "mh_score",
     "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_data_cost", "mh_expand",
     "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
     "mh_profile_get", "mh_set_tuning",
@@ -306,6 +307,21 @@ class Engine:
         idx = np.empty((self.model_count, 4), dtype=np.int32)
         self._check(self.lib.mh_get_samples(self._h, _p(idx, C.c_int)))
         return idx
+
+    def set_sampler(self, sampler: int, uniform_per_16: int = 0):
+        """mh_set_sampler: SAMPLER_UNIFORM (default) or SAMPLER_LOCAL (needs build_sample_neighbours); sticky."""
+        self._check(self.lib.mh_set_sampler(self._h, int(sampler), int(uniform_per_16)))
+
+    def build_sample_neighbours(self, k: int):
+        """mh_build_sample_neighbours: the local sampler's n x k table (the labeling graph is not touched)."""
+        self._check(self.lib.mh_build_sample_neighbours(self._h, int(k)))
+
+    def get_sample_neighbours(self):
+        k = C.c_int(0)
+        self._check(self.lib.mh_get_sample_neighbours(self._h, None, C.byref(k)))
+        nbr = np.empty((self.n, k.value), dtype=np.int32)
+        self._check(self.lib.mh_get_sample_neighbours(self._h, _p(nbr, C.c_int), None))
+        return nbr
 
     # -- score --------------------------------------------------------------
     def set_residual_mode(self, symmetric: bool):

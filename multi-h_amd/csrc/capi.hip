@@ -407,6 +407,7 @@ void mh_destroy(mh_engine* e)
     if (e->h_batch) (void)hipHostFree(e->h_batch);
     e->knn_tmp.release(); e->knn_part_i.release(); e->knn_part_d.release();
     e->knn_cell.release(); e->knn_count.release(); e->knn_start.release(); e->knn_P.release(); e->knn_orig.release();
+    e->smp_nbr.release();
     for (int c = 0; c < 4; ++c) e->sel_pts[c].release();
     e->sel_pack_count.release();
     for (int c = 0; c < 4; ++c) e->sel_gone[c].release();
@@ -487,6 +488,7 @@ int mh_set_correspondences(mh_engine* e, const double* src_xy, const double* dst
     if (rc0) return rc0;
     e->pf_count = 0;
     e->pf_head = 0;
+    e->smp_k = 0;                                       // the sampling table belongs to the old point set
     // +1 element of slack: the 16-B vector loads of the residual sweep never cross the end,
     // but keep the allocation even-sized for them.
     const size_t cap = (size_t)n + 2;
@@ -578,14 +580,12 @@ int mh_set_neighbors_csr(mh_engine* e, const int* rowptr, const int* col, int n)
     });
 }
 
-// k nearest hits per query, optionally only those within `radius` (<= 0: no cut).
-static int build_knn_graph(mh_engine* e, int k, double radius)
+// The dense n x k table of the k nearest hits per query into tbl (n * k ints, reserved by the caller), those beyond `radius`
+// (<= 0: no cut) set to -1; e->gb_info (8 ints) is cleared and its word 2 collects index errors (k_hits_filter: a query with
+// fewer than k candidates at finite float32 distance, non-finite coordinates).
+static int knn_table(mh_engine* e, int k, double radius, int* tbl)
 {
-    int rc = require_points(e);
-    if (rc) return rc;
-    if (k < 1 || k > 32 || k >= e->n) return fail(MH_ERR_INVALID, "k must be in [1, 32] and < n");
     const int n = e->n;
-    HIPCHK(e->knn_tmp.reserve((size_t)n * k));
     HIPCHK(e->gb_info.reserve(8));
     HIPCHK(hipMemsetAsync(e->gb_info.p, 0, sizeof(int) * 8, e->stream));
     // r05: through a grid over the source image when the points' bounding box is finite (knn.hip, k_knn_grid: the same table,
@@ -598,11 +598,11 @@ static int build_knn_graph(mh_engine* e, int k, double radius)
         HIPCHK(e->knn_start.reserve((size_t)G * G + 1));
         HIPCHK(e->knn_P.reserve((size_t)4 * n));
         HIPCHK(e->knn_orig.reserve((size_t)n));
-        const hipError_t hg = launch_knn_grid(pp, k, e->knn_tmp.p, e->knn_cell.p, e->knn_count.p, e->knn_start.p, e->knn_P.p, e->knn_orig.p, e->stream);
+        const hipError_t hg = launch_knn_grid(pp, k, tbl, e->knn_cell.p, e->knn_count.p, e->knn_start.p, e->knn_P.p, e->knn_orig.p, e->stream);
         if (hg == hipSuccess) {
             const float r2g = radius > 0.0 ? (float)radius * (float)radius : INFINITY;
-            HIPCHK(launch_hits_filter(pp, k, r2g, e->knn_tmp.p, e->gb_info.p + 2, e->stream));
-            return device_sym_graph(e, nullptr, k, e->knn_tmp.p);
+            HIPCHK(launch_hits_filter(pp, k, r2g, tbl, e->gb_info.p + 2, e->stream));
+            return MH_OK;
         }
         if (hg != hipErrorInvalidValue) HIPCHK(hg);      // InvalidValue: no usable grid (all source points coincide, or a cell size beyond float32) — the exhaustive pass below
     }
@@ -615,11 +615,23 @@ static int build_knn_graph(mh_engine* e, int k, double radius)
         HIPCHK(e->knn_part_d.reserve((size_t)splits * n * kk));
         HIPCHK(e->knn_part_i.reserve((size_t)splits * n * kk));
     }
-    HIPCHK(launch_knn(e->pts(), k, e->knn_tmp.p, splits, e->knn_part_d.p, e->knn_part_i.p, e->stream));
+    HIPCHK(launch_knn(e->pts(), k, tbl, splits, e->knn_part_d.p, e->knn_part_i.p, e->stream));
     // the reference's radius (M/MultiH.cpp:252-253) in the kernels' float32 arithmetic; without a radius the pass only
     // validates the indices (non-finite coordinates leave garbage in the k-NN table)
     const float r2 = radius > 0.0 ? (float)radius * (float)radius : INFINITY;
-    HIPCHK(launch_hits_filter(e->pts(), k, r2, e->knn_tmp.p, e->gb_info.p + 2, e->stream));
+    HIPCHK(launch_hits_filter(e->pts(), k, r2, tbl, e->gb_info.p + 2, e->stream));
+    return MH_OK;
+}
+
+// k nearest hits per query, optionally only those within `radius` (<= 0: no cut).
+static int build_knn_graph(mh_engine* e, int k, double radius)
+{
+    int rc = require_points(e);
+    if (rc) return rc;
+    if (k < 1 || k > 32 || k >= e->n) return fail(MH_ERR_INVALID, "k must be in [1, 32] and < n");
+    HIPCHK(e->knn_tmp.reserve((size_t)e->n * k));
+    rc = knn_table(e, k, radius, e->knn_tmp.p);
+    if (rc) return rc;
     return device_sym_graph(e, nullptr, k, e->knn_tmp.p);
 }
 
@@ -631,6 +643,38 @@ int mh_build_neighbors_knn(mh_engine* e, int k)
 int mh_build_neighbors_knn_radius(mh_engine* e, int k, double radius)
 {
     return guarded([&]() -> int { return build_knn_graph(e, k, radius); });
+}
+
+int mh_build_sample_neighbours(mh_engine* e, int k)
+{
+    return guarded([&]() -> int {
+    int rc = require_points(e);
+    if (rc) return rc;
+    if (k < 3 || k > 32 || k >= e->n) return fail(MH_ERR_INVALID, "k must be in [3, 32] and < n");
+    rc = quiesce(e);                                   // a prefetched DLT on the second stream may still read the old table
+    if (rc) return rc;
+    e->smp_k = 0;                                      // no table until this one is complete and valid
+    HIPCHK(e->smp_nbr.reserve((size_t)e->n * k));
+    rc = knn_table(e, k, 0.0, e->smp_nbr.p);
+    if (rc) return rc;
+    int err = 0;
+    HIPCHK(fetch_ints(e, &err, e->gb_info.p + 2, 1));
+    if (err) return fail(MH_ERR_INVALID, "neighbour index out of range (non-finite coordinates, or fewer than k neighbours at finite float32 distance?)");
+    e->smp_k = k;
+    return MH_OK;
+    });
+}
+
+int mh_get_sample_neighbours(mh_engine* e, int* nbr, int* k_out)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (e->smp_k <= 0) return fail(MH_ERR_NOT_SET, "no sampling table; call mh_build_sample_neighbours");
+    HIPCHK(hipSetDevice(e->device));
+    if (nbr) HIPCHK(fetch_ints(e, nbr, e->smp_nbr.p, (size_t)e->n * e->smp_k));
+    if (k_out) *k_out = e->smp_k;
+    return MH_OK;
+    });
 }
 
 int mh_build_neighbors_radius(mh_engine* e, double radius, long long max_hits, long long* hits_out)

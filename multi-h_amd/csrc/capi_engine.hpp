@@ -233,6 +233,13 @@ struct mh_engine {
     DevBuf<float> knn_P;
     DevBuf<int> knn_tmp, knn_part_i;
     DevBuf<float> knn_part_d;
+    // the proposer's sampler (mh_set_sampler, sticky) and its table (mh_build_sample_neighbours): the dense n x smp_k k-NN table
+    // in a buffer of its own — the labeling graph neither feeds it nor sees it; mh_set_correspondences drops it (smp_k = 0)
+    int sampler = MH_SAMPLER_UNIFORM, sampler_uniform_per_16 = 0;
+    DevBuf<int> smp_nbr;
+    int smp_k = 0;
+    // what launch_dlt4 gets under the engine's sampler (nbr == null: the uniform kernels)
+    Dlt4Local dlt_local() const { return sampler == MH_SAMPLER_LOCAL ? Dlt4Local{ smp_nbr.p, smp_k, sampler_uniform_per_16 } : Dlt4Local{}; }
 
     bool profiling = false;
     KernelTimer timers[MH_K_COUNT_];

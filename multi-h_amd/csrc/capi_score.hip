@@ -63,17 +63,30 @@ int mh_propose_dlt4(mh_engine* e, unsigned long long seed, long long first, int 
     if (rc) return rc;
     if (m <= 0) return fail(MH_ERR_INVALID, "m must be positive");
     if (e->n < 4) return fail(MH_ERR_INVALID, "need at least 4 correspondences");
+    if (e->sampler == MH_SAMPLER_LOCAL && e->smp_k <= 0) return fail(MH_ERR_NOT_SET, "the local sampler has no table; call mh_build_sample_neighbours");
     HIPCHK(e->H.reserve((size_t)m * 9));
     HIPCHK(e->samples.reserve((size_t)m * 4));
     HIPCHK(reserve_counts(e, (size_t)m + 1));
     {
         ScopedTimer t(e, MH_K_DLT4);
-        HIPCHK(launch_dlt4(e->pts(), seed, first, m, e->samples.p, e->H.p, e->stream, e->tune_dlt_variant == 1 ? 1 : 0));   // alone on the device: the register form (0.26 against 0.40 ms per 100k)
+        HIPCHK(launch_dlt4(e->pts(), seed, first, m, e->samples.p, e->H.p, e->stream, e->tune_dlt_variant == 1 ? 1 : 0, e->dlt_local()));   // alone on the device: the register form (0.26 against 0.40 ms per 100k)
     }
     e->m = m;
     e->have_samples = true;
     e->cost_L = 0;
     e->counts_fresh = false; ++e->models_seq;
+    return MH_OK;
+    });
+}
+
+int mh_set_sampler(mh_engine* e, int sampler, int uniform_per_16)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (sampler != MH_SAMPLER_UNIFORM && sampler != MH_SAMPLER_LOCAL) return fail(MH_ERR_INVALID, "unknown sampler");
+    if (uniform_per_16 < 0 || uniform_per_16 > 16) return fail(MH_ERR_INVALID, "uniform_per_16 must be in [0, 16]");
+    e->sampler = sampler;
+    e->sampler_uniform_per_16 = uniform_per_16;
     return MH_OK;
     });
 }
@@ -291,6 +304,7 @@ int mh_prefetch_dlt4(mh_engine* e, unsigned long long seed, long long first, int
     if (rc) return rc;
     if (m <= 0) return fail(MH_ERR_INVALID, "m must be positive");
     if (e->n < 4) return fail(MH_ERR_INVALID, "need at least 4 correspondences");
+    if (e->sampler == MH_SAMPLER_LOCAL && e->smp_k <= 0) return fail(MH_ERR_NOT_SET, "the local sampler has no table; call mh_build_sample_neighbours");
     rc = ensure_side_stream(e);
     if (rc) return rc;
     if (e->pf_count >= mh_engine::PF_DEPTH) return fail(MH_ERR_INVALID, "two batches are already prefetched: adopt one first (mh_adopt_prefetched)");
@@ -313,7 +327,7 @@ int mh_prefetch_dlt4(mh_engine* e, unsigned long long seed, long long first, int
         // fit next to the sweep's five waves per SIMD, so it shares the compute units with the sweep's head, while the
         // register form (128) has to displace sweep workgroups and its run time is added to the step: 0.964 against 0.994 ms
         // per step at the 12 500-hypothesis shard, 1.891 / 1.928 at 25 000, 7.41 / 7.41 at 100 000 (tools/shard_proxy.py DLTFORM=1).
-        HIPCHK(launch_dlt4(e->pts(), seed, first, m, e->pf_samples[slot].p, e->pf_H[slot].p, e->side_stream, e->tune_dlt_variant == 2 ? 0 : 1));
+        HIPCHK(launch_dlt4(e->pts(), seed, first, m, e->pf_samples[slot].p, e->pf_H[slot].p, e->side_stream, e->tune_dlt_variant == 2 ? 0 : 1, e->dlt_local()));
     }
     HIPCHK(hipEventRecord(e->pf_ev[slot], e->side_stream));
     e->pf_m[slot] = m;

@@ -101,6 +101,9 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
     const bool refine = e->tune_select_refine != 0;
     const bool refit3 = e->estimator == MH_ESTIMATOR_3PT;
     const bool refine_usable = refine && e->have_epi && (refit3 || e->have_aff);
+    // The proposer's sampler travels in the word too: bit 3 the local sampler, bits 4-9 its k, bits 10-14 uniform_per_16 — all
+    // zero under the default, so those records are what they were.  A rank-independent batch needs the ranks to agree on it.
+    const int sampler_bits = e->sampler == MH_SAMPLER_LOCAL ? (8 | (e->smp_k << 4) | (e->sampler_uniform_per_16 << 10)) : 0;
     if (refine && !refine_usable)
         local_failure(MH_ERR_NOT_SET, refit3 ? "mh_select_greedy with refitted winners (mh_set_tuning key 30) needs the epipolar geometry"
                                              : "mh_select_greedy with refitted winners (mh_set_tuning key 30) needs affinities and the epipolar geometry");
@@ -212,7 +215,7 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
         const int local_err = local_rc != MH_OK ? 1 : 0;
         const bool gather_scores = sharded && first && longest > 0;      // north_star's exchange, once per batch
         HIPCHK(launch_sel_argmax(e->sel_counts.p, orig, Mc, my_off, key_local, gather_scores ? e->sel_scores.p : nullptr, s));
-        HIPCHK(launch_sel_record(e->sel_counts.p, orig, Hs, Mc, my_off, key_local, local_err, symmetric | (refine ? 2 : 0) | (refine && refit3 ? 4 : 0), my_record, s));
+        HIPCHK(launch_sel_record(e->sel_counts.p, orig, Hs, Mc, my_off, key_local, local_err, symmetric | (refine ? 2 : 0) | (refine && refit3 ? 4 : 0) | sampler_bits, my_record, s));
         if (sharded) {
             if (gather_scores) {
                 rc = exchange(e, e->sel_scores.p, e->sel_gathered.p, sizeof(int) * (size_t)longest, s);
@@ -242,7 +245,7 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
         if (e->h_sel[4] != 0)                            // every rank sees the same word, so every rank leaves here
             return fail(e->h_sel[4] == 3 ? MH_ERR_INVALID : MH_ERR_HIP,
                         e->h_sel[4] == 2 ? "greedy selection: the gathered score vector and the ranks' records disagree about the winner"
-                        : e->h_sel[4] == 3 ? "greedy selection: the ranks are not in the same residual mode (mh_set_residual_mode) or do not agree on refitted winners (mh_set_tuning key 30) or the estimator (mh_set_estimator)"
+                        : e->h_sel[4] == 3 ? "greedy selection: the ranks are not in the same residual mode (mh_set_residual_mode) or do not agree on refitted winners (mh_set_tuning key 30), the estimator (mh_set_estimator) or the proposer's sampler (mh_set_sampler)"
                                            : "greedy selection: a rank reported an error");
         const int best = e->h_sel[0];
         if (best < need) break;

@@ -55,6 +55,44 @@ __device__ __forceinline__ void sample4(unsigned long long seed, unsigned long l
     sample_tuple<4, 64>(seed, m, N, out);
 }
 
+// The tuple of hypothesis c under the sampler of k_dlt4 / k_dlt4_lds.  The kernels hand on their trailing
+// arguments: none under DLT_SAMPLER_UNIFORM, which is sample4 and nothing else; the sampling table under DLT_SAMPLER_LOCAL.
+// There the hypotheses with (c & 15) < uniform_per_16 keep the uniform tuple; the others take the uniform tuple's first index
+// i0 and fill up from row i0 of the table (nbr: n x k, the k nearest neighbours of every point, all in [0, n)): draw
+// j = 1 .. 63 proposes nbr[i0 k + (((r_j >> 32) k) >> 32)], taken unless it is already in the tuple; slots still empty after
+// draw 63 take out[0] (sample_tuple's exhaustion rule).  One more dependent load per index than the uniform form; the indices
+// live in named registers, not in an indexed array (no scratch).
+constexpr int DLT_SAMPLER_UNIFORM = 0, DLT_SAMPLER_LOCAL = 1;
+
+__device__ __forceinline__ void sample4_by(unsigned long long seed, unsigned long long c, unsigned int N, int out[4])
+{
+    sample4(seed, c, N, out);
+}
+
+__device__ __forceinline__ void sample4_by(unsigned long long seed, unsigned long long c, unsigned int N, int out[4],
+                                           const int* __restrict__ nbr, int k, int uniform_per_16)
+{
+    if ((int)(c & 15ull) < uniform_per_16) { sample4(seed, c, N, out); return; }
+    const unsigned long long base = seed + (c << 8);
+    const int i0 = (int)(((splitmix64(base) >> 32) * (unsigned long long)N) >> 32);
+    const int* __restrict__ row = nbr + (size_t)i0 * (size_t)k;
+    int o1 = -1, o2 = -1, o3 = -1, got = 1;                       // (-1 equals no table entry)
+    for (unsigned int j = 1; j < 64 && got < 4; ++j) {
+        const unsigned long long r = splitmix64(base + j);
+        const int cand = row[(int)(((r >> 32) * (unsigned long long)(unsigned int)k) >> 32)];
+        if (cand != i0 && cand != o1 && cand != o2) {
+            o1 = got == 1 ? cand : o1;
+            o2 = got == 2 ? cand : o2;
+            o3 = got == 3 ? cand : o3;
+            ++got;
+        }
+    }
+    out[0] = i0;
+    out[1] = got > 1 ? o1 : i0;
+    out[2] = got > 2 ? o2 : i0;
+    out[3] = got > 3 ? o3 : i0;
+}
+
 // circle-method schedule: round r, slot k (1..4): a = (r+k)%9, b = (r+9-k)%9
 __device__ __forceinline__ void rr_pair(int r, int slot, int& p, int& q)
 {
@@ -147,12 +185,16 @@ __device__ __forceinline__ void null9_vector(double (*W)[HPW], int hs, double g[
 // 0.26 ms per 100 000 hypotheses, same bits), but the one of the two that fits beside a resident sweep (capi_score.hip, mh_prefetch_dlt4).
 // At most 72 VGPRs: that is what the resident residual sweep leaves free on every SIMD (5 waves of 88 registers), so a
 // workgroup of this kernel fits beside it on any compute unit (residual.hip, k_residual_resident).
+// SAMPLER / TABLE: DLT_SAMPLER_UNIFORM and no further argument, or DLT_SAMPLER_LOCAL and the table (const int* nbr, int k,
+// int uniform_per_16; sample4_by).  The local instantiation keeps the 72 registers: it fits beside the sweep like the uniform one.
+template <int SAMPLER, class... TABLE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(72)))
 k_dlt4_lds(const double* __restrict__ x1, const double* __restrict__ y1,
        const double* __restrict__ x2, const double* __restrict__ y2, int N,
        unsigned long long seed, long long first, int M, int* __restrict__ idx_out,
-       double* __restrict__ H_out)
+       double* __restrict__ H_out, TABLE... table)
 {
+    static_assert(sizeof...(TABLE) == (SAMPLER == DLT_SAMPLER_LOCAL ? 3 : 0), "the local sampler takes nbr, k, uniform_per_16");
     // Issue priority above the sweep's waves (priority 0).  A SIMD issues from its oldest ready wave first; beside five
     // resident sweep waves that always have an FP64 instruction ready, a wave of this kernel hardly ever issued: the DLT
     // of the next batch took the whole sweep and its own run time again after it, whatever the stream's priority and
@@ -172,7 +214,7 @@ k_dlt4_lds(const double* __restrict__ x1, const double* __restrict__ y1,
     // ---- sample + normalise (all 4 lanes of a hypothesis redundantly) ----
     int id[4] = { 0, 0, 0, 0 };
     double sx[4], sy[4], dx[4], dy[4];
-    if (live) sample4(seed, (unsigned long long)(first + m), (unsigned int)N, id);
+    if (live) sample4_by(seed, (unsigned long long)(first + m), (unsigned int)N, id, table...);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         sx[k] = x1[id[k]]; sy[k] = y1[id[k]]; dx[k] = x2[id[k]]; dy[k] = y2[id[k]];
@@ -356,12 +398,14 @@ __device__ __forceinline__ double column_norm(const Col& a)
     return n;
 }
 
+template <int SAMPLER, class... TABLE>          // (as k_dlt4_lds)
 __global__ void __launch_bounds__(256)
 k_dlt4(const double* __restrict__ x1, const double* __restrict__ y1,
        const double* __restrict__ x2, const double* __restrict__ y2, int N,
        unsigned long long seed, long long first, int M, int* __restrict__ idx_out,
-       double* __restrict__ H_out)
+       double* __restrict__ H_out, TABLE... table)
 {
+    static_assert(sizeof...(TABLE) == (SAMPLER == DLT_SAMPLER_LOCAL ? 3 : 0), "the local sampler takes nbr, k, uniform_per_16");
     __builtin_amdgcn_s_setprio(3);           // (as k_dlt4_lds; this form runs alone on the device, where it changes nothing)
     __shared__ double sN[4][9][HPW];         // column norms, then the null vector: 1.1 KB per wave
     __shared__ double sK[4][6][HPW];         // the normalisation, parked while the sweeps need the registers
@@ -376,7 +420,7 @@ k_dlt4(const double* __restrict__ x1, const double* __restrict__ y1,
     {
         int id[4] = { 0, 0, 0, 0 };
         double sx[4], sy[4], dx[4], dy[4];
-        if (live) sample4(seed, (unsigned long long)(first + m), (unsigned int)N, id);
+        if (live) sample4_by(seed, (unsigned long long)(first + m), (unsigned int)N, id, table...);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             sx[k] = x1[id[k]]; sy[k] = y1[id[k]]; dx[k] = x2[id[k]]; dy[k] = y2[id[k]];
@@ -836,15 +880,24 @@ hipError_t launch_fund8(const Points& p, unsigned long long seed, long long firs
 }
 
 hipError_t launch_dlt4(const Points& p, unsigned long long seed, long long first, int M,
-                       int* idx_out, double* H_out, hipStream_t s, int variant)
+                       int* idx_out, double* H_out, hipStream_t s, int variant, Dlt4Local local)
 {
     if (M <= 0) return hipSuccess;
     const int per_block = 4 * HPW;
-    if (variant == 1)
-        hipLaunchKernelGGL(k_dlt4_lds, dim3((M + per_block - 1) / per_block), dim3(256), 0, s, p.x1, p.y1,
+    const dim3 grid((M + per_block - 1) / per_block);
+    if (local.nbr) {
+        if (local.k < 1 || local.k >= p.n || local.uniform_per_16 < 0 || local.uniform_per_16 > 16) return hipErrorInvalidValue;
+        if (variant == 1)
+            hipLaunchKernelGGL((k_dlt4_lds<DLT_SAMPLER_LOCAL, const int*, int, int>), grid, dim3(256), 0, s, p.x1, p.y1,
+                               p.x2, p.y2, p.n, seed, first, M, idx_out, H_out, local.nbr, local.k, local.uniform_per_16);
+        else
+            hipLaunchKernelGGL((k_dlt4<DLT_SAMPLER_LOCAL, const int*, int, int>), grid, dim3(256), 0, s, p.x1, p.y1,
+                               p.x2, p.y2, p.n, seed, first, M, idx_out, H_out, local.nbr, local.k, local.uniform_per_16);
+    } else if (variant == 1)
+        hipLaunchKernelGGL(k_dlt4_lds<DLT_SAMPLER_UNIFORM>, grid, dim3(256), 0, s, p.x1, p.y1,
                            p.x2, p.y2, p.n, seed, first, M, idx_out, H_out);
     else
-        hipLaunchKernelGGL(k_dlt4, dim3((M + per_block - 1) / per_block), dim3(256), 0, s, p.x1, p.y1,
+        hipLaunchKernelGGL(k_dlt4<DLT_SAMPLER_UNIFORM>, grid, dim3(256), 0, s, p.x1, p.y1,
                            p.x2, p.y2, p.n, seed, first, M, idx_out, H_out);
     return hipGetLastError();
 }

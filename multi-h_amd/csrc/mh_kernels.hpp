@@ -76,8 +76,11 @@ hipError_t launch_compat_fit(const double* pts, const int* begin, int clusters, 
                              double* H, unsigned char* ok, hipStream_t s);
 
 // --- dlt4.hip ---------------------------------------------------------------
+// local.nbr != null: the neighbourhood-guided sampler (dlt4.hip, sample4_by) over the n x k table nbr, every entry in [0, n)
+struct Dlt4Local { const int* nbr = nullptr; int k = 0; int uniform_per_16 = 0; };
 hipError_t launch_dlt4(const Points& p, unsigned long long seed, long long first, int M,
-                       int* idx_out, double* H_out, hipStream_t s, int variant = 0 /* 1: the LDS-staged form */);
+                       int* idx_out, double* H_out, hipStream_t s, int variant = 0 /* 1: the LDS-staged form */,
+                       Dlt4Local local = Dlt4Local{});
 
 hipError_t launch_fund8(const Points& p, unsigned long long seed, long long first, int M,
                         int* idx_out /* M x 8 */, double* F_out, hipStream_t s);
@@ -302,7 +305,7 @@ hipError_t launch_argmin_labels(const int* cost, int L, int n, int* label, long 
 hipError_t launch_sel_pack_points(const Points& p, const unsigned char* mask, double* cx1, double* cy1, double* cx2, double* cy2,
                                   int* count, hipStream_t s);
 // one rank's offer in a round of the greedy selection: 88 bytes, the unit of the sharded exchange
-struct SelRecord { unsigned long long key; double H[9]; int err; int mode; };      // mode: bit 0 the rank's residual mode, bit 1 refitted winners (key 30), bit 2 those refits by the 3-point estimator (mh_set_estimator); the ranks' words must agree
+struct SelRecord { unsigned long long key; double H[9]; int err; int mode; };      // mode: bit 0 the rank's residual mode, bit 1 refitted winners (key 30), bit 2 those refits by the 3-point estimator (mh_set_estimator), bits 3-14 the proposer's sampler (capi_select.hip); the ranks' words must agree
 static_assert(sizeof(SelRecord) == 88, "the exchanged record is 88 bytes");
 hipError_t launch_sel_argmax(const int* counts, const int* orig, int Mc, unsigned int my_off, unsigned long long* key,
                              int* scores_full, hipStream_t s);

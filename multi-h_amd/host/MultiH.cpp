@@ -24,6 +24,9 @@
 #pragma weak mh_set_estimator
 #pragma weak mh_refine_points
 #pragma weak mh_estimate_fundamental_minimal
+// ... and for the proposal sampler (SetProposalSampler): without its entry points the local sampler fails with a message.
+#pragma weak mh_set_sampler
+#pragma weak mh_build_sample_neighbours
 
 namespace {
 
@@ -403,6 +406,36 @@ bool MultiH::Run(bool points_only)
     }
     if (!Check(mh_set_epipolar(engine, fundamental_matrix, epipole_2), "mh_set_epipolar")) return false;
 
+    // The proposal sampler: its three arguments are checked here, once; then the local sampler's table, once, on the
+    // correspondences the proposer samples (the refined ones).
+    if (proposal_sampler != PROPOSAL_UNIFORM && proposal_sampler != PROPOSAL_LOCAL) {
+        std::cerr << "Error: unknown proposal sampler " << proposal_sampler << " (PROPOSAL_UNIFORM or PROPOSAL_LOCAL)\n";
+        return false;
+    }
+    proposal_local_run = proposal_sampler == PROPOSAL_LOCAL && init_mode != INIT_STABLE_SETS;
+    if (proposal_local_run) {
+        if (proposal_sampler_k < 3 || proposal_sampler_k > 32) {
+            std::cerr << "Error: SetProposalSampler: k = " << proposal_sampler_k << " is outside [3, 32]\n";
+            return false;
+        }
+        if (proposal_uniform_per_16 < 0 || proposal_uniform_per_16 > 16) {
+            std::cerr << "Error: SetProposalSampler: uniform_per_16 = " << proposal_uniform_per_16 << " is outside [0, 16]\n";
+            return false;
+        }
+        if (!mh_set_sampler || !mh_build_sample_neighbours) {
+            std::cerr << "Error: the engine library has no local proposal sampler (mh_set_sampler, mh_build_sample_neighbours)\n";
+            return false;
+        }
+        const int points = static_cast<int>(src_points.size());          // (at least 8 here, so k stays >= 3)
+        int k = proposal_sampler_k;
+        if (k > points - 1) {
+            k = points - 1;
+            printf("[Multi-H] Proposal sampler: k reduced from %d to %d (%d correspondences)\n", proposal_sampler_k, k, points);
+        }
+        if (!Check(mh_build_sample_neighbours(engine, k), "mh_build_sample_neighbours")) return false;
+        stage("sampling table");
+    }
+
     if (!initial_homographies.empty()) {
         for (const cv::Mat& h : initial_homographies) cluster_homographies.push_back(h.clone());
     } else if (init_mode == INIT_STABLE_SETS) {
@@ -590,6 +623,13 @@ bool MultiH::ProposeInitialModels()
     return ok;
 }
 
+// The engine's sampler for the coming batch.  An engine library without the entry point has the uniform sampler only.
+bool MultiH::ApplyProposalSampler(bool local)
+{
+    if (!mh_set_sampler) return !local;
+    return Check(mh_set_sampler(engine, local ? MH_SAMPLER_LOCAL : MH_SAMPLER_UNIFORM, local ? proposal_uniform_per_16 : 0), "mh_set_sampler");
+}
+
 // `mask`: 1 = point still unexplained (in/out).  Appends the selected models to cluster_homographies.
 // One hypothesis batch -> mh_propose_dlt4 (this rank's shard of it) -> mh_select_greedy: scoring, arg-max, claiming
 // the winner's inliers and pruning the candidates all stay on the device; per round the host reads three control
@@ -603,6 +643,7 @@ bool MultiH::ProposeModels(uint64_t seed, long long first, int M, int max_models
     const int W = std::max(shard_world, 1), base = M / W, rem = M % W;
     const int mine = base + (shard_rank < rem ? 1 : 0);
     const long long off = (long long)shard_rank * base + std::min(shard_rank, rem);
+    if (!ApplyProposalSampler(proposal_local_run)) return false;      // (sticky on the engine, and engines are reused)
     if (mine > 0) {
         if (!Check(mh_propose_dlt4(engine, seed, first + off, mine), "mh_propose_dlt4")) return false;
     } else if (!Check(mh_set_models(engine, nullptr, 0), "mh_set_models")) {
@@ -882,6 +923,7 @@ void MultiH::HandleDegenerateCase()
         if (!Check(mh_set_correspondences(engine, s.data(), d.data(), point_only_run ? nullptr : a.data(), N), "mh_set_correspondences")) return;
     }
     const int M = std::max(proposal_hypotheses, 1000);
+    if (!ApplyProposalSampler(false)) return;          // this batch is uniform whatever SetProposalSampler says (the oracle's mho_handle_degenerate defines it)
     if (!Check(mh_propose_dlt4(engine, proposal_seed ^ 0xdeadull, 0, M), "mh_propose_dlt4")) return;
     std::vector<int> counts(M);
     if (!Check(mh_score(engine, sqr_threshold_homography, nullptr, counts.data()), "mh_score")) return;
@@ -948,6 +990,13 @@ void mhh_set_neighbour_hits(const int* rowptr, const int* col, int n)
 static int g_proposal_refit = 1;
 extern "C" __attribute__((visibility("default")))
 void mhh_set_proposal_refit(int on) { g_proposal_refit = on; }
+// MultiH::SetProposalSampler for the next mhh_run_process calls (default: uniform)
+static int g_proposal_sampler = 0, g_proposal_sampler_k = 0, g_proposal_uniform_per_16 = 0;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_proposal_sampler(int mode, int k, int uniform_per_16)
+{
+    g_proposal_sampler = mode; g_proposal_sampler_k = k; g_proposal_uniform_per_16 = uniform_per_16;
+}
 // schedule knobs (mh_set_tuning) for the engines of the next mhh_run_process calls; key < 0 clears the list
 static std::vector<std::pair<int, int>> g_tuning;
 extern "C" __attribute__((visibility("default")))
@@ -1042,6 +1091,7 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     mh.SetDevice(g_device);
     mh.SetCompatibilityCheck(g_post_filter != 0);
     mh.SetProposalRefit(g_proposal_refit != 0);
+    if (g_proposal_sampler != 0) mh.SetProposalSampler(g_proposal_sampler, g_proposal_sampler_k, g_proposal_uniform_per_16);
     if (g_fund_metric >= 0) mh.SetFundamentalMetric(g_fund_metric);
     if (g_fund_estimator >= 0) mh.SetFundamentalEstimator(g_fund_estimator, g_fund_max_samples, g_fund_confidence);
     for (const auto& kv : g_tuning) mh.SetEngineTuning(kv.first, kv.second);

@@ -131,6 +131,16 @@ public:
     // non-minimal fit (M/MultiH.cpp:913-989, the reference's; default) or the 3-point least squares from the points alone.
     enum { ESTIMATOR_HAF = 0, ESTIMATOR_3PT = 1 };
     void SetEstimator(int e) { estimator = e; }
+    // The sampler of the proposal batches (the initial one and the iterative ones): uniform 4-tuples (default), or
+    // neighbourhood-guided ones (mh_set_sampler, MH_SAMPLER_LOCAL): the first index uniform, the other three from its `k`
+    // nearest neighbours in (x1, y1, x2, y2), with `uniform_per_16` hypotheses of every 16 left uniform (a homography from a
+    // small patch extrapolates poorly: DESIGN.md 3.3).  Process() builds the sampler's table once, on the refined
+    // correspondences, after the front half.  The degenerate tail's batch stays uniform; INIT_STABLE_SETS ignores the setting.
+    enum { PROPOSAL_UNIFORM = 0, PROPOSAL_LOCAL = 1 };
+    void SetProposalSampler(int sampler, int k = 32, int uniform_per_16 = 4)
+    {
+        proposal_sampler = sampler; proposal_sampler_k = k; proposal_uniform_per_16 = uniform_per_16;
+    }
     // Multi-GPU propose stage (BASELINE configs[3] and [4]): one process per GPU, every rank holds all
     // correspondences and owns a contiguous shard of each hypothesis batch (the hypotheses are a pure function of
     // (seed, counter), so the union over ranks is the single-GPU batch).  In the first greedy round the ranks all-gather
@@ -220,6 +230,9 @@ protected:
     int proposal_max_models = 32;
     bool proposal_refit = true;
     int estimator = ESTIMATOR_HAF;
+    int proposal_sampler = PROPOSAL_UNIFORM, proposal_sampler_k = 32, proposal_uniform_per_16 = 4;
+    bool proposal_local_run = false;      // this Process() call proposes with the local sampler (its table is on the engine)
+    bool ApplyProposalSampler(bool local);
     bool point_only_run = false;                 // the last Process() was the point-only one
     int fixed_iterations = 0;
     int iter_hypotheses = 0, iter_max_new = 4;

@@ -23,6 +23,9 @@
 //                                row (x1 y1 x2 y2 label); runs MultiH::Process(src, dst), the point-only route (3-point refits)
 //                  [--estimator haf|3pt]   the re-estimator of the route with affinities (MultiH::SetEstimator; haf, the default,
 //                                is the reference's); --points always takes 3pt
+//                  [--sampler uniform|local[:k[:u]]]   the sampler of the proposal batches (MultiH::SetProposalSampler): uniform
+//                                4-tuples (default) or neighbourhood-guided ones from the k nearest neighbours (32) with u of
+//                                every 16 hypotheses left uniform (4)
 //                  [--ranks N]   one process per GPU (rank r on device r), the hypothesis batches sharded over the ranks and
 //                                exchanged by RCCL (host/rccl_transport.cpp: ncclAllGather on the engine's stream); this
 //                                process becomes rank 0 and starts the others before anything touches the GPU.  Every rank
@@ -102,7 +105,7 @@ int main(int argc, char** argv)
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
                      "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] [--f-estimator ls8|minimal] "
-                     "[--stages file] [--points] [--estimator haf|3pt] [--ranks n]\n";
+                     "[--stages file] [--points] [--estimator haf|3pt] [--sampler uniform|local[:k[:u]]] [--ranks n]\n";
         return 2;
     }
     double thrF = 2.6, thrH = 2.2, locality = 0.005, lambda = 0.5;     // M/main.cpp:55-59
@@ -115,6 +118,7 @@ int main(int argc, char** argv)
     std::string epi, neighbourhood = "knn", stages_path;
     bool points_only = false;
     int estimator = MultiH::ESTIMATOR_HAF;
+    int sampler = MultiH::PROPOSAL_UNIFORM, sampler_k = 32, sampler_u = 4;
     for (int i = 3; i < argc; ++i) {
         const std::string k = argv[i];
         if (k == "--points") { points_only = true; continue; }      // the one option without a value
@@ -125,6 +129,28 @@ int main(int argc, char** argv)
             if (std::string(v) == "haf") estimator = MultiH::ESTIMATOR_HAF;
             else if (std::string(v) == "3pt") estimator = MultiH::ESTIMATOR_3PT;
             else { std::cerr << "--estimator: haf or 3pt\n"; return 2; }
+        }
+        else if (k == "--sampler") {
+            // uniform | local | local:k | local:k:u — whole numbers, nothing behind them
+            const std::string sv = v;
+            auto whole = [](const std::string& t, int lo, int hi, int& out) {
+                if (t.empty() || t.size() > 3 || t.find_first_not_of("0123456789") != std::string::npos) return false;
+                out = atoi(t.c_str());
+                return out >= lo && out <= hi;
+            };
+            bool good = true;
+            int kk = 32, uu = 4;
+            if (sv == "uniform") sampler = MultiH::PROPOSAL_UNIFORM;
+            else if (sv.compare(0, 5, "local") == 0 && (sv.size() == 5 || sv[5] == ':')) {
+                if (sv.size() > 5) {
+                    const std::string rest = sv.substr(6);
+                    const size_t colon = rest.find(':');
+                    good = whole(rest.substr(0, colon), 3, 32, kk) && (colon == std::string::npos || whole(rest.substr(colon + 1), 0, 16, uu));
+                }
+                if (good) { sampler = MultiH::PROPOSAL_LOCAL; sampler_k = kk; sampler_u = uu; }
+            }
+            else good = false;
+            if (!good) { std::cerr << "--sampler " << sv << ": uniform, local, local:k or local:k:u with whole numbers 3 <= k <= 32, 0 <= u <= 16\n"; return 2; }
         }
         else if (k == "--thrF") thrF = atof(v);
         else if (k == "--thrH") thrH = atof(v);
@@ -271,6 +297,7 @@ int main(int argc, char** argv)
     if (neighbourhood == "radius") multiH->SetNeighbourRadius(1.0 / locality);        // the complete list of M/MultiH.cpp:252-253 (see MultiH.h)
     else if (neighbourhood == "approx") multiH->SetNeighbourApprox(4, 32, 0x464c414e4eull + seed);   // ... as FLANN's default search answers it
     multiH->SetEstimator(estimator);
+    multiH->SetProposalSampler(sampler, sampler_k, sampler_u);
     const bool processed = points_only ? multiH->Process(srcPointsOrig, dstPointsOrig)
                                        : multiH->Process(srcPointsOrig, dstPointsOrig, origAffines);
     if (!processed) { delete multiH; return finish(1); }
