@@ -237,8 +237,8 @@ MH_API int mh_score(mh_engine* e, double thr2, const unsigned char* point_mask, 
  * written to HBM by one kernel that also produces the inlier counts.  R_host (nullable)
  * receives a host copy — leave NULL to keep the matrix on the device only. */
 MH_API int mh_residual_matrix(mh_engine* e, double thr2, double* R_host, int* counts);
-/* The s = 4 variant of the matrix: the int32 PEARL data cost (dataEnergy, M/MultiH.cpp:473-504, label =
- * model + 1) of every current model against every point, model-major C[m*n + i], written to HBM by one kernel that also
+/* The s = 4 variant of the matrix: the int32 PEARL data cost (dataEnergy, M/MultiH.cpp:473-504, or the engine's
+ * other data term: mh_set_data_term; label = model + 1) of every current model against every point, model-major C[m*n + i], written to HBM by one kernel that also
  * produces the inlier counts (strict d2 < thr_hom^2).  Uses the engine's lambda and thr_hom (mh_set_params).  C_host
  * (nullable) receives a host copy. */
 MH_API int mh_cost_matrix(mh_engine* e, int* C_host, int* counts);
@@ -338,8 +338,26 @@ MH_API int mh_get_copy_stats(mh_engine* e, long long* h2d, long long* d2h, int r
 MH_API int mh_inlier_moments(mh_engine* e, double thr2, double* moments /* m x 6 */, double* min_eig /* m */);
 
 /* ---- label --------------------------------------------------------------- */
-/* dataEnergy (M/MultiH.cpp:473-504) for every (site, label): cost[i*(Nh+1)+l], int32, label 0 =
- * outlier, l>=1 = current model l-1.  cost (nullable) receives a host copy. */
+/* The data term of mh_data_cost, mh_cost_matrix and mh_labeling_step.  With lam = 100 / lambda and T = thr_hom^2 * 81 / 16
+ * (both computed in double, in that order of operations), B = (int)round(lam * T), and d2 the forward transfer error of the
+ * pair in the reference's operation order (M/MultiH.cpp:434-441: s = h6 x + h7 y + h8; u = (h0 x + h1 y + h2) / s;
+ * v = (h3 x + h4 y + h5) / s; d2 = (x2 - u)^2 + (y2 - v)^2, every operation rounded once), the int32 cost of (point, label) is
+ *                               MH_DATA_TERM_REFERENCE (default)             MH_DATA_TERM_RISING
+ *   label 0 (outlier)           B                                            B
+ *   d2 < T (strictly)           (int)round(lam * (1.0 - (d2 / T)))           (int)round(lam * (d2 / T))
+ *   otherwise (d2 >= T, NaN)    2 * B                                        2 * B
+ * d2 / T is one IEEE double division, lam * (...) one rounded double multiplication (no fused multiply-add anywhere), round
+ * is C round(): halves away from zero.  REFERENCE is dataEnergy (M/MultiH.cpp:473-504): 100 / lambda at a perfect fit falling
+ * to 0 at the threshold.  RISING is the same expression without the `1.0 -`: 0 at a perfect fit rising to round(lam) just
+ * below the threshold; the outlier cost, the truncation, the scales and the Potts term are the same.
+ * Sticky per engine; mh_set_correspondences does not reset it.  Setting it (to any value) marks the data cost stale, as
+ * mh_set_params does: mh_expand answers MH_ERR_NOT_SET until mh_data_cost has run.  The inlier counts fused into
+ * mh_cost_matrix do not depend on it, and mh_select_greedy never reads it.  Another value, or a null engine: MH_ERR_INVALID. */
+#define MH_DATA_TERM_REFERENCE 0
+#define MH_DATA_TERM_RISING 1
+MH_API int mh_set_data_term(mh_engine* e, int term);
+/* The engine's data term (dataEnergy, M/MultiH.cpp:473-504, by default) for every (site, label): cost[i*(Nh+1)+l], int32,
+ * label 0 = outlier, l>=1 = current model l-1.  cost (nullable) receives a host copy. */
 MH_API int mh_data_cost(mh_engine* e, int* cost);
 /* alpha-expansion over the current data cost and neighbour graph with the Potts term
  * round(100*lambda) (M/MultiH.cpp:506-511; GCoptimization.cpp:975-1058,1212-1289).

@@ -171,6 +171,7 @@ struct mh_engine {
     int ms_persist_per_cu = -1, ms_persist_per_cu6 = -1;   // workgroups of k_ms_persist<10> / <6> a compute unit holds (-1: not queried; a failed query is not kept)
     int tune_select_refine = 0;              // key 30: mh_select_greedy refits each round's winner to its inliers before the claim (0 = off)
     int estimator = MH_ESTIMATOR_HAF;        // mh_set_estimator: the re-estimator of mh_reestimate, mh_labeling_step and the key-30 refit
+    int data_term = MH_DATA_TERM_REFERENCE;  // mh_set_data_term: the data term of mh_data_cost, mh_cost_matrix and mh_labeling_step (changes results: not a tuning key)
     DevBuf<int> r3_scratch;                  // member lists of the 3-point re-estimator (reestimate3pt.hip)
     int tune_3pt_form = 0;                   // key 34 (measurement libraries): 0 by size, 1 the match loop, 2 the compacted member lists (reestimate3pt.hip)
     DevBuf<double> sel_refit;                // the refit (9 doubles) and its inlier count

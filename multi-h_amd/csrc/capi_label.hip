@@ -72,7 +72,8 @@ int do_data_cost(mh_engine* e)
     HIPCHK(e->cost.reserve((size_t)e->n * L));
     {
         ScopedTimer t(e, MH_K_DATACOST);
-        HIPCHK(launch_data_cost(e->pts(), e->H.p, e->m, e->lambda, e->thr_H * e->thr_H, e->cost.p, e->stream));
+        HIPCHK(launch_data_cost(e->pts(), e->H.p, e->m, e->lambda, e->thr_H * e->thr_H, e->cost.p, e->stream,
+                                e->data_term == MH_DATA_TERM_RISING));
     }
     e->cost_L = L;
     return MH_OK;
@@ -427,6 +428,17 @@ int mh_set_estimator(mh_engine* e, int estimator)
     if (rc) return rc;
     if (estimator != MH_ESTIMATOR_HAF && estimator != MH_ESTIMATOR_3PT) return fail(MH_ERR_INVALID, "unknown estimator");
     e->estimator = estimator;
+    return MH_OK;
+    });
+}
+
+int mh_set_data_term(mh_engine* e, int term)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (term != MH_DATA_TERM_REFERENCE && term != MH_DATA_TERM_RISING) return fail(MH_ERR_INVALID, "unknown data term");
+    e->data_term = term;
+    e->cost_L = 0;                                               // as mh_set_params: the table on the device is another term's
     return MH_OK;
     });
 }

@@ -266,9 +266,11 @@ int mh_cost_matrix(mh_engine* e, int* C_host, int* counts)
                 ctl = e->sweep_ctl.p;
             }
             HIPCHK(launch_cost32(e->pts(), e->H.p, e->H32.p, e->m, e->lambda, thr2, e->absmax_dst, e->C.p, e->ldc, e->counts.p, e->stream,
-                                 ctl, e->cu_count, e->tune_cost32_resident > 0 ? e->tune_cost32_resident : 0, e->tune_cost32_slice_major, e->tune_cost32_batched, &e->occ_cost32));
+                                 ctl, e->cu_count, e->tune_cost32_resident > 0 ? e->tune_cost32_resident : 0, e->tune_cost32_slice_major, e->tune_cost32_batched, &e->occ_cost32,
+                                 e->data_term == MH_DATA_TERM_RISING));
         } else
-            HIPCHK(launch_cost_matrix(e->pts(), e->H.p, e->m, e->lambda, thr2, e->C.p, e->ldc, e->counts.p, e->stream));
+            HIPCHK(launch_cost_matrix(e->pts(), e->H.p, e->m, e->lambda, thr2, e->C.p, e->ldc, e->counts.p, e->stream,
+                                      e->data_term == MH_DATA_TERM_RISING));
     }
     e->counts_zeroed = false;
     e->counts_fresh = true;

@@ -7,6 +7,8 @@
 //     label 0 (outlier)         -> round(lam*T)
 //     d2 < T                    -> round(lam*(1 - d2/T))     (quirk A-4: decreasing in d2)
 //     otherwise                 -> 2*round(lam*T)
+// RISING (mh_set_data_term(MH_DATA_TERM_RISING)): the middle row without its `1.0 -`, round(lam*(d2/T)) — the cost grows
+// with the error; the other two rows, the scales and the truncation are the same (data_term, mh_device.hpp).
 // cost is int32, site-major: cost[i*(Nh+1) + l]  (the layout GCO's dense
 // data-cost array uses, GCoptimization.h setDataCost(EnergyTermType*)).
 // One thread per (site, label) element; consecutive threads write consecutive
@@ -17,6 +19,7 @@
 
 namespace mh {
 
+template <bool RISING>
 __global__ void __launch_bounds__(256)
 k_data_cost(const double* __restrict__ x1, const double* __restrict__ y1,
             const double* __restrict__ x2, const double* __restrict__ y2, int N,
@@ -33,8 +36,8 @@ k_data_cost(const double* __restrict__ x1, const double* __restrict__ y1,
         const double* h = H + 9 * (size_t)(l - 1);
         const double d2 = fwd_d2(h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], x1[i],
                                  y1[i], x2[i], y2[i]);
-        if (d2 < T) c = (int)round(lam * (1.0 - (d2 / T)));
-        else c = 2 * (int)round(lam * T);
+        if (d2 < T) c = (int)round(lam * (RISING ? (d2 / T) : (1.0 - (d2 / T))));     // (data_term of mh_device.hpp, in the order the
+        else c = 2 * (int)round(lam * T);                                            // reference form has always been compiled from)
     }
     cost[e] = c;
 }
@@ -51,7 +54,7 @@ k_data_cost(const double* __restrict__ x1, const double* __restrict__ y1,
 // (mh_cost_matrix runs k_cost32 of score32.hip instead — the same matrix behind an FP32 pre-test — wherever that kernel's
 // preconditions hold; this one remains for the other inputs and as its A/B partner, mh_set_tuning key 15.)
 // ---------------------------------------------------------------------------
-template <int MC>
+template <int MC, bool RISING>
 __global__ void __launch_bounds__(256)
 k_cost_matrix(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
               const double* __restrict__ y2, int N, const double* __restrict__ H, int M, double lam, double T, double thr2,
@@ -94,7 +97,7 @@ k_cost_matrix(const double* __restrict__ x1, const double* __restrict__ y1, cons
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const double d2 = fwd_d2_fast<true>(h0, h1, h2, h3, h4, h5, h6, h7, h8, px[q], py[q], qx[q], qy[q], pok[q] && hok);
-                c[q] = d2 < T ? (int)round(lam * (1.0 - (d2 / T))) : beyond;
+                c[q] = data_term<RISING>(d2, T, lam, beyond);
                 inl += __builtin_popcountll(__builtin_amdgcn_ballot_w64(ok[q] && d2 < thr2));
             }
             int* dst = C + (size_t)m * ldc + n;
@@ -112,7 +115,7 @@ k_cost_matrix(const double* __restrict__ x1, const double* __restrict__ y1, cons
 }
 
 hipError_t launch_cost_matrix(const Points& p, const double* H, int M, double lambda, double thr2, int* C, long long ldc,
-                              int* counts, hipStream_t s)
+                              int* counts, hipStream_t s, int rising)
 {
     if (M <= 0 || p.n <= 0) return hipSuccess;
     constexpr int MC = 16;
@@ -124,21 +127,26 @@ hipError_t launch_cost_matrix(const Points& p, const double* H, int M, double la
         hipError_t e = hipMemsetAsync(counts, 0, sizeof(int) * (size_t)M, s);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_cost_matrix<MC>, dim3(gx, psplit), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, M, 100.0 / lambda,
-                       thr2 * 81.0 / 16.0, thr2, C, ldc, counts, psplit);
+    if (rising)
+        hipLaunchKernelGGL((k_cost_matrix<MC, true>), dim3(gx, psplit), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, M, 100.0 / lambda,
+                           thr2 * 81.0 / 16.0, thr2, C, ldc, counts, psplit);
+    else
+        hipLaunchKernelGGL((k_cost_matrix<MC, false>), dim3(gx, psplit), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, M, 100.0 / lambda,
+                           thr2 * 81.0 / 16.0, thr2, C, ldc, counts, psplit);
     return hipGetLastError();
 }
 
 hipError_t launch_data_cost(const Points& p, const double* H, int Nh, double lambda, double thr2,
-                            int* cost, hipStream_t s)
+                            int* cost, hipStream_t s, int rising)
 {
     const int L = Nh + 1;
     const double lam = 100.0 / lambda;        // one_per_energy_lambda, M/MultiH.h:42
     const double T = thr2 * 81.0 / 16.0;      // truncated_sqr_threshold, M/MultiH.h:44
     const long long total = (long long)p.n * L;
     if (total <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_data_cost, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p.x1,
-                       p.y1, p.x2, p.y2, p.n, H, L, lam, T, cost);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (rising) hipLaunchKernelGGL(k_data_cost<true>, grid, dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, L, lam, T, cost);
+    else hipLaunchKernelGGL(k_data_cost<false>, grid, dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, L, lam, T, cost);
     return hipGetLastError();
 }
 

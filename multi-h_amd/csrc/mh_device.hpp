@@ -19,6 +19,16 @@ __device__ __forceinline__ double fwd_d2(double h0, double h1, double h2, double
     return dx * dx + dy * dy;
 }
 
+// The data term of one (point, model) pair from its forward error d2 (include/multih_hip.h, mh_set_data_term): one IEEE
+// division, one rounded multiplication, C round(); a NaN d2 fails `d2 < T` and takes `beyond`.  RISING = false is
+// dataEnergy (M/MultiH.cpp:496-503); RISING = true drops its `1.0 -` and nothing else.
+template <bool RISING>
+__device__ __forceinline__ int data_term(double d2, double T, double lam, int beyond)
+{
+    if (RISING) return d2 < T ? (int)round(lam * (d2 / T)) : beyond;
+    return d2 < T ? (int)round(lam * (1.0 - (d2 / T))) : beyond;
+}
+
 // ---------------------------------------------------------------------------
 // Shared-reciprocal division for the residual sweep.
 //

@@ -60,7 +60,7 @@ hipError_t launch_score32(const Points& p, const double* H, const float* H32, in
 // the materialised int32 cost matrix (launch_cost_matrix, datacost.hip) through the same pre-test; H32 made with the same Cmax
 hipError_t launch_cost32(const Points& p, const double* H, const float* H32, int M, double lambda, double thr2, double Cmax,
                          int* C, long long ldc, int* counts, hipStream_t s, int* resident_ctl = nullptr, int cu_count = 256,
-                         int psplit_override = 0, int slice_major = 0, int batched = 0, int* occ_cache = nullptr);
+                         int psplit_override = 0, int slice_major = 0, int batched = 0, int* occ_cache = nullptr, int rising = 0);
 // occ_cache (both launchers): the caller's per-engine cache of the resident kernel's workgroups per compute unit (-1 = not asked yet)
 hipError_t launch_inliers_of_model(const Points& p, const double* H, int idx, double thr2,
                                    int label_value, int* labels, hipStream_t s);
@@ -108,10 +108,11 @@ hipError_t launch_fund_refit(const Points& p, const double* F_in, double thr2, d
 // --- datacost.hip -----------------------------------------------------------
 // the data cost of every model against every point, int32, model-major with pitch ldc (datacost.hip)
 inline long long cost_ld(int n) { return ((long long)n + 31) & ~31ll; }
+// rising (here and in launch_cost32): 0 the reference's data term, 1 MH_DATA_TERM_RISING (include/multih_hip.h)
 hipError_t launch_cost_matrix(const Points& p, const double* H, int M, double lambda, double thr2, int* C, long long ldc,
-                              int* counts, hipStream_t s);
+                              int* counts, hipStream_t s, int rising = 0);
 hipError_t launch_data_cost(const Points& p, const double* H, int Nh, double lambda, double thr2,
-                            int* cost, hipStream_t s);
+                            int* cost, hipStream_t s, int rising = 0);
 
 // --- reestimate.hip ---------------------------------------------------------
 hipError_t launch_reestimate(const Points& p, const Affines& a, const int* labels, int Nh,

@@ -274,7 +274,7 @@ __device__ __forceinline__ void wave_lds_handover()
 }
 
 // cost32_wg: the work of ONE workgroup — model block bx (MC models), point slice by.
-template <int MC, int WAVES>
+template <int MC, int WAVES, bool RISING>
 __device__ __forceinline__ void
 cost32_wg(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
           const double* __restrict__ y2, int N, const double* __restrict__ H, const float* __restrict__ H32, int M,
@@ -365,7 +365,7 @@ cost32_wg(const double* __restrict__ x1, const double* __restrict__ y1, const do
                         const int id = my_list[p0 + lane], q2 = id >> 6, l2 = id & 63;
                         const double* pp = wave_p + (q2 * 4) * 64 + l2;
                         const double d2 = fwd_d2(h0d, h1d, h2d, h3d, h4d, h5d, h6d, h7d, h8d, pp[0], pp[64], pp[128], pp[192]);
-                        my_c[id] = d2 < T ? (int)round(lam * (1.0 - (d2 / T))) : beyond;
+                        my_c[id] = data_term<RISING>(d2, T, lam, beyond);
                         in64 = (base_n + l2 * PPL + q2 < N) && d2 < thr2;
                     }
                     c_m += __builtin_popcountll(__builtin_amdgcn_ballot_w64(in64));
@@ -418,7 +418,7 @@ cost32_wg(const double* __restrict__ x1, const double* __restrict__ y1, const do
 // the end of a tile): full lanes, one eighth of the passes.  The cost of a near pair then goes straight to C[m][n], over
 // the constant written before: the wave drains its stores (s_waitcnt vmcnt(0)) before the first such store of a batch, so
 // the two writes of an address arrive in order.  Inlier counts go through an LDS counter per (wave, model).
-template <int MC, int WAVES>
+template <int MC, int WAVES, bool RISING>
 __device__ __forceinline__ void
 cost32_wg_batched(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
                   const double* __restrict__ y2, int N, const double* __restrict__ H, const float* __restrict__ H32, int M,
@@ -473,7 +473,7 @@ cost32_wg_batched(const double* __restrict__ x1, const double* __restrict__ y1, 
                 const double* h = s_h + 9 * mi2;
                 const double* pp = wave_p + (q2 * 4) * 64 + l2;
                 const double d2 = fwd_d2(h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], pp[0], pp[64], pp[128], pp[192]);
-                const int cost = d2 < T ? (int)round(lam * (1.0 - (d2 / T))) : beyond;
+                const int cost = data_term<RISING>(d2, T, lam, beyond);
                 const int n = base_n + l2 * PPL + q2;
                 if (n < N) {
                     C[(size_t)(m0 + mi2) * ldc + n] = cost;
@@ -544,23 +544,25 @@ cost32_wg_batched(const double* __restrict__ x1, const double* __restrict__ y1, 
     }
 }
 
-template <int MC, int WAVES, bool BATCH>
-__global__ void __launch_bounds__(64 * WAVES)
-k_cost32(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
-         const double* __restrict__ y2, int N, const double* __restrict__ H, const float* __restrict__ H32, int M,
-         double lam, double T, double thr2, float k1, int* __restrict__ C, long long ldc, int* __restrict__ counts, int psplit)
+// The data term (mh_set_data_term) is a template argument of the workgroup functions above, not of k_cost32 / k_cost32_resident:
+// the product's two kernels keep their names and their code, and the rising term runs in kernels of its own name below.
+template <int MC, int WAVES, bool BATCH, bool RISING>
+__device__ __forceinline__ void
+cost32_grid(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
+            const double* __restrict__ y2, int N, const double* __restrict__ H, const float* __restrict__ H32, int M,
+            double lam, double T, double thr2, float k1, int* __restrict__ C, long long ldc, int* __restrict__ counts, int psplit)
 {
-    if (BATCH) cost32_wg_batched<MC, WAVES>(x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit, blockIdx.x, blockIdx.y);
-    else cost32_wg<MC, WAVES>(x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit, blockIdx.x, blockIdx.y);
+    if (BATCH) cost32_wg_batched<MC, WAVES, RISING>(x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit, blockIdx.x, blockIdx.y);
+    else cost32_wg<MC, WAVES, RISING>(x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit, blockIdx.x, blockIdx.y);
 }
 
 // The same work items walked by a resident grid that hands them out through a counter (as k_residual_resident, residual.hip).
-template <int MC, int WAVES, bool BATCH>
-__global__ void __launch_bounds__(64 * WAVES)
-k_cost32_resident(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
-                  const double* __restrict__ y2, int N, const double* __restrict__ H, const float* __restrict__ H32, int M,
-                  double lam, double T, double thr2, float k1, int* __restrict__ C, long long ldc, int* __restrict__ counts, int psplit,
-                  int gx, int nitems, int* __restrict__ ctl, int slice_major)
+template <int MC, int WAVES, bool BATCH, bool RISING>
+__device__ __forceinline__ void
+cost32_resident_grid(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
+                     const double* __restrict__ y2, int N, const double* __restrict__ H, const float* __restrict__ H32, int M,
+                     double lam, double T, double thr2, float k1, int* __restrict__ C, long long ldc, int* __restrict__ counts, int psplit,
+                     int gx, int nitems, int* __restrict__ ctl, int slice_major)
 {
     __shared__ int s_item;
 #pragma unroll 1
@@ -574,8 +576,8 @@ k_cost32_resident(const double* __restrict__ x1, const double* __restrict__ y1, 
         int bx, by;
         if (slice_major) { bx = item / psplit; by = item - bx * psplit; }
         else { by = item / gx; bx = item - by * gx; }
-        if (BATCH) cost32_wg_batched<MC, WAVES>(x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit, bx, by);
-        else cost32_wg<MC, WAVES>(x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit, bx, by);
+        if (BATCH) cost32_wg_batched<MC, WAVES, RISING>(x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit, bx, by);
+        else cost32_wg<MC, WAVES, RISING>(x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit, bx, by);
         __syncthreads();
     }
     if (threadIdx.x == 0 && atomicAdd(&ctl[1], 1) == (int)gridDim.x - 1) {
@@ -584,8 +586,45 @@ k_cost32_resident(const double* __restrict__ x1, const double* __restrict__ y1, 
     }
 }
 
+#define MH_COST32_ARGS                                                                                                          \
+    const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2, const double* __restrict__ y2, \
+    int N, const double* __restrict__ H, const float* __restrict__ H32, int M, double lam, double T, double thr2, float k1,     \
+    int* __restrict__ C, long long ldc, int* __restrict__ counts, int psplit
+#define MH_COST32_PASS x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit
+
+template <int MC, int WAVES, bool BATCH>
+__global__ void __launch_bounds__(64 * WAVES)
+k_cost32(MH_COST32_ARGS)
+{
+    cost32_grid<MC, WAVES, BATCH, false>(MH_COST32_PASS);
+}
+
+template <int MC, int WAVES, bool BATCH>
+__global__ void __launch_bounds__(64 * WAVES)
+k_cost32_resident(MH_COST32_ARGS, int gx, int nitems, int* __restrict__ ctl, int slice_major)
+{
+    cost32_resident_grid<MC, WAVES, BATCH, false>(MH_COST32_PASS, gx, nitems, ctl, slice_major);
+}
+
+// MH_DATA_TERM_RISING: the same pre-test, lists and stores around round(lam * (d2 / T)) for the near pairs.
+template <int MC, int WAVES, bool BATCH>
+__global__ void __launch_bounds__(64 * WAVES)
+k_rising32(MH_COST32_ARGS)
+{
+    cost32_grid<MC, WAVES, BATCH, true>(MH_COST32_PASS);
+}
+
+template <int MC, int WAVES, bool BATCH>
+__global__ void __launch_bounds__(64 * WAVES)
+k_rising32_resident(MH_COST32_ARGS, int gx, int nitems, int* __restrict__ ctl, int slice_major)
+{
+    cost32_resident_grid<MC, WAVES, BATCH, true>(MH_COST32_PASS, gx, nitems, ctl, slice_major);
+}
+#undef MH_COST32_ARGS
+#undef MH_COST32_PASS
+
 // H32: the table launch_model32 made for these models with the same Cmax.  thr2 in [2^-40, 2^40], coordinates below 2^20.
-template <bool BATCH>
+template <bool BATCH, bool RISING>
 static hipError_t launch_cost32_t(const Points& p, const double* H, const float* H32, int M, double lambda, double thr2, double Cmax,
                                   int* C, long long ldc, int* counts, hipStream_t s, int* resident_ctl, int cu_count, int psplit_override, int slice_major,
                                   int* occ_cache)
@@ -605,6 +644,8 @@ static hipError_t launch_cost32_t(const Points& p, const double* H, const float*
     }
     // far = beyond T = (9/4 thr)^2 with a 2 % margin: the cheap test's k1 with 1.12 x 9/4 thr in place of 2.5 thr
     const float k1 = (float)(std::fmax(1.12 * 2.25 * std::sqrt(std::fabs(thr2)), 25.4 * 5.9604644775390625e-08 * Cmax) * (1.0 + 1e-6)) + 1e-30f;
+    const auto k_plain = RISING ? k_rising32<MC, WAVES, BATCH> : k_cost32<MC, WAVES, BATCH>;
+    const auto k_resident = RISING ? k_rising32_resident<MC, WAVES, BATCH> : k_cost32_resident<MC, WAVES, BATCH>;
     if (resident_ctl) {
         // resident grid: as many workgroups as the chip holds, ~37 500 items (r04 experiment: mh_set_tuning key 23)
         // workgroups a compute unit holds: asked once per ENGINE (the caller's cache; a function-local static would be shared
@@ -612,7 +653,7 @@ static hipError_t launch_cost32_t(const Points& p, const double* H, const float*
         int per_cu = occ_cache ? *occ_cache : -1;
         if (per_cu < 0) {
             int q = 0;
-            per_cu = hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, (const void*)k_cost32_resident<MC, WAVES, BATCH>, 64 * WAVES, 0) == hipSuccess ? q : 0;
+            per_cu = hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, (const void*)k_resident, 64 * WAVES, 0) == hipSuccess ? q : 0;
             if (per_cu > 0 && occ_cache) *occ_cache = per_cu;
         }
         const int grid = per_cu * cu_count;
@@ -622,31 +663,35 @@ static hipError_t launch_cost32_t(const Points& p, const double* H, const float*
         if (grid > 0 && gx * ps > grid) {
             hipError_t e = hipMemsetAsync(counts, 0, sizeof(int) * (size_t)M, s);
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_cost32_resident<MC, WAVES, BATCH>), dim3(grid), dim3(64 * WAVES), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, H32, M,
+            hipLaunchKernelGGL(k_resident, dim3(grid), dim3(64 * WAVES), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, H32, M,
                                100.0 / lambda, thr2 * 81.0 / 16.0, thr2, k1, C, ldc, counts, ps, gx, gx * ps, resident_ctl, slice_major);
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL((k_cost32<MC, WAVES, BATCH>), dim3(gx, psplit), dim3(64 * WAVES), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, H32, M, 100.0 / lambda,
+    hipLaunchKernelGGL(k_plain, dim3(gx, psplit), dim3(64 * WAVES), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, H32, M, 100.0 / lambda,
                        thr2 * 81.0 / 16.0, thr2, k1, C, ldc, counts, psplit);
     return hipGetLastError();
 }
 
 hipError_t launch_cost32(const Points& p, const double* H, const float* H32, int M, double lambda, double thr2, double Cmax,
                          int* C, long long ldc, int* counts, hipStream_t s, int* resident_ctl, int cu_count, int psplit_override, int slice_major,
-                         int batched, int* occ_cache)
+                         int batched, int* occ_cache, int rising)
 {
     // batched: the experiment above (mh_set_tuning key 28) instead of the default form, in which every wave x model iteration
     // with a near pair runs the IEEE formula at once and hands the costs to the owning lanes through LDS
 #ifdef MH_TUNING
     // (a measured-and-rejected variant: compiled into measurement libraries only, mh_set_tuning key 28; so are the
     // slice-major item order, key 27, and the other tilings of the score kernel below, key 16)
-    if (batched) return launch_cost32_t<true>(p, H, H32, M, lambda, thr2, Cmax, C, ldc, counts, s, resident_ctl, cu_count, psplit_override, slice_major, nullptr);
+    if (batched && rising) return launch_cost32_t<true, true>(p, H, H32, M, lambda, thr2, Cmax, C, ldc, counts, s, resident_ctl, cu_count, psplit_override, slice_major, nullptr);
+    if (batched) return launch_cost32_t<true, false>(p, H, H32, M, lambda, thr2, Cmax, C, ldc, counts, s, resident_ctl, cu_count, psplit_override, slice_major, nullptr);
 #else
     (void)batched;
     slice_major = 0;
 #endif
-    return launch_cost32_t<false>(p, H, H32, M, lambda, thr2, Cmax, C, ldc, counts, s, resident_ctl, cu_count, psplit_override, slice_major, occ_cache);
+    // (the rising kernels differ from the default ones in a handful of FP64 instructions and hold the same registers and LDS —
+    // DESIGN 3.7 — so the engine's cached occupancy answer serves both)
+    if (rising) return launch_cost32_t<false, true>(p, H, H32, M, lambda, thr2, Cmax, C, ldc, counts, s, resident_ctl, cu_count, psplit_override, slice_major, occ_cache);
+    return launch_cost32_t<false, false>(p, H, H32, M, lambda, thr2, Cmax, C, ldc, counts, s, resident_ctl, cu_count, psplit_override, slice_major, occ_cache);
 }
 
 hipError_t launch_model32(const double* H, int M, double X, double Y, double Cmax, float* H32, hipStream_t s)

@@ -27,6 +27,8 @@
 // ... and for the proposal sampler (SetProposalSampler): without its entry points the local sampler fails with a message.
 #pragma weak mh_set_sampler
 #pragma weak mh_build_sample_neighbours
+// ... and for the data term (SetDataTerm): without its entry point the rising term fails with a message.
+#pragma weak mh_set_data_term
 
 namespace {
 
@@ -284,6 +286,15 @@ bool MultiH::Run(bool points_only)
             return false;
         }
     } else if (!Check(mh_set_estimator(engine, est), "mh_set_estimator")) {
+        return false;
+    }
+    // the data term of the labeling (sticky on the engine, and engines are reused)
+    if (!mh_set_data_term) {
+        if (data_term != DATA_TERM_REFERENCE) {
+            std::cerr << "Error: the engine library has no selectable data term (mh_set_data_term)\n";
+            return false;
+        }
+    } else if (!Check(mh_set_data_term(engine, data_term), "mh_set_data_term")) {
         return false;
     }
     stage("engine");
@@ -1019,6 +1030,10 @@ void mhh_set_fundamental_estimator(int mode, int max_samples, double confidence)
 {
     g_fund_estimator = mode; g_fund_max_samples = max_samples; g_fund_confidence = confidence;
 }
+// MultiH::SetDataTerm for the next mhh_run_process calls (< 0: the class default)
+static int g_data_term = -1;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_data_term(int term) { g_data_term = term; }
 extern "C" __attribute__((visibility("default")))
 void mhh_get_front_stages(int out[4]) { for (int i = 0; i < 4; ++i) out[i] = g_front_stages[i]; }
 // multih::FilterCorrespondencesByEpipolarGeometry on plain arrays: mask (n flags) out; returns the number kept, -1 on failure
@@ -1093,6 +1108,7 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     mh.SetProposalRefit(g_proposal_refit != 0);
     if (g_proposal_sampler != 0) mh.SetProposalSampler(g_proposal_sampler, g_proposal_sampler_k, g_proposal_uniform_per_16);
     if (g_fund_metric >= 0) mh.SetFundamentalMetric(g_fund_metric);
+    if (g_data_term >= 0) mh.SetDataTerm(g_data_term);
     if (g_fund_estimator >= 0) mh.SetFundamentalEstimator(g_fund_estimator, g_fund_max_samples, g_fund_confidence);
     for (const auto& kv : g_tuning) mh.SetEngineTuning(kv.first, kv.second);
     if (g_radius > 0.0 && g_max_hits > 0) { mh.SetNeighbourRadius(g_radius, g_max_hits); if (g_knn > 0) mh.SetFallbackK(g_knn); }

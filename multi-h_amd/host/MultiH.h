@@ -131,6 +131,13 @@ public:
     // non-minimal fit (M/MultiH.cpp:913-989, the reference's; default) or the 3-point least squares from the points alone.
     enum { ESTIMATOR_HAF = 0, ESTIMATOR_3PT = 1 };
     void SetEstimator(int e) { estimator = e; }
+    // The data term of the labeling (mh_set_data_term, include/multih_hip.h): DATA_TERM_REFERENCE is dataEnergy
+    // (M/MultiH.cpp:473-504), whose cost inside the truncation threshold FALLS as the fit gets worse (default);
+    // DATA_TERM_RISING drops its `1.0 -`, so the cost rises with the error.  Process() applies it to its engine on every
+    // call, on both initialisation routes and the point-only route; nothing on the host evaluates the data term itself
+    // (the loop's energy is the engine's).  Any other value makes Process() fail with a message.
+    enum { DATA_TERM_REFERENCE = 0, DATA_TERM_RISING = 1 };
+    void SetDataTerm(int t) { data_term = t; }
     // The sampler of the proposal batches (the initial one and the iterative ones): uniform 4-tuples (default), or
     // neighbourhood-guided ones (mh_set_sampler, MH_SAMPLER_LOCAL): the first index uniform, the other three from its `k`
     // nearest neighbours in (x1, y1, x2, y2), with `uniform_per_16` hypotheses of every 16 left uniform (a homography from a
@@ -230,6 +237,7 @@ protected:
     int proposal_max_models = 32;
     bool proposal_refit = true;
     int estimator = ESTIMATOR_HAF;
+    int data_term = DATA_TERM_REFERENCE;
     int proposal_sampler = PROPOSAL_UNIFORM, proposal_sampler_k = 32, proposal_uniform_per_16 = 4;
     bool proposal_local_run = false;      // this Process() call proposes with the local sampler (its table is on the engine)
     bool ApplyProposalSampler(bool local);
