@@ -193,6 +193,8 @@ MH_API int mh_propose_dlt4(mh_engine* e, unsigned long long seed, long long firs
 MH_API int mh_set_models(mh_engine* e, const double* H, int m);
 MH_API int mh_get_models(mh_engine* e, double* H /* m x 9 */);
 MH_API int mh_get_model_count(mh_engine* e, int* m);
+/* One model of the current set (9 doubles): what a caller who wants a single winner copies instead of all m. */
+MH_API int mh_get_model(mh_engine* e, int idx, double H[9]);
 MH_API int mh_get_samples(mh_engine* e, int* idx /* m x 4, valid after mh_propose_dlt4 */);
 /* The sampler of mh_propose_dlt4 and mh_prefetch_dlt4.  Sticky per engine; mh_set_correspondences does not reset it.
  *   MH_SAMPLER_UNIFORM  every index uniform over all correspondences (default; uniform_per_16 is ignored).
@@ -233,6 +235,27 @@ MH_API int mh_set_residual_mode(mh_engine* e, int mode);
  * points with mask != 0.  counts (m ints, nullable) receives a host copy; the counts also
  * stay resident (mh_device_buffer MH_BUF_COUNTS). */
 MH_API int mh_score(mh_engine* e, double thr2, const unsigned char* point_mask, int* counts);
+/* MSAC-weighted scores: per model the inlier count of mh_score AND a weight that says how well the inliers fit.  With d2 the
+ * forward transfer error of the pair in the reference's operation order (M/MultiH.cpp:434-441, as under mh_set_data_term):
+ *   d2 < thr2 (strictly; mh_score's decision)   the pair counts 1 and weighs (int)round(256.0 * (1.0 - (d2 / thr2)))
+ *   otherwise (d2 >= thr2, inf, NaN)            the pair counts 0 and weighs 0
+ * d2 / thr2 is one IEEE double division, 256.0 * (...) one rounded double multiplication (no fused multiply-add), round is C
+ * round(): halves away from zero.  count[m] and weight[m] are the int32 sums over the points with mask != 0 (all points
+ * without a mask): exact, independent of the order of summation, weight <= MH_MSAC_SCALE * count; an inlier just under the
+ * threshold counts 1 and weighs 0.  Forward residual only: MH_ERR_INVALID under MH_RESIDUAL_SYMMETRIC.  MH_ERR_OVERFLOW,
+ * before anything is launched, when n * MH_MSAC_SCALE exceeds 2^31 - 1.
+ * counts / weights (m ints each, nullable) receive host copies.  The counts stay resident in MH_BUF_COUNTS exactly as after
+ * mh_score (a following mh_select_best behaves as after mh_score), the weights in MH_BUF_WEIGHTS.  Most pairs are decided
+ * "far" by the FP32 pre-test of mh_score (csrc/msac32.hip; mh_set_tuning key 15 = 0: every pair in FP64); the call adds n * m
+ * to the pairs of mh_get_score_stats and the pairs that went through the FP64 formula to its pairs_fp64.  On an empty shard
+ * (a transport is set, more ranks than hypotheses) a no-op that succeeds, as mh_score is. */
+#define MH_MSAC_SCALE 256
+MH_API int mh_score_msac(mh_engine* e, double thr2, const unsigned char* point_mask, int* counts, int* weights);
+/* The model with the highest weight of the last mh_score_msac, the lowest index on ties (the one-workgroup arg-max of
+ * mh_select_best on the weights), and that model's count.  Outputs nullable.  MH_ERR_NOT_SET unless mh_score_msac has run on
+ * the current model set and correspondences: mh_set_models, mh_propose_dlt4, mh_adopt_prefetched and mh_set_correspondences
+ * make the weights stale.  One rank only: MH_ERR_INVALID with a transport of world > 1. */
+MH_API int mh_select_best_msac(mh_engine* e, long long* best_index, int* best_weight, int* best_count);
 /* The N x M residual matrix of north_star, model-major: R[m*n + i] = d2(point i, model m),
  * written to HBM by one kernel that also produces the inlier counts.  R_host (nullable)
  * receives a host copy — leave NULL to keep the matrix on the device only. */
@@ -420,7 +443,8 @@ MH_API int mh_labeling_step(mh_engine* e, int warm, int* labeling, double* energ
 
 /* ---- device-side access (bench / multi-GPU plumbing) --------------------- */
 enum { MH_BUF_COUNTS = 0, MH_BUF_MODELS = 1, MH_BUF_RESIDUALS = 2, MH_BUF_LABELS = 3, MH_BUF_COST = 4, MH_BUF_GATHERED_SCORES = 5,
-       MH_BUF_LABEL_COUNTS = 6 /* per label, its member count in the last re-estimation (mh_reestimate / mh_labeling_step) */ };
+       MH_BUF_LABEL_COUNTS = 6 /* per label, its member count in the last re-estimation (mh_reestimate / mh_labeling_step) */,
+       MH_BUF_WEIGHTS = 7 /* per model, the weight of the last mh_score_msac (m ints) */ };
 /* Device pointer and size in bytes of a resident buffer (valid until the next call that
  * re-allocates it).  Used to wrap the per-model scores in a tensor for the RCCL all-gather. */
 MH_API int mh_device_buffer(mh_engine* e, int which, void** ptr_dev, unsigned long long* bytes);

@@ -16,7 +16,8 @@ LIB_PATH = os.environ.get("MH_LIB") or os.path.join(HERE, "libmultih_hip.so")
 MH_OK = 0
 ERR_NAMES = {-1: "MH_ERR_NO_DEVICE", -2: "MH_ERR_INVALID", -3: "MH_ERR_HIP", -4: "MH_ERR_NOT_SET",
              -5: "MH_ERR_OVERFLOW"}
-BUF_COUNTS, BUF_MODELS, BUF_RESIDUALS, BUF_LABELS, BUF_COST, BUF_LABEL_COUNTS = 0, 1, 2, 3, 4, 6
+BUF_COUNTS, BUF_MODELS, BUF_RESIDUALS, BUF_LABELS, BUF_COST, BUF_LABEL_COUNTS, BUF_WEIGHTS = 0, 1, 2, 3, 4, 6, 7
+MSAC_SCALE = 256                       # MH_MSAC_SCALE
 ESTIMATORS = {"haf": 0, "3pt": 1}      # MH_ESTIMATOR_HAF, MH_ESTIMATOR_3PT
 SAMPLER_UNIFORM, SAMPLER_LOCAL = 0, 1  # MH_SAMPLER_UNIFORM, MH_SAMPLER_LOCAL
 DATA_TERMS = {"reference": 0, "rising": 1}      # MH_DATA_TERM_REFERENCE, MH_DATA_TERM_RISING
@@ -29,7 +30,7 @@ SYMBOLS = [
     "mh_set_neighbors_csr", "mh_build_neighbors_knn", "mh_build_neighbors_knn_radius", "mh_build_neighbors_radius", "mh_get_sym_graph", "mh_set_fundamental_metric", "mh_propose_fund8",
     "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_propose_fund7", "mh_get_fund7_samples", "mh_estimate_fundamental_minimal", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons", "mh_refine_points",
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
-    "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_set_residual_mode", "mh_score",
+    "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_set_residual_mode", "mh_score", "mh_score_msac", "mh_select_best_msac",
     "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
     "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
     "mh_profile_get", "mh_set_tuning",
@@ -304,6 +305,12 @@ class Engine:
         self._check(self.lib.mh_get_models(self._h, _p(H, C.c_double)))
         return H
 
+    def get_model(self, idx: int):
+        """mh_get_model: one model of the current set."""
+        H = np.empty(9, dtype=np.float64)
+        self._check(self.lib.mh_get_model(self._h, int(idx), _p(H, C.c_double)))
+        return H
+
     def get_samples(self):
         idx = np.empty((self.model_count, 4), dtype=np.int32)
         self._check(self.lib.mh_get_samples(self._h, _p(idx, C.c_int)))
@@ -336,6 +343,25 @@ class Engine:
             mp = _p(mask, C.c_ubyte)
         self._check(self.lib.mh_score(self._h, C.c_double(thr2), mp, _p(cnt, C.c_int) if fetch else None))
         return cnt
+
+    def score_msac(self, thr2: float, mask=None, fetch: bool = True):
+        """mh_score_msac: (counts, weights) per model — mh_score's counts and the MSAC weights; fetch=False leaves both on the device."""
+        m = self.model_count
+        cnt = np.empty(m, dtype=np.int32) if fetch else None
+        wgt = np.empty(m, dtype=np.int32) if fetch else None
+        mp = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+            mp = _p(mask, C.c_ubyte)
+        self._check(self.lib.mh_score_msac(self._h, C.c_double(thr2), mp, _p(cnt, C.c_int) if fetch else None,
+                                           _p(wgt, C.c_int) if fetch else None))
+        return cnt, wgt
+
+    def select_best_msac(self):
+        """mh_select_best_msac: (index, weight, count) of the model with the highest weight, the lowest index on ties."""
+        idx, wgt, cnt = C.c_longlong(0), C.c_int(0), C.c_int(0)
+        self._check(self.lib.mh_select_best_msac(self._h, C.byref(idx), C.byref(wgt), C.byref(cnt)))
+        return int(idx.value), int(wgt.value), int(cnt.value)
 
     def residual_matrix(self, thr2: float, fetch_R: bool = True, fetch_counts: bool = True):
         m = self.model_count

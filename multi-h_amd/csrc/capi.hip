@@ -425,7 +425,9 @@ void mh_destroy(mh_engine* e)
     e->ms_partial2.release(); e->ms_ctl.release(); e->ms_pcnt2.release(); e->ms_ticks.release();
     for (int q = 0; q < mh_engine::PF_DEPTH; ++q) { e->pf_H[q].release(); e->pf_samples[q].release(); if (e->pf_ev[q]) (void)hipEventDestroy(e->pf_ev[q]); }
     e->best_key.release(); e->H32.release(); e->fb_pairs.release();
+    e->weights.release(); e->weights_counts.release();
     if (e->h_best) (void)hipHostFree(e->h_best);
+    if (e->h_best_w) (void)hipHostFree(e->h_best_w);
     if (e->ev_main) (void)hipEventDestroy(e->ev_main);
     if (e->ev_side_pre) (void)hipEventDestroy(e->ev_side_pre);
     if (e->side_stream) { (void)hipStreamSynchronize(e->side_stream); (void)hipStreamDestroy(e->side_stream); }
@@ -489,6 +491,7 @@ int mh_set_correspondences(mh_engine* e, const double* src_xy, const double* dst
     e->pf_count = 0;
     e->pf_head = 0;
     e->smp_k = 0;                                       // the sampling table belongs to the old point set
+    e->weights_models_seq = -1;                         // ... and so do the weights of mh_score_msac
     // +1 element of slack: the 16-B vector loads of the residual sweep never cross the end,
     // but keep the allocation even-sized for them.
     const size_t cap = (size_t)n + 2;
@@ -748,6 +751,7 @@ int mh_device_buffer(mh_engine* e, int which, void** ptr_dev, unsigned long long
     case MH_BUF_COST: *ptr_dev = e->cost.p; *bytes = sizeof(int) * (size_t)e->n * e->cost_L; break;
     case MH_BUF_GATHERED_SCORES: *ptr_dev = e->sel_gathered.p; *bytes = sizeof(int) * e->sel_gathered.cap; break;
     case MH_BUF_LABEL_COUNTS: *ptr_dev = e->label_counts.p; *bytes = sizeof(int) * std::min<size_t>(e->label_counts.cap, (size_t)e->m); break;
+    case MH_BUF_WEIGHTS: *ptr_dev = e->weights_models_seq == e->models_seq ? e->weights.p : nullptr; *bytes = sizeof(int) * (size_t)e->m; break;
     default: return fail(MH_ERR_INVALID, "unknown buffer id");
     }
     if (!*ptr_dev) return fail(MH_ERR_NOT_SET, "buffer has not been produced yet");

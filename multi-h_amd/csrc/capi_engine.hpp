@@ -266,6 +266,13 @@ struct mh_engine {
     DevBuf<float> H32;
     DevBuf<unsigned long long> fb_pairs;
     long long score_pairs = 0;                 // pairs scored through the pre-test since the last reset (mh_get_score_stats)
+    long long score_pairs_plain_fp64 = 0;      // ... of which mh_score_msac's plain FP64 form took (all of them through the FP64 formula)
+    // mh_score_msac: the weights, a copy of the counts they belong to (the counts buffer itself may go to an exchange: mh_select_best),
+    // and the model-set generation both were computed for (-1: none; mh_set_correspondences resets it)
+    DevBuf<int> weights, weights_counts;
+    long long weights_models_seq = -1;
+    int* h_best_w = nullptr;                   // mapped pinned: mh_select_best_msac's weight, index, sequence number, error word
+    int* h_best_w_dev = nullptr;
     Points pts() const { return Points{ x1.p, y1.p, x2.p, y2.p, n, bbox[0], bbox[1], bbox[2], bbox[3] }; }
 };
 

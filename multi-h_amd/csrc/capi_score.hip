@@ -121,6 +121,19 @@ int mh_get_models(mh_engine* e, double* H)
     });
 }
 
+int mh_get_model(mh_engine* e, int idx, double H[9])
+{
+    return guarded([&]() -> int {
+    if (!e || !H) return fail(MH_ERR_INVALID, "null argument");
+    HIPCHK(hipSetDevice(e->device));
+    if (e->m <= 0) return fail(MH_ERR_NOT_SET, "model set is empty");
+    if (idx < 0 || idx >= e->m) return fail(MH_ERR_INVALID, "model index out of range");
+    HIPCHK(hipMemcpyAsync(H, e->H.p + 9 * (size_t)idx, sizeof(double) * 9, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MH_OK;
+    });
+}
+
 int mh_get_model_count(mh_engine* e, int* m)
 {
     return guarded([&]() -> int {
@@ -176,6 +189,51 @@ int mh_score(mh_engine* e, double thr2, const unsigned char* point_mask, int* co
         HIPCHK(hipMemcpyAsync(counts, e->counts.p, sizeof(int) * e->m, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
     }
+    return MH_OK;
+    });
+}
+
+int mh_score_msac(mh_engine* e, double thr2, const unsigned char* point_mask, int* counts, int* weights)
+{
+    return guarded([&]() -> int {
+    bool empty_shard = false;
+    int rc = require_models_or_empty_shard(e, &empty_shard);
+    if (rc || empty_shard) return rc;
+    if (e->residual_mode == MH_RESIDUAL_SYMMETRIC) return fail(MH_ERR_INVALID, "mh_score_msac: forward residual only");
+    if ((long long)e->n * MH_MSAC_SCALE > 2147483647ll) return fail(MH_ERR_OVERFLOW, "mh_score_msac: n * MH_MSAC_SCALE exceeds int32");
+    HIPCHK(reserve_counts(e, (size_t)e->m + 1));
+    HIPCHK(e->weights.reserve((size_t)e->m + 1));
+    HIPCHK(e->weights_counts.reserve((size_t)e->m + 1));
+    const unsigned char* dmask = nullptr;
+    if (point_mask) {
+        HIPCHK(e->mask.reserve((size_t)e->n + 2));
+        HIPCHK(hipMemcpyAsync(e->mask.p, point_mask, e->n, hipMemcpyHostToDevice, e->stream));
+        dmask = e->mask.p;
+    }
+    e->weights_models_seq = -1;
+    {
+        ScopedTimer t(e, MH_K_SCORE);
+        // the form: score_models' preconditions for the FP32 pre-test (key 15, bounded coordinates, thr2 in [2^-40, 2^40])
+        HIPCHK(e->fb_pairs.reserve(1));        // (both forms add to score_pairs, which decides when the device counter is cleared)
+        if (e->score_pairs == 0) HIPCHK(hipMemsetAsync(e->fb_pairs.p, 0, sizeof(unsigned long long), e->stream));
+        if (e->tune_score32 && e->coords32_ok && thr2 >= 0x1p-40 && thr2 <= 0x1p40) {
+            HIPCHK(e->H32.reserve((size_t)e->m * 16));
+            HIPCHK(launch_model32(e->H.p, e->m, e->absmax_x, e->absmax_y, e->absmax_dst, e->H32.p, e->stream));
+            HIPCHK(launch_msac32(e->pts(), e->H.p, e->H32.p, e->m, thr2, e->absmax_dst, dmask, e->counts.p, e->weights.p, e->fb_pairs.p, e->stream));
+        } else {
+            HIPCHK(launch_msac64(e->pts(), e->H.p, e->m, thr2, dmask, e->counts.p, e->weights.p, e->stream));
+            e->score_pairs_plain_fp64 += (long long)e->m * e->n;
+        }
+        e->score_pairs += (long long)e->m * e->n;
+    }
+    // mh_select_best_msac reports the winner's count too, and the counts buffer may be handed to an exchange before it is asked
+    HIPCHK(hipMemcpyAsync(e->weights_counts.p, e->counts.p, sizeof(int) * (size_t)e->m, hipMemcpyDeviceToDevice, e->stream));
+    e->counts_zeroed = false;
+    e->counts_fresh = true;
+    e->weights_models_seq = e->models_seq;
+    if (counts) HIPCHK(hipMemcpyAsync(counts, e->counts.p, sizeof(int) * e->m, hipMemcpyDeviceToHost, e->stream));
+    if (weights) HIPCHK(hipMemcpyAsync(weights, e->weights.p, sizeof(int) * e->m, hipMemcpyDeviceToHost, e->stream));
+    if (counts || weights) HIPCHK(hipStreamSynchronize(e->stream));
     return MH_OK;
     });
 }

@@ -411,6 +411,35 @@ int mh_select_best(mh_engine* e, long long total_m, long long* best_index, int* 
     });
 }
 
+int mh_select_best_msac(mh_engine* e, long long* best_index, int* best_weight, int* best_count)
+{
+    return guarded([&]() -> int {
+    int rc = require_points(e);
+    if (rc) return rc;
+    if ((e->t_stream_fn || e->t_host_fn) && e->t_world > 1) return fail(MH_ERR_INVALID, "mh_select_best_msac: one rank only (the weights are not exchanged)");
+    if (e->m <= 0) return fail(MH_ERR_NOT_SET, "model set is empty");
+    if (e->weights_models_seq != e->models_seq || !e->weights.p) return fail(MH_ERR_NOT_SET, "the batch has no weights (mh_score_msac)");
+    if (!e->h_best_w) {
+        HIPCHK(hipHostMalloc((void**)&e->h_best_w, sizeof(int) * 4, hipHostMallocMapped));
+        HIPCHK(hipHostGetDevicePointer((void**)&e->h_best_w_dev, e->h_best_w, 0));
+        e->h_best_w[0] = e->h_best_w[1] = e->h_best_w[2] = e->h_best_w[3] = 0;
+    }
+    // mh_select_best's one-workgroup arg-max (highest score, lowest index on ties) on the weights, on the main stream
+    const int seq = e->h_best_w[2];
+    HIPCHK(launch_best_fused(e->weights.p, 1, e->m, 0, 0, e->h_best_w_dev, nullptr, 0, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->h_best_w[2] != seq + 1 || e->h_best_w[3] != 0 || e->h_best_w[1] < 0 || e->h_best_w[1] >= e->m)
+        return fail(MH_ERR_HIP, "mh_select_best_msac: no result from the arg-max");
+    if (best_index) *best_index = e->h_best_w[1];
+    if (best_weight) *best_weight = e->h_best_w[0];
+    if (best_count) {
+        HIPCHK(hipMemcpyAsync(best_count, e->weights_counts.p + e->h_best_w[1], sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    return MH_OK;
+    });
+}
+
 int mh_get_score_stats(mh_engine* e, long long* pairs, long long* pairs_fp64, int reset)
 {
     return guarded([&]() -> int {
@@ -422,8 +451,8 @@ int mh_get_score_stats(mh_engine* e, long long* pairs, long long* pairs_fp64, in
         HIPCHK(hipStreamSynchronize(e->stream));
     }
     if (pairs) *pairs = e->score_pairs;
-    if (pairs_fp64) *pairs_fp64 = (long long)fb;
-    if (reset) e->score_pairs = 0;                 // (the device counter is cleared by the next scoring call)
+    if (pairs_fp64) *pairs_fp64 = (long long)fb + e->score_pairs_plain_fp64;
+    if (reset) { e->score_pairs = 0; e->score_pairs_plain_fp64 = 0; }     // (the device counter is cleared by the next scoring call)
     return MH_OK;
     });
 }

@@ -61,6 +61,13 @@ hipError_t launch_score32(const Points& p, const double* H, const float* H32, in
 hipError_t launch_cost32(const Points& p, const double* H, const float* H32, int M, double lambda, double thr2, double Cmax,
                          int* C, long long ldc, int* counts, hipStream_t s, int* resident_ctl = nullptr, int cu_count = 256,
                          int psplit_override = 0, int slice_major = 0, int batched = 0, int* occ_cache = nullptr, int rising = 0);
+// --- msac32.hip: per model the inlier count AND the sum of the inliers' MSAC gains (include/multih_hip.h, mh_score_msac) —
+// launch_msac32 behind score32.hip's pre-test (same H32 / Cmax / thr2 preconditions as launch_score32; fp64_pairs, nullable:
+// device counter of the pairs that went through the FP64 formula), launch_msac64 with every pair in FP64
+hipError_t launch_msac32(const Points& p, const double* H, const float* H32, int M, double thr2, double Cmax, const unsigned char* mask,
+                         int* counts, int* weights, unsigned long long* fp64_pairs, hipStream_t s);
+hipError_t launch_msac64(const Points& p, const double* H, int M, double thr2, const unsigned char* mask, int* counts, int* weights,
+                         hipStream_t s);
 // occ_cache (both launchers): the caller's per-engine cache of the resident kernel's workgroups per compute unit (-1 = not asked yet)
 hipError_t launch_inliers_of_model(const Points& p, const double* H, int idx, double thr2,
                                    int label_value, int* labels, hipStream_t s);

@@ -29,6 +29,10 @@
 #pragma weak mh_build_sample_neighbours
 // ... and for the data term (SetDataTerm): without its entry point the rising term fails with a message.
 #pragma weak mh_set_data_term
+// ... and for the MSAC tail (SetTailScore): without its entry points that tail fails with a message.
+#pragma weak mh_score_msac
+#pragma weak mh_select_best_msac
+#pragma weak mh_get_model
 
 namespace {
 
@@ -295,6 +299,15 @@ bool MultiH::Run(bool points_only)
             return false;
         }
     } else if (!Check(mh_set_data_term(engine, data_term), "mh_set_data_term")) {
+        return false;
+    }
+    // how the degenerate tail ranks its hypotheses
+    if (tail_score != TAIL_SCORE_COUNT && tail_score != TAIL_SCORE_MSAC) {
+        std::cerr << "Error: unknown tail score " << tail_score << " (TAIL_SCORE_COUNT or TAIL_SCORE_MSAC)\n";
+        return false;
+    }
+    if (tail_score == TAIL_SCORE_MSAC && (!mh_score_msac || !mh_select_best_msac || !mh_get_model)) {
+        std::cerr << "Error: the engine library has no MSAC scores (mh_score_msac, mh_select_best_msac, mh_get_model)\n";
         return false;
     }
     stage("engine");
@@ -936,6 +949,18 @@ void MultiH::HandleDegenerateCase()
     const int M = std::max(proposal_hypotheses, 1000);
     if (!ApplyProposalSampler(false)) return;          // this batch is uniform whatever SetProposalSampler says (the oracle's mho_handle_degenerate defines it)
     if (!Check(mh_propose_dlt4(engine, proposal_seed ^ 0xdeadull, 0, M), "mh_propose_dlt4")) return;
+    if (tail_score == TAIL_SCORE_MSAC) {
+        // by weight: the scores stay on the device, the engine's arg-max picks, one H comes back
+        long long best = 0;
+        if (!Check(mh_score_msac(engine, sqr_threshold_homography, nullptr, nullptr, nullptr), "mh_score_msac")) return;
+        if (!Check(mh_select_best_msac(engine, &best, nullptr, nullptr), "mh_select_best_msac")) return;
+        if (!Check(mh_inliers_of_model(engine, (int)best, sqr_threshold_homography, 0, labeling.data()), "mh_inliers_of_model"))
+            return;
+        double Hb[9];
+        if (!Check(mh_get_model(engine, (int)best, Hb), "mh_get_model")) return;
+        cluster_homographies.push_back(MatFrom9(Hb));
+        return;
+    }
     std::vector<int> counts(M);
     if (!Check(mh_score(engine, sqr_threshold_homography, nullptr, counts.data()), "mh_score")) return;
     const int best = static_cast<int>(std::max_element(counts.begin(), counts.end()) - counts.begin());
@@ -1034,6 +1059,10 @@ void mhh_set_fundamental_estimator(int mode, int max_samples, double confidence)
 static int g_data_term = -1;
 extern "C" __attribute__((visibility("default")))
 void mhh_set_data_term(int term) { g_data_term = term; }
+// MultiH::SetTailScore for the next mhh_run_process calls (< 0: the class default)
+static int g_tail_score = -1;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_tail_score(int score) { g_tail_score = score; }
 extern "C" __attribute__((visibility("default")))
 void mhh_get_front_stages(int out[4]) { for (int i = 0; i < 4; ++i) out[i] = g_front_stages[i]; }
 // multih::FilterCorrespondencesByEpipolarGeometry on plain arrays: mask (n flags) out; returns the number kept, -1 on failure
@@ -1109,6 +1138,7 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     if (g_proposal_sampler != 0) mh.SetProposalSampler(g_proposal_sampler, g_proposal_sampler_k, g_proposal_uniform_per_16);
     if (g_fund_metric >= 0) mh.SetFundamentalMetric(g_fund_metric);
     if (g_data_term >= 0) mh.SetDataTerm(g_data_term);
+    if (g_tail_score >= 0) mh.SetTailScore(g_tail_score);
     if (g_fund_estimator >= 0) mh.SetFundamentalEstimator(g_fund_estimator, g_fund_max_samples, g_fund_confidence);
     for (const auto& kv : g_tuning) mh.SetEngineTuning(kv.first, kv.second);
     if (g_radius > 0.0 && g_max_hits > 0) { mh.SetNeighbourRadius(g_radius, g_max_hits); if (g_knn > 0) mh.SetFallbackK(g_knn); }

@@ -138,6 +138,13 @@ public:
     // (the loop's energy is the engine's).  Any other value makes Process() fail with a message.
     enum { DATA_TERM_REFERENCE = 0, DATA_TERM_RISING = 1 };
     void SetDataTerm(int t) { data_term = t; }
+    // How the degenerate tail (HandleDegenerateCase) ranks its DLT hypotheses: TAIL_SCORE_COUNT by the inlier count (mh_score
+    // and the first maximum; default), TAIL_SCORE_MSAC by the MSAC weight of include/multih_hip.h (mh_score_msac +
+    // mh_select_best_msac: among hypotheses the one whose inliers fit best, the lowest index on ties; only the winning H is
+    // fetched).  Everything else in the tail is the same: the original points, the uniform batch, the inliers at thr^2, label 0.
+    // Any other value makes Process() fail with a message.
+    enum { TAIL_SCORE_COUNT = 0, TAIL_SCORE_MSAC = 1 };
+    void SetTailScore(int t) { tail_score = t; }
     // The sampler of the proposal batches (the initial one and the iterative ones): uniform 4-tuples (default), or
     // neighbourhood-guided ones (mh_set_sampler, MH_SAMPLER_LOCAL): the first index uniform, the other three from its `k`
     // nearest neighbours in (x1, y1, x2, y2), with `uniform_per_16` hypotheses of every 16 left uniform (a homography from a
@@ -238,6 +245,7 @@ protected:
     bool proposal_refit = true;
     int estimator = ESTIMATOR_HAF;
     int data_term = DATA_TERM_REFERENCE;
+    int tail_score = TAIL_SCORE_COUNT;
     int proposal_sampler = PROPOSAL_UNIFORM, proposal_sampler_k = 32, proposal_uniform_per_16 = 4;
     bool proposal_local_run = false;      // this Process() call proposes with the local sampler (its table is on the engine)
     bool ApplyProposalSampler(bool local);

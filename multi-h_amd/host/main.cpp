@@ -25,6 +25,8 @@
 //                                is the reference's); --points always takes 3pt
 //                  [--data-term reference|rising]   the data term of the labeling (MultiH::SetDataTerm): reference, the default, is
 //                                the reference's dataEnergy (the cost falls as the fit gets worse); rising drops its `1.0 -`
+//                  [--tail-score count|msac]   how the degenerate tail ranks its DLT hypotheses (MultiH::SetTailScore): count, the
+//                                default, by inlier count; msac by the fit-weighted score of mh_score_msac
 //                  [--sampler uniform|local[:k[:u]]]   the sampler of the proposal batches (MultiH::SetProposalSampler): uniform
 //                                4-tuples (default) or neighbourhood-guided ones from the k nearest neighbours (32) with u of
 //                                every 16 hypotheses left uniform (4)
@@ -107,7 +109,7 @@ int main(int argc, char** argv)
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
                      "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] [--f-estimator ls8|minimal] "
-                     "[--stages file] [--points] [--estimator haf|3pt] [--data-term reference|rising] [--sampler uniform|local[:k[:u]]] [--ranks n]\n";
+                     "[--stages file] [--points] [--estimator haf|3pt] [--data-term reference|rising] [--tail-score count|msac] [--sampler uniform|local[:k[:u]]] [--ranks n]\n";
         return 2;
     }
     double thrF = 2.6, thrH = 2.2, locality = 0.005, lambda = 0.5;     // M/main.cpp:55-59
@@ -121,6 +123,7 @@ int main(int argc, char** argv)
     bool points_only = false;
     int estimator = MultiH::ESTIMATOR_HAF;
     int data_term = MultiH::DATA_TERM_REFERENCE;
+    int tail_score = MultiH::TAIL_SCORE_COUNT;
     int sampler = MultiH::PROPOSAL_UNIFORM, sampler_k = 32, sampler_u = 4;
     for (int i = 3; i < argc; ++i) {
         const std::string k = argv[i];
@@ -137,6 +140,11 @@ int main(int argc, char** argv)
             if (std::string(v) == "reference") data_term = MultiH::DATA_TERM_REFERENCE;
             else if (std::string(v) == "rising") data_term = MultiH::DATA_TERM_RISING;
             else { std::cerr << "--data-term: reference or rising\n"; return 2; }
+        }
+        else if (k == "--tail-score") {
+            if (std::string(v) == "count") tail_score = MultiH::TAIL_SCORE_COUNT;
+            else if (std::string(v) == "msac") tail_score = MultiH::TAIL_SCORE_MSAC;
+            else { std::cerr << "--tail-score: count or msac\n"; return 2; }
         }
         else if (k == "--sampler") {
             // uniform | local | local:k | local:k:u — whole numbers, nothing behind them
@@ -306,6 +314,7 @@ int main(int argc, char** argv)
     else if (neighbourhood == "approx") multiH->SetNeighbourApprox(4, 32, 0x464c414e4eull + seed);   // ... as FLANN's default search answers it
     multiH->SetEstimator(estimator);
     multiH->SetDataTerm(data_term);
+    multiH->SetTailScore(tail_score);
     multiH->SetProposalSampler(sampler, sampler_k, sampler_u);
     const bool processed = points_only ? multiH->Process(srcPointsOrig, dstPointsOrig)
                                        : multiH->Process(srcPointsOrig, dstPointsOrig, origAffines);
