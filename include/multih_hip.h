@@ -321,9 +321,42 @@ MH_API int mh_set_transport(mh_engine* e, int rank, int world, mh_allgather_stre
  * shard size, a failing scoring launch) does not keep the rank out of the round's collectives: it offers
  * nothing, sets the record's error word, and after the exchange every rank leaves the loop — the failing one with its
  * own error, the others with MH_ERR_HIP "a rank reported an error".  Arguments (thr2, need, max_models, total_m) must be
- * the same on every rank. */
+ * the same on every rank, and so must the settings the records' mode word carries: the residual mode, refitted winners and their
+ * estimator, the sampler, and (bit 15) whether the rank ranks by count — this entry point — or by weight
+ * (mh_select_greedy_msac); ranks that disagree all return MH_ERR_INVALID after the first exchange. */
 MH_API int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned char* point_mask,
                             double* H_out, long long* counters_out, int* counts_out, int* selected_out, long long total_m);
+/* The same selection RANKED BY MSAC WEIGHT — a mode beside mh_select_greedy, which is unchanged.  The arguments are those of
+ * mh_select_greedy plus weights_out (nullable, max_models ints).  Each round works on the support set S: the points with
+ * mask != 0 (all points when no mask is given).
+ *   1. Score.        Every candidate c gets count_c and weight_c over S exactly as mh_score_msac defines them: a pair with
+ *                    d2 < thr2 counts 1 and weighs (int)round(256.0 * (1.0 - (d2 / thr2))), every other pair counts 0 and weighs
+ *                    0; d2 is the forward error in the reference's operation order.
+ *   2. Eligibility.  A candidate is eligible when count_c >= need.  A weight never makes up for a missing count.
+ *   3. Winner.       The eligible candidate with the highest weight, the lowest position in the WHOLE batch on ties.  If no
+ *                    candidate is eligible the selection ends.  An eligible candidate of weight 0 can still win (every inlier
+ *                    may sit just under the threshold).
+ *   4. Claim.        The winner's inliers on S leave S (d2 < thr2, strictly).  H_out, counters_out, counts_out and weights_out
+ *                    take the hypothesis' H, batch position, count and weight at the moment it was selected.
+ *   5. Compaction.   Candidates with count_c >= need move on to the next round, the winner does not (counts and weights only
+ *                    fall as S shrinks).
+ *   6. Refit (mh_set_tuning key 30; HAF or MH_ESTIMATOR_3PT as for mh_select_greedy).  The winner is refitted to its inliers on S;
+ *                    the refit takes its place in the claim and in H_out when it is finite and its WEIGHT on S is at least the
+ *                    hypothesis' weight (mh_select_greedy: "explains at least as many points").  counts_out and weights_out
+ *                    stay the hypothesis' own.
+ * MH_ERR_INVALID under MH_RESIDUAL_SYMMETRIC (as mh_score_msac); MH_ERR_OVERFLOW, before anything is launched, when
+ * n * MH_MSAC_SCALE exceeds 2^31 - 1; the argument checks of mh_select_greedy.  mh_set_tuning keys 15 (every pair in FP64) and
+ * 36 (rounds by subtraction or by recount) are schedules here too: same outputs.  The pairs scored go into mh_get_score_stats as
+ * under mh_score_msac.
+ * Sharded batch: the collectives of mh_select_greedy, with the same sizes — in the first round one all-gather of the int32 score
+ * vectors (here: the weight of every eligible hypothesis, -1 for the others), in every round one 88-byte record per rank (the
+ * key's high word is the weight).  "Ranked by weight" travels in the records' mode word: if one rank calls mh_select_greedy and
+ * another this entry point, every rank returns the mode-mismatch MH_ERR_INVALID after the first round's exchange; nobody waits
+ * in a collective the others do not run.  Rank-local failures as in mh_select_greedy.  Outputs do not depend on the number of
+ * ranks. */
+MH_API int mh_select_greedy_msac(mh_engine* e, double thr2, int need, int max_models, unsigned char* point_mask,
+                                 double* H_out, long long* counters_out, int* counts_out, int* weights_out, int* selected_out,
+                                 long long total_m);
 /* Pipelined propose: mh_prefetch_dlt4 prepares the batch (seed, first .. first+m-1) in one of the engine's spare model buffers
  * on a second stream, concurrently with whatever the main stream is doing (csrc/dlt4.hip); mh_adopt_prefetched makes the OLDEST
  * prepared batch the current model set — the main stream waits for the side stream's event, the host does not wait at all.

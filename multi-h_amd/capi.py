@@ -31,7 +31,7 @@ SYMBOLS = [
     "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_propose_fund7", "mh_get_fund7_samples", "mh_estimate_fundamental_minimal", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons", "mh_refine_points",
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
     "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_set_residual_mode", "mh_score", "mh_score_msac", "mh_select_best_msac",
-    "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
+    "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_select_greedy_msac", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
     "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
     "mh_profile_get", "mh_set_tuning",
 ]
@@ -398,6 +398,21 @@ class Engine:
                                               _p(H, C.c_double), counters.ctypes.data_as(C.POINTER(C.c_longlong)),
                                               _p(counts, C.c_int), C.byref(k), C.c_longlong(int(total_m))))
         return H[:k.value].copy(), counters[:k.value].copy(), counts[:k.value].copy(), m
+
+    def select_greedy_msac(self, thr2: float, need: int, max_models: int, mask=None, total_m: int = 0):
+        """The greedy selection ranked by MSAC weight (mh_select_greedy_msac): eligible with count >= need, the highest weight wins.
+        Returns (H [k,9], counters [k], counts [k], weights [k], mask_out or None)."""
+        H = np.zeros((int(max_models), 9))
+        counters = np.zeros(int(max_models), dtype=np.int64)
+        counts = np.zeros(int(max_models), dtype=np.int32)
+        weights = np.zeros(int(max_models), dtype=np.int32)
+        k = C.c_int(0)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).copy()
+        self._check(self.lib.mh_select_greedy_msac(self._h, C.c_double(thr2), int(need), int(max_models),
+                                                   None if m is None else m.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                                   _p(H, C.c_double), counters.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                   _p(counts, C.c_int), _p(weights, C.c_int), C.byref(k), C.c_longlong(int(total_m))))
+        return H[:k.value].copy(), counters[:k.value].copy(), counts[:k.value].copy(), weights[:k.value].copy(), m
 
     def set_transport(self, rank: int, world: int, stream_fn=None, host_fn=None, ctx=None):
         """mh_set_transport: stream_fn = a C function pointer that enqueues the all-gather on the engine's stream

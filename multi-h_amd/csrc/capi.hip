@@ -412,6 +412,7 @@ void mh_destroy(mh_engine* e)
     e->sel_pack_count.release();
     for (int c = 0; c < 4; ++c) e->sel_gone[c].release();
     e->sel_carried[0].release(); e->sel_carried[1].release(); e->sel_left.release();
+    e->sel_weights.release(); e->sel_carried_w[0].release(); e->sel_carried_w[1].release(); e->sel_left_w.release();
     e->gb_deg.release(); e->gb_start.release(); e->gb_cursor.release(); e->gb_raw.release(); e->gb_mult.release();
     e->gb_uniq.release(); e->gb_info.release(); e->gb_hits_rp.release(); e->gb_hits_col.release();
     if (e->h_flags) (void)hipHostFree(e->h_flags);

@@ -97,6 +97,7 @@ struct mh_engine {
     DevBuf<unsigned char> cp_ok;
     // greedy selection (select.hip): two candidate lists, control words, exchange buffers
     DevBuf<int> sel_orig[2], sel_counts, sel_carried[2], sel_left, sel_rec, sel_scores, sel_gathered;     // (sel_carried / sel_left: r05, the decremental rounds of mh_select_greedy)
+    DevBuf<int> sel_weights, sel_carried_w[2], sel_left_w;     // mh_select_greedy_msac: the candidates' weights beside sel_counts / sel_carried / sel_left
     DevBuf<double> sel_cand_H[2], sel_out_H;
     DevBuf<SelRecord> sel_records;             // [0] this rank's offer, [1 .. world] the gathered offers
     DevBuf<long long> sel_counter;
@@ -324,6 +325,10 @@ int quiesce(mh_engine* e);
 int join_xchg(mh_engine* e);
 // inlier counts of m models over the points p: FP32 pre-test where its preconditions hold, the FP64 sweep otherwise (capi_score.hip)
 int score_models(mh_engine* e, const Points& p, const double* Hs, int m, double thr2, const unsigned char* dmask, int* counts_dev);
+// the score_models of the selection ranked by weight: counts and MSAC weights, k_msac32 behind the pre-test where score_models'
+// preconditions hold, k_msac64 otherwise (capi_score.hip).  Forward residual; the caller has checked 256 n against int32.
+int msac_models(mh_engine* e, const Points& p, const double* Hs, int m, double thr2, const unsigned char* dmask, int* counts_dev,
+                int* weights_dev);
 // the engine's re-estimator over labels_dev (n ints) for models H_dev (Nh x 9, in place) — HAF or 3-point (capi_label.hip)
 int launch_estimator(mh_engine* e, const int* labels_dev, int Nh, double* H_dev, int* counts_dev);
 // the exchange's stream and events (capi_select.hip); the second stream of the prefetch queue (capi_score.hip)

@@ -30,6 +30,27 @@ int score_models(mh_engine* e, const Points& p, const double* Hs, int m, double 
     return MH_OK;
 }
 
+// Counts and MSAC weights of `m` models (device array Hs) over the points `p` — mh_score_msac's two forms for an arbitrary
+// candidate list and point set (the rounds of mh_select_greedy_msac): the H32 table is rebuilt for these models, the pairs go
+// into the statistics of mh_get_score_stats as there.
+int msac_models(mh_engine* e, const Points& p, const double* Hs, int m, double thr2, const unsigned char* dmask, int* counts_dev,
+                int* weights_dev)
+{
+    if (m <= 0 || p.n <= 0) return MH_OK;
+    HIPCHK(e->fb_pairs.reserve(1));        // (both forms add to score_pairs, which decides when the device counter is cleared)
+    if (e->score_pairs == 0) HIPCHK(hipMemsetAsync(e->fb_pairs.p, 0, sizeof(unsigned long long), e->stream));
+    if (e->tune_score32 && e->tune_score_variant == 0 && e->coords32_ok && thr2 >= 0x1p-40 && thr2 <= 0x1p40) {
+        HIPCHK(e->H32.reserve((size_t)m * 16));
+        HIPCHK(launch_model32(Hs, m, e->absmax_x, e->absmax_y, e->absmax_dst, e->H32.p, e->stream));
+        HIPCHK(launch_msac32(p, Hs, e->H32.p, m, thr2, e->absmax_dst, dmask, counts_dev, weights_dev, e->fb_pairs.p, e->stream));
+    } else {
+        HIPCHK(launch_msac64(p, Hs, m, thr2, dmask, counts_dev, weights_dev, e->stream));
+        e->score_pairs_plain_fp64 += (long long)m * p.n;
+    }
+    e->score_pairs += (long long)m * p.n;
+    return MH_OK;
+}
+
 // ---- pipelined propose -------------------------------------------------------------------------
 int ensure_side_stream(mh_engine* e)
 {

@@ -1,4 +1,4 @@
-// capi_select.hip: transport, greedy selection, the best model of a batch (the score exchange) — part of the C ABI of include/multih_hip.h (see capi_engine.hpp for the split).
+// capi_select.hip: transport, greedy selection (by count and by MSAC weight: one loop), the best model of a batch (the score exchange) — part of the C ABI of include/multih_hip.h (see capi_engine.hpp for the split).
 #include "capi_engine.hpp"
 
 namespace mhe {
@@ -38,35 +38,19 @@ int exchange(mh_engine* e, const void* send_dev, void* recv_dev, size_t bytes_pe
     return MH_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int mh_set_transport(mh_engine* e, int rank, int world, mh_allgather_stream_fn stream_fn, mh_allgather_dev_fn host_fn, void* ctx)
+// The rounds of mh_select_greedy (by_weight = false) and of mh_select_greedy_msac (true; select.hip, the k_sel_*_w kernels): one
+// loop, the same sequence of collectives with the same sizes either way.
+int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned char* point_mask, double* H_out,
+                  long long* counters_out, int* counts_out, int* weights_out, int* selected_out, long long total_m, const bool by_weight)
 {
-    return guarded([&]() -> int {
-    if (!e) return fail(MH_ERR_INVALID, "null engine");
-    if (world < 1 || rank < 0 || rank >= world) return fail(MH_ERR_INVALID, "bad rank / world");
-    if (stream_fn && host_fn) return fail(MH_ERR_INVALID, "give ONE transport: stream-ordered or host-synchronised");
-    if (world > 1 && !stream_fn && !host_fn) return fail(MH_ERR_INVALID, "world > 1 needs a transport");
-    if (e->xchg_pending) {                                 // an exchange in flight still uses the old transport
-        HIPCHK(hipSetDevice(e->device));
-        int rcq = quiesce(e);
-        if (rcq) return rcq;
-    }
-    e->t_rank = rank; e->t_world = world; e->t_stream_fn = stream_fn; e->t_host_fn = host_fn; e->t_ctx = ctx;
-    return MH_OK;
-    });
-}
-
-int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned char* point_mask,
-                     double* H_out, long long* counters_out, int* counts_out, int* selected_out, long long total_m)
-{
-    return guarded([&]() -> int {
     int rc = require_points(e);
     if (rc) return rc;
     if (!H_out || !selected_out || max_models <= 0 || need < 1) return fail(MH_ERR_INVALID, "bad argument");
     const int n = e->n;
+    if (by_weight) {
+        if (e->residual_mode == MH_RESIDUAL_SYMMETRIC) return fail(MH_ERR_INVALID, "mh_select_greedy_msac: forward residual only");
+        if ((long long)n * MH_MSAC_SCALE > 2147483647ll) return fail(MH_ERR_OVERFLOW, "mh_select_greedy_msac: n * MH_MSAC_SCALE exceeds int32");
+    }
     int M = e->m;                                     // M may be 0 on a rank without hypotheses (more ranks than hypotheses)
     // The transport is used whenever one is set — also with world == 1, where a one-rank communicator runs the whole
     // protocol (how the RCCL path is tested on a box with one GPU).
@@ -104,13 +88,17 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
     // The proposer's sampler travels in the word too: bit 3 the local sampler, bits 4-9 its k, bits 10-14 uniform_per_16 — all
     // zero under the default, so those records are what they were.  A rank-independent batch needs the ranks to agree on it.
     const int sampler_bits = e->sampler == MH_SAMPLER_LOCAL ? (8 | (e->smp_k << 4) | (e->sampler_uniform_per_16 << 10)) : 0;
+    // ... and so does "ranked by weight" (bit 15): a rank that called the other entry point runs the same collectives, and every
+    // rank leaves with the mode-mismatch error
+    const int mode_word = symmetric | (refine ? 2 : 0) | (refine && refit3 ? 4 : 0) | sampler_bits | (by_weight ? 1 << 15 : 0);
     if (refine && !refine_usable)
-        local_failure(MH_ERR_NOT_SET, refit3 ? "mh_select_greedy with refitted winners (mh_set_tuning key 30) needs the epipolar geometry"
-                                             : "mh_select_greedy with refitted winners (mh_set_tuning key 30) needs affinities and the epipolar geometry");
+        local_failure(MH_ERR_NOT_SET, std::string(by_weight ? "mh_select_greedy_msac" : "mh_select_greedy") +
+                                      (refit3 ? " with refitted winners (mh_set_tuning key 30) needs the epipolar geometry"
+                                              : " with refitted winners (mh_set_tuning key 30) needs affinities and the epipolar geometry"));
     if (refine) {
         HIPCHK(e->labels_pts.reserve((size_t)n));
         HIPCHK(e->sel_refit.reserve(10));
-        HIPCHK(e->sel_refit_ctr.reserve(2));
+        HIPCHK(e->sel_refit_ctr.reserve(4));
         if (refit3) HIPCHK(e->r3_scratch.reserve(reestimate_3pt_scratch_ints(n, 1)));
     }
     if (!sharded && M <= 0) local_failure(MH_ERR_NOT_SET, "model set is empty");
@@ -122,6 +110,7 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
     const size_t cap = (size_t)std::max(M, 1);
     for (int b = 0; b < 2; ++b) { HIPCHK(e->sel_orig[b].reserve(cap)); HIPCHK(e->sel_cand_H[b].reserve(cap * 9)); }
     HIPCHK(e->sel_counts.reserve(cap));
+    if (by_weight) HIPCHK(e->sel_weights.reserve(cap));
     HIPCHK(e->sel_rec.reserve(8));
     HIPCHK(e->sel_keys.reserve(2));
     HIPCHK(e->sel_out_H.reserve((size_t)max_models * 9));
@@ -163,6 +152,10 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
         for (int c = 0; c < 4; ++c) HIPCHK(e->sel_gone[c].reserve((size_t)n + 2));
         for (int b = 0; b < 2; ++b) HIPCHK(e->sel_carried[b].reserve(cap));
         HIPCHK(e->sel_left.reserve(cap));
+        if (by_weight) {
+            for (int b = 0; b < 2; ++b) HIPCHK(e->sel_carried_w[b].reserve(cap));
+            HIPCHK(e->sel_left_w.reserve(cap));
+        }
     }
     int gone = 0;                                         // points the last claim took out
 
@@ -181,17 +174,27 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
                 // the candidates' counts of the last round came along with them (k_sel_compact); subtract what left
                 if (gone == 0) {
                     HIPCHK(hipMemcpyAsync(e->sel_counts.p, e->sel_carried[cur].p, sizeof(int) * (size_t)Mc, hipMemcpyDeviceToDevice, s));
+                    if (by_weight) HIPCHK(hipMemcpyAsync(e->sel_weights.p, e->sel_carried_w[cur].p, sizeof(int) * (size_t)Mc, hipMemcpyDeviceToDevice, s));
                     return MH_OK;
                 }
                 Points left = e->pts();                       // (same bounding box: a superset's is valid)
                 left.x1 = e->sel_gone[0].p; left.y1 = e->sel_gone[1].p; left.x2 = e->sel_gone[2].p; left.y2 = e->sel_gone[3].p;
                 left.n = gone;
-                const int rcs = score_models(e, left, Hs, Mc, thr2, nullptr, e->sel_left.p);
+                const int rcs = by_weight ? msac_models(e, left, Hs, Mc, thr2, nullptr, e->sel_left.p, e->sel_left_w.p)
+                                          : score_models(e, left, Hs, Mc, thr2, nullptr, e->sel_left.p);
                 if (rcs) return rcs;
-                HIPCHK(launch_sel_subtract(e->sel_carried[cur].p, e->sel_left.p, Mc, e->sel_counts.p, s));
+                if (by_weight)      // both integer sums are exact: subtracting what left equals counting and weighing again
+                    HIPCHK(launch_sel_subtract_w(e->sel_carried[cur].p, e->sel_left.p, e->sel_carried_w[cur].p, e->sel_left_w.p, Mc,
+                                                 e->sel_counts.p, e->sel_weights.p, s));
+                else
+                    HIPCHK(launch_sel_subtract(e->sel_carried[cur].p, e->sel_left.p, Mc, e->sel_counts.p, s));
                 return MH_OK;
             }
-            if (active == n) return score_models(e, e->pts(), Hs, Mc, thr2, nullptr, e->sel_counts.p);     // every point is in the support set: no mask to read
+            auto score = [&](const Points& p) -> int {
+                return by_weight ? msac_models(e, p, Hs, Mc, thr2, nullptr, e->sel_counts.p, e->sel_weights.p)
+                                 : score_models(e, p, Hs, Mc, thr2, nullptr, e->sel_counts.p);
+            };
+            if (active == n) return score(e->pts());     // every point is in the support set: no mask to read
             if (active > 0) {
                 HIPCHK(launch_sel_pack_points(e->pts(), e->mask.p, e->sel_pts[0].p, e->sel_pts[1].p, e->sel_pts[2].p, e->sel_pts[3].p,
                                               e->sel_pack_count.p, s));
@@ -199,9 +202,10 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
                 Points packed = e->pts();                     // (same bounding box: a superset's is valid)
                 packed.x1 = e->sel_pts[0].p; packed.y1 = e->sel_pts[1].p; packed.x2 = e->sel_pts[2].p; packed.y2 = e->sel_pts[3].p;
                 packed.n = active;
-                return score_models(e, packed, Hs, Mc, thr2, nullptr, e->sel_counts.p);
+                return score(packed);
             }
             HIPCHK(hipMemsetAsync(e->sel_counts.p, 0, sizeof(int) * (size_t)Mc, s));
+            if (by_weight) HIPCHK(hipMemsetAsync(e->sel_weights.p, 0, sizeof(int) * (size_t)Mc, s));
             return MH_OK;
         };
         if (local_rc == MH_OK) {
@@ -214,8 +218,13 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
         }
         const int local_err = local_rc != MH_OK ? 1 : 0;
         const bool gather_scores = sharded && first && longest > 0;      // north_star's exchange, once per batch
-        HIPCHK(launch_sel_argmax(e->sel_counts.p, orig, Mc, my_off, key_local, gather_scores ? e->sel_scores.p : nullptr, s));
-        HIPCHK(launch_sel_record(e->sel_counts.p, orig, Hs, Mc, my_off, key_local, local_err, symmetric | (refine ? 2 : 0) | (refine && refit3 ? 4 : 0) | sampler_bits, my_record, s));
+        if (by_weight) {
+            HIPCHK(launch_sel_argmax_w(e->sel_counts.p, e->sel_weights.p, orig, Mc, need, my_off, key_local, gather_scores ? e->sel_scores.p : nullptr, s));
+            HIPCHK(launch_sel_record_w(e->sel_counts.p, e->sel_weights.p, orig, Hs, Mc, need, my_off, key_local, local_err, mode_word, my_record, s));
+        } else {
+            HIPCHK(launch_sel_argmax(e->sel_counts.p, orig, Mc, my_off, key_local, gather_scores ? e->sel_scores.p : nullptr, s));
+            HIPCHK(launch_sel_record(e->sel_counts.p, orig, Hs, Mc, my_off, key_local, local_err, mode_word, my_record, s));
+        }
         if (sharded) {
             if (gather_scores) {
                 rc = exchange(e, e->sel_scores.p, e->sel_gathered.p, sizeof(int) * (size_t)longest, s);
@@ -225,31 +234,49 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
             rc = exchange(e, my_record, records, sizeof(SelRecord), s);     // 88 bytes per rank
             if (rc) return rc;
         }
-        HIPCHK(launch_sel_compact(e->sel_counts.p, orig, Hs, Mc, need, records, world, my_off, e->sel_orig[cur ^ 1].p,
-                                  e->sel_cand_H[cur ^ 1].p, e->sel_rec.p, decrement ? e->sel_carried[cur ^ 1].p : nullptr, s));
+        if (by_weight)
+            HIPCHK(launch_sel_compact_w(e->sel_counts.p, e->sel_weights.p, orig, Hs, Mc, need, records, world, my_off, e->sel_orig[cur ^ 1].p,
+                                        e->sel_cand_H[cur ^ 1].p, e->sel_rec.p, decrement ? e->sel_carried[cur ^ 1].p : nullptr,
+                                        decrement ? e->sel_carried_w[cur ^ 1].p : nullptr, s));
+        else
+            HIPCHK(launch_sel_compact(e->sel_counts.p, orig, Hs, Mc, need, records, world, my_off, e->sel_orig[cur ^ 1].p,
+                                      e->sel_cand_H[cur ^ 1].p, e->sel_rec.p, decrement ? e->sel_carried[cur ^ 1].p : nullptr, s));
         const double* refit = nullptr;
         if (refine_usable) {
             // every rank holds all the points and the same records: the refit is computed redundantly, identically
             Affines aff{ e->a11.p, e->a12.p, e->a21.p, e->a22.p };
-            HIPCHK(launch_sel_refit(e->pts(), aff, e->epi, records, world, thr2, need, e->mask.p, e->labels_pts.p, e->sel_refit.p,
-                                    e->sel_refit_ctr.p, e->sel_refit_ctr.p + 1, s, symmetric, refit3 ? e->r3_scratch.p : nullptr));
+            if (by_weight)
+                HIPCHK(launch_sel_refit_w(e->pts(), aff, e->epi, records, world, thr2, e->mask.p, e->labels_pts.p, e->sel_refit.p,
+                                          e->sel_refit_ctr.p + 2, e->sel_refit_ctr.p + 1, s, refit3 ? e->r3_scratch.p : nullptr));
+            else
+                HIPCHK(launch_sel_refit(e->pts(), aff, e->epi, records, world, thr2, need, e->mask.p, e->labels_pts.p, e->sel_refit.p,
+                                        e->sel_refit_ctr.p, e->sel_refit_ctr.p + 1, s, symmetric, refit3 ? e->r3_scratch.p : nullptr));
             refit = e->sel_refit.p;
         }
-        HIPCHK(launch_sel_claim(e->pts(), records, world, gather_scores && !local_err ? key_check : nullptr, thr2, need, e->mask.p, e->sel_rec.p,
-                                e->sel_out_H.p, e->sel_counter.p, max_models, s, symmetric, refit,
-                                decrement ? e->sel_gone[0].p : nullptr, decrement ? e->sel_gone[1].p : nullptr,
-                                decrement ? e->sel_gone[2].p : nullptr, decrement ? e->sel_gone[3].p : nullptr));
-        HIPCHK(launch_sel_publish(e->sel_rec.p, e->sel_keys.p, my_record, need, e->h_sel_dev, s));
-        HIPCHK(hipStreamSynchronize(s));                 // five control words through mapped memory: no copy
+        const unsigned long long* check = gather_scores && !local_err ? key_check : nullptr;
+        double* gp[4] = { decrement ? e->sel_gone[0].p : nullptr, decrement ? e->sel_gone[1].p : nullptr,
+                          decrement ? e->sel_gone[2].p : nullptr, decrement ? e->sel_gone[3].p : nullptr };
+        if (by_weight) {
+            HIPCHK(launch_sel_claim_w(e->pts(), records, world, check, thr2, e->mask.p, e->sel_rec.p, e->sel_out_H.p, e->sel_counter.p,
+                                      max_models, s, refit, gp[0], gp[1], gp[2], gp[3]));
+            HIPCHK(launch_sel_publish_w(e->sel_rec.p, e->sel_keys.p, my_record, e->h_sel_dev, s));
+        } else {
+            HIPCHK(launch_sel_claim(e->pts(), records, world, check, thr2, need, e->mask.p, e->sel_rec.p,
+                                    e->sel_out_H.p, e->sel_counter.p, max_models, s, symmetric, refit, gp[0], gp[1], gp[2], gp[3]));
+            HIPCHK(launch_sel_publish(e->sel_rec.p, e->sel_keys.p, my_record, need, e->h_sel_dev, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));                 // the control words (six; seven by weight) through mapped memory: no copy
         if (local_rc != MH_OK) return fail(local_rc, local_msg);     // (the others have read this rank's error word by now)
         if (e->h_sel[4] != 0)                            // every rank sees the same word, so every rank leaves here
             return fail(e->h_sel[4] == 3 ? MH_ERR_INVALID : MH_ERR_HIP,
                         e->h_sel[4] == 2 ? "greedy selection: the gathered score vector and the ranks' records disagree about the winner"
-                        : e->h_sel[4] == 3 ? "greedy selection: the ranks are not in the same residual mode (mh_set_residual_mode) or do not agree on refitted winners (mh_set_tuning key 30), the estimator (mh_set_estimator) or the proposer's sampler (mh_set_sampler)"
+                        : e->h_sel[4] == 3 ? "greedy selection: the ranks are not in the same residual mode (mh_set_residual_mode) or do not agree on refitted winners (mh_set_tuning key 30), the estimator (mh_set_estimator), the proposer's sampler (mh_set_sampler) or the selection's score (mh_select_greedy / mh_select_greedy_msac)"
                                            : "greedy selection: a rank reported an error");
+        // by count: word 0 is the winner's count; by weight: its weight (-1 when nobody was eligible), its count is word 6
         const int best = e->h_sel[0];
-        if (best < need) break;
-        if (counts_out) counts_out[selected] = best;
+        if (by_weight ? best < 0 : best < need) break;
+        if (counts_out) counts_out[selected] = by_weight ? e->h_sel[6] : best;
+        if (weights_out) weights_out[selected] = best;
         ++selected;
         gone = e->h_sel[5];
         active -= gone;                                   // what the claim took out of the support set (the winner's inliers, or its refit's)
@@ -273,6 +300,42 @@ int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsign
     if (packed_n != packed_as)                           // the host's bookkeeping of the support set against the device's own count
         return fail(MH_ERR_HIP, "greedy selection: the packed support set does not have the expected size");
     return MH_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int mh_set_transport(mh_engine* e, int rank, int world, mh_allgather_stream_fn stream_fn, mh_allgather_dev_fn host_fn, void* ctx)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (world < 1 || rank < 0 || rank >= world) return fail(MH_ERR_INVALID, "bad rank / world");
+    if (stream_fn && host_fn) return fail(MH_ERR_INVALID, "give ONE transport: stream-ordered or host-synchronised");
+    if (world > 1 && !stream_fn && !host_fn) return fail(MH_ERR_INVALID, "world > 1 needs a transport");
+    if (e->xchg_pending) {                                 // an exchange in flight still uses the old transport
+        HIPCHK(hipSetDevice(e->device));
+        int rcq = quiesce(e);
+        if (rcq) return rcq;
+    }
+    e->t_rank = rank; e->t_world = world; e->t_stream_fn = stream_fn; e->t_host_fn = host_fn; e->t_ctx = ctx;
+    return MH_OK;
+    });
+}
+
+int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned char* point_mask,
+                     double* H_out, long long* counters_out, int* counts_out, int* selected_out, long long total_m)
+{
+    return guarded([&]() -> int {
+    return select_greedy(e, thr2, need, max_models, point_mask, H_out, counters_out, counts_out, nullptr, selected_out, total_m, false);
+    });
+}
+
+int mh_select_greedy_msac(mh_engine* e, double thr2, int need, int max_models, unsigned char* point_mask,
+                          double* H_out, long long* counters_out, int* counts_out, int* weights_out, int* selected_out, long long total_m)
+{
+    return guarded([&]() -> int {
+    return select_greedy(e, thr2, need, max_models, point_mask, H_out, counters_out, counts_out, weights_out, selected_out, total_m, true);
     });
 }
 

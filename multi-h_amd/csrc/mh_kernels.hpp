@@ -313,7 +313,7 @@ hipError_t launch_argmin_labels(const int* cost, int L, int n, int* label, long 
 hipError_t launch_sel_pack_points(const Points& p, const unsigned char* mask, double* cx1, double* cy1, double* cx2, double* cy2,
                                   int* count, hipStream_t s);
 // one rank's offer in a round of the greedy selection: 88 bytes, the unit of the sharded exchange
-struct SelRecord { unsigned long long key; double H[9]; int err; int mode; };      // mode: bit 0 the rank's residual mode, bit 1 refitted winners (key 30), bit 2 those refits by the 3-point estimator (mh_set_estimator), bits 3-14 the proposer's sampler (capi_select.hip); the ranks' words must agree
+struct SelRecord { unsigned long long key; double H[9]; int err; int mode; };      // mode: bit 0 the rank's residual mode, bit 1 refitted winners (key 30), bit 2 those refits by the 3-point estimator (mh_set_estimator), bits 3-14 the proposer's sampler, bit 15 ranked by MSAC weight: mh_select_greedy_msac (capi_select.hip); the ranks' words must agree
 static_assert(sizeof(SelRecord) == 88, "the exchanged record is 88 bytes");
 hipError_t launch_sel_argmax(const int* counts, const int* orig, int Mc, unsigned int my_off, unsigned long long* key,
                              int* scores_full, hipStream_t s);
@@ -338,6 +338,29 @@ hipError_t launch_sel_refit(const Points& p, const Affines& a, const Epipolar& e
                             int need, const unsigned char* mask, int* labels, double* refit, int* counter, int* label_count,
                             hipStream_t s, int symmetric, int* scratch3 = nullptr);
 hipError_t launch_sel_publish(int* rec, unsigned long long* keys, SelRecord* my_record, int need, int* h_rec_dev, hipStream_t s);
+// The rounds of mh_select_greedy_msac (select.hip, the k_sel_*_w kernels): every candidate has a count AND a weight on the support
+// set; count >= need makes it eligible (and carries it to the next round), the key is weight << 32 | ~position and is built for
+// eligible candidates only.  scores_full: the weight of an eligible candidate, -1 otherwise.  The control words are those of
+// launch_sel_publish except [0] = the winner's weight (-1: nobody eligible) and [6] = the winner's count on the support set.
+hipError_t launch_sel_argmax_w(const int* counts, const int* weights, const int* orig, int Mc, int need, unsigned int my_off,
+                               unsigned long long* key, int* scores_full, hipStream_t s);
+hipError_t launch_sel_record_w(const int* counts, const int* weights, const int* orig, const double* Hs, int Mc, int need,
+                               unsigned int my_off, const unsigned long long* key_local, int err, int mode, SelRecord* record, hipStream_t s);
+hipError_t launch_sel_compact_w(const int* counts, const int* weights, const int* orig, const double* Hs, int Mc, int need,
+                                const SelRecord* records, int world, unsigned int my_off, int* next_orig, double* next_H, int* rec,
+                                int* next_counts, int* next_weights, hipStream_t s);
+hipError_t launch_sel_subtract_w(const int* carried_c, const int* left_c, const int* carried_w, const int* left_w, int Mc, int* counts,
+                                 int* weights, hipStream_t s);
+hipError_t launch_sel_claim_w(const Points& p, const SelRecord* records, int world, const unsigned long long* key_check, double thr2,
+                              unsigned char* mask, int* rec, double* sel_H, long long* sel_counter, int max_models, hipStream_t s,
+                              const double* refit = nullptr, double* cx1 = nullptr, double* cy1 = nullptr, double* cx2 = nullptr,
+                              double* cy2 = nullptr);
+// refit[9] = the refit's WEIGHT on the support set; launch_sel_claim_w takes the refit when it is finite and weighs at least as
+// much as the hypothesis.  sums: two ints (scratch: the refit's weight and count)
+hipError_t launch_sel_refit_w(const Points& p, const Affines& a, const Epipolar& ep, const SelRecord* records, int world, double thr2,
+                              const unsigned char* mask, int* labels, double* refit, int* sums, int* label_count, hipStream_t s,
+                              int* scratch3 = nullptr);
+hipError_t launch_sel_publish_w(int* rec, unsigned long long* keys, SelRecord* my_record, int* h_rec_dev, hipStream_t s);
 hipError_t launch_best_publish(unsigned long long* key, int* h_best_dev, hipStream_t s);
 hipError_t launch_best_fused(int* scores, int world, int longest, int base, int rem, int* h_best_dev, int* clear,
                              int clear_count, hipStream_t s);

@@ -20,6 +20,8 @@
 // After the first round the candidate list is a small fraction of the batch, so later rounds are short.  Keys carry the
 // hypothesis' position in the WHOLE batch (shard offset + local index), so the order of selection — and with it every
 // output, the counters included — is the single-GPU one for any number of ranks.
+// mh_select_greedy_msac runs the same rounds ranked by MSAC weight: its kernels (k_sel_*_w) are at the end of the file.
+#include "../../include/multih_hip.h"
 #include "mh_device.hpp"
 #include "mh_kernels.hpp"
 
@@ -472,6 +474,260 @@ hipError_t launch_pad_scores(const int* counts, int m, int longest, int* scores,
 {
     if (longest <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_pad_scores, dim3((longest + 255) / 256), dim3(256), 0, s, counts, m, longest, scores);
+    return hipGetLastError();
+}
+
+// ---- the selection ranked by MSAC weight (mh_select_greedy_msac, include/multih_hip.h) -------------------------------------
+// The same rounds with two numbers per candidate, its count and its weight on the support set (launch_msac32 / launch_msac64).
+// The count decides who may be selected (count >= need) and who moves on to the next round; the weight decides who wins.
+// The kernels above compare a key's high word with `need`; here the high word is a weight and `need` is a count, so these are
+// kernels of their own: a key is built for ELIGIBLE candidates only (key != 0 is the eligibility; a weight of 0 still makes
+// a key, its low word is never 0), the compaction carries both numbers, the claim counts the winner's inliers itself.
+// k_sel_argmax_gathered, k_sel_winner_labels (with need = 0) and k_sel_pack_points serve this mode unchanged.
+
+// scores_full (nullable): scores_full[orig] = weight of an eligible candidate, -1 otherwise
+__global__ void __launch_bounds__(256)
+k_sel_argmax_w(const int* __restrict__ counts, const int* __restrict__ weights, const int* __restrict__ orig, int Mc, int need,
+               unsigned int my_off, unsigned long long* __restrict__ key, int* __restrict__ scores_full)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    unsigned long long k = 0;
+    if (c < Mc) {
+        const int o = orig ? orig[c] : c;
+        const bool eligible = counts[c] >= need;
+        const int w = weights[c];
+        if (eligible) k = sel_key(w, my_off + (unsigned int)o);
+        if (scores_full) scores_full[o] = eligible ? w : -1;
+    }
+    const unsigned long long b = wg_max_u64(k);
+    if (threadIdx.x == 0 && b) atomicMax(key, b);
+}
+
+__global__ void __launch_bounds__(256)
+k_sel_record_w(const int* __restrict__ counts, const int* __restrict__ weights, const int* __restrict__ orig,
+               const double* __restrict__ Hs, int Mc, int need, unsigned int my_off, const unsigned long long* __restrict__ key_local,
+               int err, int mode, SelRecord* __restrict__ record)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long kl = *key_local;
+    if (c == 0) { record->err = err; record->mode = mode; }
+    if (c >= Mc || !kl) return;
+    const int o = orig ? orig[c] : c;
+    if (counts[c] < need || sel_key(weights[c], my_off + (unsigned int)o) != kl) return;
+    record->key = kl;
+    const double* h = Hs + 9 * (size_t)c;
+    for (int q = 0; q < 9; ++q) record->H[q] = h[q];
+}
+
+// next_counts / next_weights (nullable, key 36): what the candidate counted and weighed on the support set of THIS round
+__global__ void __launch_bounds__(256)
+k_sel_compact_w(const int* __restrict__ counts, const int* __restrict__ weights, const int* __restrict__ orig,
+                const double* __restrict__ Hs, int Mc, int need, const SelRecord* __restrict__ records, int world, unsigned int my_off,
+                int* __restrict__ next_orig, double* __restrict__ next_H, int* __restrict__ rec, int* __restrict__ next_counts,
+                int* __restrict__ next_weights)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long kg = sel_winner(records, world, nullptr);
+    bool keep = false;
+    int o = 0, cnt_c = 0, wgt_c = 0;
+    if (c < Mc) {
+        o = orig ? orig[c] : c;
+        cnt_c = counts[c];
+        wgt_c = weights[c];
+        const bool is_winner = kg && sel_key(wgt_c, my_off + (unsigned int)o) == kg;
+        keep = cnt_c >= need && !is_winner;
+    }
+    __shared__ int s_cnt, s_base;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    int off = 0;
+    if (keep) off = atomicAdd(&s_cnt, 1);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt > 0) s_base = atomicAdd(&rec[2], s_cnt);
+    __syncthreads();
+    if (keep) {
+        const int pos = s_base + off;
+        next_orig[pos] = o;
+        if (next_counts) { next_counts[pos] = cnt_c; next_weights[pos] = wgt_c; }
+        const double* h = Hs + 9 * (size_t)c;
+        for (int q = 0; q < 9; ++q) next_H[9 * (size_t)pos + q] = h[q];
+    }
+}
+
+// rec[0] = the winner's weight (-1: no eligible candidate anywhere), rec[7] += the HYPOTHESIS' inliers in the support set (its
+// count when selected: the record has no room for it, and every rank holds every point), rec[5] += the points that leave —
+// the same points unless a refit claims in the hypothesis' place.  refit[9] = the refit's weight on the support set.
+__global__ void __launch_bounds__(256)
+k_sel_claim_w(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
+              const double* __restrict__ y2, int N, const SelRecord* __restrict__ records, int world,
+              const unsigned long long* __restrict__ key_check, double thr2, unsigned char* __restrict__ mask, int* __restrict__ rec,
+              double* __restrict__ sel_H, long long* __restrict__ sel_counter, int max_models, const double* __restrict__ refit,
+              double* __restrict__ cx1, double* __restrict__ cy1, double* __restrict__ cx2, double* __restrict__ cy2)
+{
+    int wr = 0;
+    const unsigned long long kg = sel_winner(records, world, &wr);
+    const int weight = (int)(kg >> 32);
+    const unsigned int pos = 0xffffffffu - (unsigned int)(kg & 0xffffffffull);
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n == 0) {
+        rec[0] = kg ? weight : -1;
+        rec[1] = (int)pos;
+        int err = 0;
+        for (int r = 0; r < world; ++r) if (records[r].err) err = records[r].err;
+        if (key_check && *key_check != kg) err = 2;
+        for (int r = 1; r < world; ++r) if (records[r].mode != records[0].mode) err = 3;      // (bit 15 too: a rank that ranks by count)
+        if (err) rec[4] = err;
+    }
+    if (!kg) return;
+    const int sel = rec[3];
+    if (sel >= max_models) return;
+    const double* hyp = records[wr].H;
+    const double* h = hyp;
+    // the refit takes the hypothesis' place when it is finite and weighs at least as much on the support set
+    if (refit && refit[9] >= (double)weight) {
+        bool finite = true;
+        for (int q = 0; q < 9; ++q) finite = finite && fabs(refit[q]) < 0x1p1000;
+        if (finite) h = refit;
+    }
+    if (n == 0) {
+        for (int q = 0; q < 9; ++q) sel_H[9 * (size_t)sel + q] = h[q];
+        sel_counter[sel] = (long long)pos;
+    }
+    bool leaves = false, own = false;
+    if (n < N && mask[n]) {
+        leaves = fwd_d2(h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], x1[n], y1[n], x2[n], y2[n]) < thr2;
+        own = leaves;
+        if (h != hyp) own = fwd_d2(hyp[0], hyp[1], hyp[2], hyp[3], hyp[4], hyp[5], hyp[6], hyp[7], hyp[8], x1[n], y1[n], x2[n], y2[n]) < thr2;
+        if (leaves) mask[n] = 0;
+    }
+    const int lane = threadIdx.x & 63;
+    const unsigned long long om = __ballot(own);
+    if (lane == 0 && om) atomicAdd(&rec[7], (int)__popcll(om));
+    const unsigned long long lm = __ballot(leaves);
+    int base = 0;
+    if (lane == 0 && lm) base = atomicAdd(&rec[5], (int)__popcll(lm));
+    base = __shfl(base, 0, 64);
+    if (leaves && cx1) {
+        const int at = base + (int)__popcll(lm & ((1ull << lane) - 1ull));
+        cx1[at] = x1[n]; cy1[at] = y1[n]; cx2[at] = x2[n]; cy2[at] = y2[n];
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_sel_subtract_w(const int* __restrict__ carried_c, const int* __restrict__ left_c, const int* __restrict__ carried_w,
+                 const int* __restrict__ left_w, int Mc, int* __restrict__ counts, int* __restrict__ weights)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < Mc) { counts[c] = carried_c[c] - left_c[c]; weights[c] = carried_w[c] - left_w[c]; }
+}
+
+// sums[0] += the weight, sums[1] += the count of the refit (refit[0..9)) over the points of the support set: k_sel_count with the gain
+__global__ void __launch_bounds__(256)
+k_sel_weigh(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
+            const double* __restrict__ y2, int N, double thr2, const unsigned char* __restrict__ mask, const double* __restrict__ refit,
+            int* __restrict__ sums)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const double* h = refit;
+    bool in = false;
+    int w = 0;
+    if (n < N && mask[n]) {
+        const double d2 = fwd_d2(h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], x1[n], y1[n], x2[n], y2[n]);
+        in = d2 < thr2;
+        w = data_term<false>(d2, thr2, (double)MH_MSAC_SCALE, 0);       // 0 unless d2 < thr2
+    }
+    const unsigned long long m = __ballot(in);
+    if (m == 0ull) return;                                               // wave-uniform
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) w += __shfl_xor(w, o, 64);
+    if ((threadIdx.x & 63) == 0) { atomicAdd(&sums[0], w); atomicAdd(&sums[1], (int)__popcll(m)); }
+}
+
+// (an integer below 2^31 kept in a double: exact, so the claim's comparison with the hypothesis' weight is one line)
+__global__ void k_sel_weigh_finish(const int* __restrict__ sums, double* __restrict__ refit)
+{
+    if (threadIdx.x == 0) refit[9] = (double)sums[0];
+}
+
+__global__ void k_sel_publish_w(int* __restrict__ rec, unsigned long long* __restrict__ keys, SelRecord* __restrict__ my_record,
+                                int* __restrict__ h_rec)
+{
+    if (threadIdx.x != 0) return;
+    h_rec[0] = rec[0]; h_rec[1] = rec[1]; h_rec[2] = rec[2]; h_rec[4] = rec[4]; h_rec[5] = rec[5]; h_rec[6] = rec[7];
+    if (rec[0] >= 0) rec[3] += 1;
+    h_rec[3] = rec[3];
+    rec[2] = 0;
+    rec[5] = 0;
+    rec[7] = 0;
+    keys[0] = 0; keys[1] = 0;
+    my_record->key = 0;
+}
+
+hipError_t launch_sel_argmax_w(const int* counts, const int* weights, const int* orig, int Mc, int need, unsigned int my_off,
+                               unsigned long long* key, int* scores_full, hipStream_t s)
+{
+    if (Mc <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_sel_argmax_w, dim3((Mc + 255) / 256), dim3(256), 0, s, counts, weights, orig, Mc, need, my_off, key, scores_full);
+    return hipGetLastError();
+}
+
+hipError_t launch_sel_record_w(const int* counts, const int* weights, const int* orig, const double* Hs, int Mc, int need,
+                               unsigned int my_off, const unsigned long long* key_local, int err, int mode, SelRecord* record, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sel_record_w, dim3(Mc > 0 ? (Mc + 255) / 256 : 1), dim3(256), 0, s, counts, weights, orig, Hs, Mc, need, my_off,
+                       key_local, err, mode, record);
+    return hipGetLastError();
+}
+
+hipError_t launch_sel_compact_w(const int* counts, const int* weights, const int* orig, const double* Hs, int Mc, int need,
+                                const SelRecord* records, int world, unsigned int my_off, int* next_orig, double* next_H, int* rec,
+                                int* next_counts, int* next_weights, hipStream_t s)
+{
+    if (Mc <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_sel_compact_w, dim3((Mc + 255) / 256), dim3(256), 0, s, counts, weights, orig, Hs, Mc, need, records, world,
+                       my_off, next_orig, next_H, rec, next_counts, next_weights);
+    return hipGetLastError();
+}
+
+hipError_t launch_sel_subtract_w(const int* carried_c, const int* left_c, const int* carried_w, const int* left_w, int Mc, int* counts,
+                                 int* weights, hipStream_t s)
+{
+    if (Mc <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_sel_subtract_w, dim3((Mc + 255) / 256), dim3(256), 0, s, carried_c, left_c, carried_w, left_w, Mc, counts, weights);
+    return hipGetLastError();
+}
+
+hipError_t launch_sel_claim_w(const Points& p, const SelRecord* records, int world, const unsigned long long* key_check, double thr2,
+                              unsigned char* mask, int* rec, double* sel_H, long long* sel_counter, int max_models, hipStream_t s,
+                              const double* refit, double* cx1, double* cy1, double* cx2, double* cy2)
+{
+    hipLaunchKernelGGL(k_sel_claim_w, dim3((p.n + 255) / 256), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, records, world, key_check,
+                       thr2, mask, rec, sel_H, sel_counter, max_models, refit, cx1, cy1, cx2, cy2);
+    return hipGetLastError();
+}
+
+// launch_sel_refit for this mode (forward residual only): the winner's inliers labelled (k_sel_winner_labels with need = 0: a
+// key is an eligible candidate), the same re-estimators, then the refit's WEIGHT into refit[9].  sums: two ints (scratch).
+hipError_t launch_sel_refit_w(const Points& p, const Affines& a, const Epipolar& ep, const SelRecord* records, int world, double thr2,
+                              const unsigned char* mask, int* labels, double* refit, int* sums, int* label_count, hipStream_t s,
+                              int* scratch3)
+{
+    const dim3 grid((p.n + 255) / 256);
+    hipLaunchKernelGGL(k_sel_winner_labels, grid, dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, records, world, thr2, 0, mask,
+                       labels, refit, 0);
+    hipError_t he = scratch3 ? launch_reestimate_3pt(p, labels, 1, ep, refit, label_count, scratch3, s)
+                             : launch_reestimate(p, a, labels, 1, ep, refit, label_count, s);
+    if (he != hipSuccess) return he;
+    he = hipMemsetAsync(sums, 0, sizeof(int) * 2, s);
+    if (he != hipSuccess) return he;
+    hipLaunchKernelGGL(k_sel_weigh, grid, dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, thr2, mask, refit, sums);
+    hipLaunchKernelGGL(k_sel_weigh_finish, dim3(1), dim3(64), 0, s, sums, refit);
+    return hipGetLastError();
+}
+
+hipError_t launch_sel_publish_w(int* rec, unsigned long long* keys, SelRecord* my_record, int* h_rec_dev, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sel_publish_w, dim3(1), dim3(64), 0, s, rec, keys, my_record, h_rec_dev);
     return hipGetLastError();
 }
 

@@ -33,6 +33,8 @@
 #pragma weak mh_score_msac
 #pragma weak mh_select_best_msac
 #pragma weak mh_get_model
+// ... and for the selection ranked by weight (SetSelectionScore): without its entry point that mode fails with a message.
+#pragma weak mh_select_greedy_msac
 
 namespace {
 
@@ -309,6 +311,17 @@ bool MultiH::Run(bool points_only)
     if (tail_score == TAIL_SCORE_MSAC && (!mh_score_msac || !mh_select_best_msac || !mh_get_model)) {
         std::cerr << "Error: the engine library has no MSAC scores (mh_score_msac, mh_select_best_msac, mh_get_model)\n";
         return false;
+    }
+    // how ProposeModels ranks a batch (INIT_STABLE_SETS proposes nothing: the mode is not looked at)
+    if (init_mode != INIT_STABLE_SETS) {
+        if (selection_score != SELECTION_SCORE_COUNT && selection_score != SELECTION_SCORE_MSAC) {
+            std::cerr << "Error: unknown selection score " << selection_score << " (SELECTION_SCORE_COUNT or SELECTION_SCORE_MSAC)\n";
+            return false;
+        }
+        if (selection_score == SELECTION_SCORE_MSAC && !mh_select_greedy_msac) {
+            std::cerr << "Error: the engine library has no selection ranked by MSAC weight (mh_select_greedy_msac)\n";
+            return false;
+        }
     }
     stage("engine");
 
@@ -676,9 +689,14 @@ bool MultiH::ProposeModels(uint64_t seed, long long first, int M, int max_models
     std::vector<double> H(9 * (size_t)max_models);
     int selected = 0;
     if (!Check(mh_set_tuning(engine, 30, proposal_refit ? 1 : 0), "mh_set_tuning(30)")) return false;
-    if (!Check(mh_select_greedy(engine, sqr_threshold_homography, need, max_models, mask.data(), H.data(), nullptr, nullptr,
-                                &selected, (long long)M),
-               "mh_select_greedy"))
+    if (selection_score == SELECTION_SCORE_MSAC && init_mode != INIT_STABLE_SETS) {      // (validated at the head of Process())
+        if (!Check(mh_select_greedy_msac(engine, sqr_threshold_homography, need, max_models, mask.data(), H.data(), nullptr, nullptr,
+                                         nullptr, &selected, (long long)M),
+                   "mh_select_greedy_msac"))
+            return false;
+    } else if (!Check(mh_select_greedy(engine, sqr_threshold_homography, need, max_models, mask.data(), H.data(), nullptr, nullptr,
+                                       &selected, (long long)M),
+                      "mh_select_greedy"))
         return false;
     for (int i = 0; i < selected; ++i) cluster_homographies.push_back(MatFrom9(&H[9 * (size_t)i]));
     return true;
@@ -1063,6 +1081,10 @@ void mhh_set_data_term(int term) { g_data_term = term; }
 static int g_tail_score = -1;
 extern "C" __attribute__((visibility("default")))
 void mhh_set_tail_score(int score) { g_tail_score = score; }
+// MultiH::SetSelectionScore for the next mhh_run_process calls (< 0: the class default)
+static int g_selection_score = -1;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_selection_score(int score) { g_selection_score = score; }
 extern "C" __attribute__((visibility("default")))
 void mhh_get_front_stages(int out[4]) { for (int i = 0; i < 4; ++i) out[i] = g_front_stages[i]; }
 // multih::FilterCorrespondencesByEpipolarGeometry on plain arrays: mask (n flags) out; returns the number kept, -1 on failure
@@ -1139,6 +1161,7 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     if (g_fund_metric >= 0) mh.SetFundamentalMetric(g_fund_metric);
     if (g_data_term >= 0) mh.SetDataTerm(g_data_term);
     if (g_tail_score >= 0) mh.SetTailScore(g_tail_score);
+    if (g_selection_score >= 0) mh.SetSelectionScore(g_selection_score);
     if (g_fund_estimator >= 0) mh.SetFundamentalEstimator(g_fund_estimator, g_fund_max_samples, g_fund_confidence);
     for (const auto& kv : g_tuning) mh.SetEngineTuning(kv.first, kv.second);
     if (g_radius > 0.0 && g_max_hits > 0) { mh.SetNeighbourRadius(g_radius, g_max_hits); if (g_knn > 0) mh.SetFallbackK(g_knn); }

@@ -145,6 +145,13 @@ public:
     // Any other value makes Process() fail with a message.
     enum { TAIL_SCORE_COUNT = 0, TAIL_SCORE_MSAC = 1 };
     void SetTailScore(int t) { tail_score = t; }
+    // How ProposeModels ranks the hypotheses of a batch — the initial batch, the iterative ones and the sharded route alike:
+    // SELECTION_SCORE_COUNT (default) by inlier count (mh_select_greedy), SELECTION_SCORE_MSAC by the MSAC weight among the
+    // hypotheses with at least min_inliers-or-8 inliers (mh_select_greedy_msac, include/multih_hip.h: the count makes a hypothesis
+    // eligible, the fit decides; a refit replaces its hypothesis when it weighs at least as much).  INIT_STABLE_SETS proposes
+    // nothing and ignores it; independent of SetTailScore.  Any other value makes Process() fail with a message.
+    enum { SELECTION_SCORE_COUNT = 0, SELECTION_SCORE_MSAC = 1 };
+    void SetSelectionScore(int s) { selection_score = s; }
     // The sampler of the proposal batches (the initial one and the iterative ones): uniform 4-tuples (default), or
     // neighbourhood-guided ones (mh_set_sampler, MH_SAMPLER_LOCAL): the first index uniform, the other three from its `k`
     // nearest neighbours in (x1, y1, x2, y2), with `uniform_per_16` hypotheses of every 16 left uniform (a homography from a
@@ -246,6 +253,7 @@ protected:
     int estimator = ESTIMATOR_HAF;
     int data_term = DATA_TERM_REFERENCE;
     int tail_score = TAIL_SCORE_COUNT;
+    int selection_score = SELECTION_SCORE_COUNT;
     int proposal_sampler = PROPOSAL_UNIFORM, proposal_sampler_k = 32, proposal_uniform_per_16 = 4;
     bool proposal_local_run = false;      // this Process() call proposes with the local sampler (its table is on the engine)
     bool ApplyProposalSampler(bool local);

@@ -27,6 +27,9 @@
 //                                the reference's dataEnergy (the cost falls as the fit gets worse); rising drops its `1.0 -`
 //                  [--tail-score count|msac]   how the degenerate tail ranks its DLT hypotheses (MultiH::SetTailScore): count, the
 //                                default, by inlier count; msac by the fit-weighted score of mh_score_msac
+//                  [--select-score count|msac]   how the proposal batches are ranked (MultiH::SetSelectionScore): count, the default,
+//                                by inlier count (mh_select_greedy); msac by the MSAC weight among the hypotheses with enough
+//                                inliers (mh_select_greedy_msac)
 //                  [--sampler uniform|local[:k[:u]]]   the sampler of the proposal batches (MultiH::SetProposalSampler): uniform
 //                                4-tuples (default) or neighbourhood-guided ones from the k nearest neighbours (32) with u of
 //                                every 16 hypotheses left uniform (4)
@@ -124,6 +127,7 @@ int main(int argc, char** argv)
     int estimator = MultiH::ESTIMATOR_HAF;
     int data_term = MultiH::DATA_TERM_REFERENCE;
     int tail_score = MultiH::TAIL_SCORE_COUNT;
+    int select_score = MultiH::SELECTION_SCORE_COUNT;
     int sampler = MultiH::PROPOSAL_UNIFORM, sampler_k = 32, sampler_u = 4;
     for (int i = 3; i < argc; ++i) {
         const std::string k = argv[i];
@@ -145,6 +149,11 @@ int main(int argc, char** argv)
             if (std::string(v) == "count") tail_score = MultiH::TAIL_SCORE_COUNT;
             else if (std::string(v) == "msac") tail_score = MultiH::TAIL_SCORE_MSAC;
             else { std::cerr << "--tail-score: count or msac\n"; return 2; }
+        }
+        else if (k == "--select-score") {
+            if (std::string(v) == "count") select_score = MultiH::SELECTION_SCORE_COUNT;
+            else if (std::string(v) == "msac") select_score = MultiH::SELECTION_SCORE_MSAC;
+            else { std::cerr << "--select-score: count or msac\n"; return 2; }
         }
         else if (k == "--sampler") {
             // uniform | local | local:k | local:k:u — whole numbers, nothing behind them
@@ -315,6 +324,7 @@ int main(int argc, char** argv)
     multiH->SetEstimator(estimator);
     multiH->SetDataTerm(data_term);
     multiH->SetTailScore(tail_score);
+    multiH->SetSelectionScore(select_score);
     multiH->SetProposalSampler(sampler, sampler_k, sampler_u);
     const bool processed = points_only ? multiH->Process(srcPointsOrig, dstPointsOrig)
                                        : multiH->Process(srcPointsOrig, dstPointsOrig, origAffines);
