@@ -219,6 +219,38 @@ MH_API int mh_set_sampler(mh_engine* e, int sampler, int uniform_per_16);
  * read.  mh_set_correspondences drops the table.  mh_get_sample_neighbours copies it out (MH_ERR_NOT_SET without one). */
 MH_API int mh_build_sample_neighbours(mh_engine* e, int k);
 MH_API int mh_get_sample_neighbours(mh_engine* e, int* nbr /* n x k, nullable */, int* k_out /* nullable */);
+/* HAF proposals: one hypothesis per affine correspondence, from the reference's own minimal solver (GetHomographyHAF,
+ * M/MultiH.cpp:850-911: a homography from ONE affine correspondence and F), optionally refitted to the anchor's consistent
+ * neighbours (GetHomographyHAFNonminimal's least squares, :913-989, without the rescale of RefineHomographyHAF).  Such a hypothesis
+ * lies on its anchor's plane and is compatible with F by construction, and a batch has n / stride of them.  Fills the engine's
+ * current model set with m hypotheses, replacing it exactly as mh_propose_dlt4 / mh_set_models do: the data cost and the MSAC
+ * weights go stale, mh_get_samples answers as after mh_set_models.  mh_score, mh_score_msac, mh_select_greedy,
+ * mh_select_greedy_msac and mh_select_best work on the batch unchanged.
+ * Hypothesis s has counter c = first + s and anchor i = c * stride.
+ *   1. H0 is what mh_local_homographies writes for row i, the same bits: the six HAF rows r0 .. r5 (four columns) of the
+ *      correspondence; the ten sums of A^T A (pairs a <= b of columns in the order 00 01 02 03 11 12 13 22 23 33), each
+ *      s = r0a * r0b, then s = s + rqa * rqb for q = 1 .. 5; the cyclic Jacobi solve of the symmetric 4 x 4 (csrc/mh_device.hpp,
+ *      jacobi_sym_dev(4)); the column of the smallest eigenvalue, the first index on ties; rows 1-2 of H from e2, F and lambda
+ *      (:984-989); every entry times 1.0 / h33.
+ *   2. members == 0: the hypothesis is H0.
+ *   3. members > 0: for j = 0 .. members - 1, in the order of row i of the sampling table (mh_build_sample_neighbours, its first
+ *      `members` columns), q = nbr[i k + j] is CONSISTENT iff the forward transfer error d2(H0 as stored, q) < thr2 — strictly; a
+ *      NaN is not consistent; always the forward error (M/MultiH.cpp:434-441), whatever mh_set_residual_mode says.
+ *   4. The ten sums start as the anchor's; every consistent q adds its own ten terms, formed like the anchor's, with one
+ *      acc = acc + s each, in ascending j.  Then the same Jacobi solve, column choice, rows and 1.0 / h33 as in step 1.  With no
+ *      consistent neighbour the result is H0, bit for bit.
+ *   5. A result that is not finite stays as it is: it scores 0, as NaN models do everywhere.
+ * stride >= 1, m >= 0, first >= 0, (first + m - 1) * stride < n; members is 0 or in [3, k of the table]; thr2 is not NaN.  m == 0
+ * leaves an empty set, like mh_set_models(NULL, 0).  Affinities or the epipolar geometry missing: MH_ERR_NOT_SET; members > 0
+ * without a table: MH_ERR_NOT_SET; everything else that is wrong: MH_ERR_INVALID.
+ * The counters are global and the table is a function of the correspondences, so rank r of a sharded batch proposes its shard with
+ * first + (its offset into the batch).  The ranks of a sharded selection must agree on "proposed by mh_propose_haf" and on
+ * `members`: the records' mode word carries both (bit 16, bits 17-22; what the RESIDENT batch was proposed with — mh_set_models,
+ * mh_propose_dlt4 and mh_adopt_prefetched clear it), and ranks that disagree all return the mode-mismatch MH_ERR_INVALID. */
+MH_API int mh_propose_haf(mh_engine* e, long long first, int m, int stride, int members, double thr2);
+/* Per hypothesis of the resident batch, the bit mask of its consistent neighbours (bit j = column j of the anchor's table row).
+ * MH_ERR_NOT_SET unless the resident model set came from mh_propose_haf. */
+MH_API int mh_get_haf_support(mh_engine* e, unsigned* used /* m */);
 
 /* ---- score -------------------------------------------------------------- */
 /* Residual definition used by mh_score / mh_residual_matrix / mh_get_residual_rows:
@@ -322,8 +354,9 @@ MH_API int mh_set_transport(mh_engine* e, int rank, int world, mh_allgather_stre
  * nothing, sets the record's error word, and after the exchange every rank leaves the loop — the failing one with its
  * own error, the others with MH_ERR_HIP "a rank reported an error".  Arguments (thr2, need, max_models, total_m) must be
  * the same on every rank, and so must the settings the records' mode word carries: the residual mode, refitted winners and their
- * estimator, the sampler, and (bit 15) whether the rank ranks by count — this entry point — or by weight
- * (mh_select_greedy_msac); ranks that disagree all return MH_ERR_INVALID after the first exchange. */
+ * estimator, the sampler, (bit 15) whether the rank ranks by count — this entry point — or by weight
+ * (mh_select_greedy_msac), and (bit 16, bits 17-22) whether the resident batch is mh_propose_haf's and with how many members;
+ * ranks that disagree all return MH_ERR_INVALID after the first exchange. */
 MH_API int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned char* point_mask,
                             double* H_out, long long* counters_out, int* counts_out, int* selected_out, long long total_m);
 /* The same selection RANKED BY MSAC WEIGHT — a mode beside mh_select_greedy, which is unchanged.  The arguments are those of

@@ -30,7 +30,7 @@ SYMBOLS = [
     "mh_set_neighbors_csr", "mh_build_neighbors_knn", "mh_build_neighbors_knn_radius", "mh_build_neighbors_radius", "mh_get_sym_graph", "mh_set_fundamental_metric", "mh_propose_fund8",
     "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_propose_fund7", "mh_get_fund7_samples", "mh_estimate_fundamental_minimal", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons", "mh_refine_points",
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
-    "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_set_residual_mode", "mh_score", "mh_score_msac", "mh_select_best_msac",
+    "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_propose_haf", "mh_get_haf_support", "mh_set_residual_mode", "mh_score", "mh_score_msac", "mh_select_best_msac",
     "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_select_greedy_msac", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
     "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
     "mh_profile_get", "mh_set_tuning",
@@ -330,6 +330,17 @@ class Engine:
         nbr = np.empty((self.n, k.value), dtype=np.int32)
         self._check(self.lib.mh_get_sample_neighbours(self._h, _p(nbr, C.c_int), None))
         return nbr
+
+    def propose_haf(self, first: int, m: int, stride: int = 1, members: int = 0, thr2: float = 0.0):
+        """mh_propose_haf: m hypotheses, one per affine correspondence (anchors (first + s) * stride), refitted to the consistent
+        ones among the first `members` neighbours of the sampling table (members = 0: the single correspondence)."""
+        self._check(self.lib.mh_propose_haf(self._h, C.c_longlong(int(first)), int(m), int(stride), int(members), C.c_double(thr2)))
+
+    def get_haf_support(self):
+        """mh_get_haf_support: per hypothesis of the resident HAF batch the bit mask of its consistent neighbours (uint32)."""
+        used = np.zeros(self.model_count, dtype=np.uint32)
+        self._check(self.lib.mh_get_haf_support(self._h, _p(used, C.c_uint)))
+        return used
 
     # -- score --------------------------------------------------------------
     def set_residual_mode(self, symmetric: bool):

@@ -407,7 +407,7 @@ void mh_destroy(mh_engine* e)
     if (e->h_batch) (void)hipHostFree(e->h_batch);
     e->knn_tmp.release(); e->knn_part_i.release(); e->knn_part_d.release();
     e->knn_cell.release(); e->knn_count.release(); e->knn_start.release(); e->knn_P.release(); e->knn_orig.release();
-    e->smp_nbr.release();
+    e->smp_nbr.release(); e->haf_used.release();
     for (int c = 0; c < 4; ++c) e->sel_pts[c].release();
     e->sel_pack_count.release();
     for (int c = 0; c < 4; ++c) e->sel_gone[c].release();
@@ -518,7 +518,7 @@ int mh_set_correspondences(mh_engine* e, const double* src_xy, const double* dst
     if (n != e->n) {
         // everything sized by the previous point set is stale: the residual matrix and its pitch, the sampled batch,
         // the fundamental-matrix hypotheses
-        e->m = 0; e->ldr = 0; e->have_samples = false; e->fm = 0; e->f7_m = 0;
+        e->m = 0; e->ldr = 0; e->have_samples = false; e->haf_batch = false; e->fm = 0; e->f7_m = 0;
         e->counts_fresh = false; ++e->models_seq;
     }
     {

@@ -3,6 +3,7 @@
 //   capi.hip          life cycle, parameters, correspondences, neighbourhood graph, buffers, profiling, tuning keys
 //   capi_front.hip    epipolar front half, per-point homographies, mean shift          
 //   capi_score.hip    propose, model sets, score / residual matrix / cost matrix, prefetch queue, inlier read-outs
+//   capi_propose.hip  HAF proposals: a hypothesis per affine correspondence (mh_propose_haf, mh_get_haf_support)
 //   capi_select.hip   transport, greedy selection, best model of a batch (the score exchange)
 //   capi_label.hip    data cost, alpha-expansion, re-estimation, LabelingStep, post-filter statistics
 #pragma once
@@ -86,6 +87,11 @@ struct mh_engine {
     bool have_samples = false;
     DevBuf<double> H, H_one;
     DevBuf<int> samples, counts;
+    // how the resident batch was proposed (mh_propose_haf): mh_set_models, mh_propose_dlt4 and mh_adopt_prefetched clear the record;
+    // the selection records carry it (bit 16 and bits 17-22 of their mode word)
+    bool haf_batch = false;
+    int haf_members = 0;
+    DevBuf<unsigned> haf_used;               // per hypothesis of a HAF batch, the mask of consistent neighbours (mh_get_haf_support)
     DevBuf<double> R;
     long long ldr = 0;
     DevBuf<int> C;                            // mh_cost_matrix

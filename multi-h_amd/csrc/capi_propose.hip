@@ -1,0 +1,55 @@
+// capi_propose.hip: HAF proposals — a hypothesis per affine correspondence as the engine's model set (mh_propose_haf) and the
+// neighbours each of them was refitted to (mh_get_haf_support) — part of the C ABI of include/multih_hip.h (see capi_engine.hpp
+// for the split).  The kernel is csrc/haf_propose.hip.
+#include "capi_engine.hpp"
+
+extern "C" {
+
+int mh_propose_haf(mh_engine* e, long long first, int m, int stride, int members, double thr2)
+{
+    return guarded([&]() -> int {
+    int rc = require_points(e);
+    if (rc) return rc;
+    if (m < 0 || first < 0 || stride < 1) return fail(MH_ERR_INVALID, "mh_propose_haf: m >= 0, first >= 0 and stride >= 1");
+    if (members < 0 || (members > 0 && members < 3) || members > 32) return fail(MH_ERR_INVALID, "mh_propose_haf: members must be 0 or in [3, k of the sampling table]");
+    if (thr2 != thr2) return fail(MH_ERR_INVALID, "mh_propose_haf: thr2 is not a number");
+    if (!e->have_aff) return fail(MH_ERR_NOT_SET, "affinities are not set");
+    if (!e->have_epi) return fail(MH_ERR_NOT_SET, "fundamental matrix / epipole are not set");
+    if (members > 0 && e->smp_k <= 0) return fail(MH_ERR_NOT_SET, "mh_propose_haf with members > 0 needs the sampling table; call mh_build_sample_neighbours");
+    if (members > e->smp_k) return fail(MH_ERR_INVALID, "mh_propose_haf: members exceeds k of the sampling table");
+    // the last anchor (first + m - 1) * stride must be a correspondence: compared by division, nothing can overflow
+    if (m > 0 && first + (long long)m - 1 > (long long)(e->n - 1) / stride) return fail(MH_ERR_INVALID, "mh_propose_haf: (first + m - 1) * stride must be below n");
+    e->counts_fresh = false; ++e->models_seq;
+    e->have_samples = false;
+    e->cost_L = 0;
+    e->m = 0;
+    e->haf_members = members;
+    e->haf_batch = (m == 0);                                   // an empty batch is one already; a full one once its launch is accepted
+    if (m == 0) return MH_OK;                                  // an empty model set, as mh_set_models(NULL, 0) leaves one
+    HIPCHK(e->H.reserve((size_t)m * 9));
+    HIPCHK(e->haf_used.reserve((size_t)m));
+    HIPCHK(reserve_counts(e, (size_t)m + 1));
+    Affines a{ e->a11.p, e->a12.p, e->a21.p, e->a22.p };
+    HIPCHK(launch_haf_propose(e->pts(), a, e->epi, members > 0 ? e->smp_nbr.p : nullptr, e->smp_k, members, thr2, first, m, stride,
+                              e->H.p, e->haf_used.p, e->stream));
+    e->m = m;
+    e->haf_batch = true;
+    return MH_OK;
+    });
+}
+
+int mh_get_haf_support(mh_engine* e, unsigned* used)
+{
+    return guarded([&]() -> int {
+    int rc = enter(e);
+    if (rc) return rc;
+    if (!e->haf_batch) return fail(MH_ERR_NOT_SET, "the resident model set was not proposed by mh_propose_haf");
+    if (e->m <= 0) return MH_OK;
+    if (!used) return fail(MH_ERR_INVALID, "null argument");
+    HIPCHK(hipMemcpyAsync(used, e->haf_used.p, sizeof(unsigned) * (size_t)e->m, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MH_OK;
+    });
+}
+
+} // extern "C"

@@ -90,7 +90,11 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
     const int sampler_bits = e->sampler == MH_SAMPLER_LOCAL ? (8 | (e->smp_k << 4) | (e->sampler_uniform_per_16 << 10)) : 0;
     // ... and so does "ranked by weight" (bit 15): a rank that called the other entry point runs the same collectives, and every
     // rank leaves with the mode-mismatch error
-    const int mode_word = symmetric | (refine ? 2 : 0) | (refine && refit3 ? 4 : 0) | sampler_bits | (by_weight ? 1 << 15 : 0);
+    // ... and how the resident batch was proposed: bit 16 = by mh_propose_haf, bits 17-22 its `members` (0 .. 32).  Zero for every
+    // other batch, so those records are what they were.  A rank that proposed DLT hypotheses beside one that proposed HAF ones
+    // leaves with the others through the same mismatch.
+    const int haf_bits = e->haf_batch ? (1 << 16) | (e->haf_members << 17) : 0;
+    const int mode_word = symmetric | (refine ? 2 : 0) | (refine && refit3 ? 4 : 0) | sampler_bits | (by_weight ? 1 << 15 : 0) | haf_bits;
     if (refine && !refine_usable)
         local_failure(MH_ERR_NOT_SET, std::string(by_weight ? "mh_select_greedy_msac" : "mh_select_greedy") +
                                       (refit3 ? " with refitted winners (mh_set_tuning key 30) needs the epipolar geometry"
@@ -270,7 +274,7 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
         if (e->h_sel[4] != 0)                            // every rank sees the same word, so every rank leaves here
             return fail(e->h_sel[4] == 3 ? MH_ERR_INVALID : MH_ERR_HIP,
                         e->h_sel[4] == 2 ? "greedy selection: the gathered score vector and the ranks' records disagree about the winner"
-                        : e->h_sel[4] == 3 ? "greedy selection: the ranks are not in the same residual mode (mh_set_residual_mode) or do not agree on refitted winners (mh_set_tuning key 30), the estimator (mh_set_estimator), the proposer's sampler (mh_set_sampler) or the selection's score (mh_select_greedy / mh_select_greedy_msac)"
+                        : e->h_sel[4] == 3 ? "greedy selection: the ranks are not in the same residual mode (mh_set_residual_mode) or do not agree on refitted winners (mh_set_tuning key 30), the estimator (mh_set_estimator), the proposer's sampler (mh_set_sampler) or the selection's score (mh_select_greedy / mh_select_greedy_msac), or proposed their shards differently (mh_propose_haf and its members)"
                                            : "greedy selection: a rank reported an error");
         // by count: word 0 is the winner's count; by weight: its weight (-1 when nobody was eligible), its count is word 6
         const int best = e->h_sel[0];

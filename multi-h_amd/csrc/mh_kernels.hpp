@@ -137,6 +137,12 @@ hipError_t launch_haf_point(const Points& p, const Affines& a, const Epipolar& e
                             double* H_out /* n x 9, nullable */, double* feat_out /* n x 10, nullable */,
                             hipStream_t s);
 
+// --- haf_propose.hip: one hypothesis per affine correspondence (mh_propose_haf) ---
+// hypothesis s: anchor (first + s) * stride, the caller has checked the range; nbr: the n x k sampling table (null with
+// members == 0), of which the first `members` columns are read; used_out: per hypothesis the mask of consistent neighbours
+hipError_t launch_haf_propose(const Points& p, const Affines& a, const Epipolar& ep, const int* nbr, int k, int members,
+                              double thr2, long long first, int m, int stride, double* H_out, unsigned* used_out, hipStream_t s);
+
 // --- refine.hip -------------------------------------------------------------
 // points_only: step 1 alone (no affinity is read, a may be null), out is n x 4 (x1 y1 x2 y2) and every triangulated row is kept
 hipError_t launch_refine_points(const Points& p, const Affines& a, const double F[9], const double e1[2],
@@ -313,7 +319,7 @@ hipError_t launch_argmin_labels(const int* cost, int L, int n, int* label, long 
 hipError_t launch_sel_pack_points(const Points& p, const unsigned char* mask, double* cx1, double* cy1, double* cx2, double* cy2,
                                   int* count, hipStream_t s);
 // one rank's offer in a round of the greedy selection: 88 bytes, the unit of the sharded exchange
-struct SelRecord { unsigned long long key; double H[9]; int err; int mode; };      // mode: bit 0 the rank's residual mode, bit 1 refitted winners (key 30), bit 2 those refits by the 3-point estimator (mh_set_estimator), bits 3-14 the proposer's sampler, bit 15 ranked by MSAC weight: mh_select_greedy_msac (capi_select.hip); the ranks' words must agree
+struct SelRecord { unsigned long long key; double H[9]; int err; int mode; };      // mode: bit 0 the rank's residual mode, bit 1 refitted winners (key 30), bit 2 those refits by the 3-point estimator (mh_set_estimator), bits 3-14 the proposer's sampler, bit 15 ranked by MSAC weight: mh_select_greedy_msac, bit 16 the batch is mh_propose_haf's and bits 17-22 its members (capi_select.hip); the ranks' words must agree
 static_assert(sizeof(SelRecord) == 88, "the exchanged record is 88 bytes");
 hipError_t launch_sel_argmax(const int* counts, const int* orig, int Mc, unsigned int my_off, unsigned long long* key,
                              int* scores_full, hipStream_t s);

@@ -35,6 +35,8 @@
 #pragma weak mh_get_model
 // ... and for the selection ranked by weight (SetSelectionScore): without its entry point that mode fails with a message.
 #pragma weak mh_select_greedy_msac
+// ... and for the HAF proposals (SetProposalSource): without its entry point that source fails with a message.
+#pragma weak mh_propose_haf
 
 namespace {
 
@@ -276,6 +278,36 @@ bool MultiH::Run(bool points_only)
         std::cerr << "Error: the stable point sets (INIT_STABLE_SETS) need affinities; the point-only Process() cannot use them\n";
         return false;
     }
+    // where the initial batch comes from (looked at only where a batch is proposed)
+    proposal_haf_run = false;
+    if (initial_homographies.empty() && init_mode != INIT_STABLE_SETS) {
+        if (proposal_source != PROPOSAL_SOURCE_DLT && proposal_source != PROPOSAL_SOURCE_HAF) {
+            std::cerr << "Error: unknown proposal source " << proposal_source << " (PROPOSAL_SOURCE_DLT or PROPOSAL_SOURCE_HAF)\n";
+            return false;
+        }
+        if (proposal_source == PROPOSAL_SOURCE_HAF) {
+            if (points_only) {
+                std::cerr << "Error: HAF proposals (PROPOSAL_SOURCE_HAF) need affinities; the point-only Process() cannot use them\n";
+                return false;
+            }
+            if (!mh_propose_haf) {
+                std::cerr << "Error: the engine library has no HAF proposals (mh_propose_haf)\n";
+                return false;
+            }
+            if (proposal_haf_stride < 1 || proposal_haf_members < 0 || proposal_haf_members == 1 || proposal_haf_members == 2 ||
+                proposal_haf_members > 32) {
+                std::cerr << "Error: SetProposalSource: members = " << proposal_haf_members << ", stride = " << proposal_haf_stride
+                          << " (members 0 or in [3, 32], stride >= 1)\n";
+                return false;
+            }
+            if (proposal_sampler == PROPOSAL_LOCAL && proposal_haf_members > proposal_sampler_k) {
+                std::cerr << "Error: SetProposalSource: members = " << proposal_haf_members << " exceeds k = " << proposal_sampler_k
+                          << " of the local sampler, whose table the HAF proposals share\n";
+                return false;
+            }
+            proposal_haf_run = true;
+        }
+    }
     point_only_run = points_only;
     const bool timing = std::getenv("MULTIH_TIMING") != nullptr;          // diagnostic: where Process() spends its time
     const auto t_process = std::chrono::system_clock::now();
@@ -471,6 +503,26 @@ bool MultiH::Run(bool points_only)
         }
         if (!Check(mh_build_sample_neighbours(engine, k), "mh_build_sample_neighbours")) return false;
         stage("sampling table");
+        if (proposal_haf_run && proposal_haf_members > k) {
+            std::cerr << "Error: SetProposalSource: members = " << proposal_haf_members << " exceeds k = " << k << " of the local sampler's table\n";
+            return false;
+        }
+    }
+    // The HAF proposals' neighbour table: the sampler's when there is one, else built here, once, with k = members.
+    haf_members_run = proposal_haf_run ? proposal_haf_members : 0;
+    if (proposal_haf_run && haf_members_run > 0 && !proposal_local_run) {
+        if (!mh_build_sample_neighbours) {
+            std::cerr << "Error: the engine library has no neighbour table for the HAF proposals (mh_build_sample_neighbours)\n";
+            return false;
+        }
+        const int points = static_cast<int>(src_points.size());          // (at least 8 here, so members stays >= 3)
+        if (haf_members_run > points - 1) {
+            haf_members_run = points - 1;
+            // (said whatever the verbosity, like the sampler's "k reduced": the caller's setting is not what runs)
+            printf("[Multi-H] HAF proposals: members reduced from %d to %d (%d correspondences)\n", proposal_haf_members, haf_members_run, points);
+        }
+        if (!Check(mh_build_sample_neighbours(engine, haf_members_run), "mh_build_sample_neighbours")) return false;
+        stage("HAF neighbour table");
     }
 
     if (!initial_homographies.empty()) {
@@ -653,6 +705,19 @@ bool MultiH::EstablishStablePointSets()
 bool MultiH::ProposeInitialModels()
 {
     std::vector<unsigned char> mask(src_points.size(), 1);
+    if (proposal_haf_run) {
+        // one hypothesis per stride-th refined correspondence: counters 0 .. M - 1, anchors c * stride
+        const int M = (static_cast<int>(src_points.size()) + proposal_haf_stride - 1) / proposal_haf_stride;
+        if (log_to_console || std::getenv("MULTIH_TIMING") != nullptr)      // (part of the stage log too)
+            printf("[Multi-H] HAF proposals: %d hypotheses (members %d, stride %d); SetProposal's count of %d is ignored\n", M, haf_members_run,
+                   proposal_haf_stride, proposal_hypotheses);
+        haf_batch_now = true;
+        const bool ok = ProposeModels(proposal_seed, 0, M, proposal_max_models, mask);
+        haf_batch_now = false;
+        if (ok && log_to_console)
+            printf("[Multi-H] Proposed %d models from %d HAF hypotheses\n", (int)cluster_homographies.size(), M);
+        return ok;
+    }
     const bool ok = ProposeModels(proposal_seed, 0, proposal_hypotheses, proposal_max_models, mask);
     if (ok && log_to_console)
         printf("[Multi-H] Proposed %d models from %d DLT hypotheses\n", (int)cluster_homographies.size(),
@@ -681,7 +746,10 @@ bool MultiH::ProposeModels(uint64_t seed, long long first, int M, int max_models
     const int mine = base + (shard_rank < rem ? 1 : 0);
     const long long off = (long long)shard_rank * base + std::min(shard_rank, rem);
     if (!ApplyProposalSampler(proposal_local_run)) return false;      // (sticky on the engine, and engines are reused)
-    if (mine > 0) {
+    if (haf_batch_now) {      // an empty shard too: mh_propose_haf(.., 0, ..) keeps the batch's record, which every rank's selection compares
+        if (!Check(mh_propose_haf(engine, first + off, mine, proposal_haf_stride, haf_members_run, sqr_threshold_homography), "mh_propose_haf"))
+            return false;
+    } else if (mine > 0) {
         if (!Check(mh_propose_dlt4(engine, seed, first + off, mine), "mh_propose_dlt4")) return false;
     } else if (!Check(mh_set_models(engine, nullptr, 0), "mh_set_models")) {
         return false;
@@ -1051,6 +1119,13 @@ void mhh_set_proposal_sampler(int mode, int k, int uniform_per_16)
 {
     g_proposal_sampler = mode; g_proposal_sampler_k = k; g_proposal_uniform_per_16 = uniform_per_16;
 }
+// MultiH::SetProposalSource for the next mhh_run_process calls (default: DLT)
+static int g_proposal_source = 0, g_proposal_haf_members = 16, g_proposal_haf_stride = 1;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_proposal_source(int source, int members, int stride)
+{
+    g_proposal_source = source; g_proposal_haf_members = members; g_proposal_haf_stride = stride;
+}
 // schedule knobs (mh_set_tuning) for the engines of the next mhh_run_process calls; key < 0 clears the list
 static std::vector<std::pair<int, int>> g_tuning;
 extern "C" __attribute__((visibility("default")))
@@ -1158,6 +1233,7 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     mh.SetCompatibilityCheck(g_post_filter != 0);
     mh.SetProposalRefit(g_proposal_refit != 0);
     if (g_proposal_sampler != 0) mh.SetProposalSampler(g_proposal_sampler, g_proposal_sampler_k, g_proposal_uniform_per_16);
+    if (g_proposal_source != 0) mh.SetProposalSource(g_proposal_source, g_proposal_haf_members, g_proposal_haf_stride);
     if (g_fund_metric >= 0) mh.SetFundamentalMetric(g_fund_metric);
     if (g_data_term >= 0) mh.SetDataTerm(g_data_term);
     if (g_tail_score >= 0) mh.SetTailScore(g_tail_score);

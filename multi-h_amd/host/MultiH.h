@@ -162,6 +162,19 @@ public:
     {
         proposal_sampler = sampler; proposal_sampler_k = k; proposal_uniform_per_16 = uniform_per_16;
     }
+    // Where the INITIAL batch of ProposeModels comes from: PROPOSAL_SOURCE_DLT (default) — `hypotheses` 4-point DLT hypotheses from
+    // sampled tuples — or PROPOSAL_SOURCE_HAF (mh_propose_haf, include/multih_hip.h): one hypothesis per `stride`-th refined
+    // correspondence from its affinity and F (the reference's minimal solver, GetHomographyHAF), refitted to the consistent ones
+    // (within sqr_threshold_homography) among its `members` nearest neighbours; members = 0: the single correspondence.  The batch
+    // has ceil(n / stride) hypotheses — SetProposal's count is ignored, and a log line says so — and is sharded, scored and selected
+    // as a DLT batch is.  With members > 0 Process() builds the neighbour table once; if the local sampler is set as well the table
+    // is the sampler's and members must not exceed its k.  The iterative batches and the degenerate tail stay DLT;
+    // INIT_STABLE_SETS and SetInitialHomographies ignore the source; the point-only Process() refuses it (no affinities).
+    enum { PROPOSAL_SOURCE_DLT = 0, PROPOSAL_SOURCE_HAF = 1 };
+    void SetProposalSource(int source, int members = 16, int stride = 1)
+    {
+        proposal_source = source; proposal_haf_members = members; proposal_haf_stride = stride;
+    }
     // Multi-GPU propose stage (BASELINE configs[3] and [4]): one process per GPU, every rank holds all
     // correspondences and owns a contiguous shard of each hypothesis batch (the hypotheses are a pure function of
     // (seed, counter), so the union over ranks is the single-GPU batch).  In the first greedy round the ranks all-gather
@@ -257,6 +270,10 @@ protected:
     int proposal_sampler = PROPOSAL_UNIFORM, proposal_sampler_k = 32, proposal_uniform_per_16 = 4;
     bool proposal_local_run = false;      // this Process() call proposes with the local sampler (its table is on the engine)
     bool ApplyProposalSampler(bool local);
+    int proposal_source = PROPOSAL_SOURCE_DLT, proposal_haf_members = 16, proposal_haf_stride = 1;
+    bool proposal_haf_run = false;        // this Process() call proposes its initial batch with mh_propose_haf
+    int haf_members_run = 0;              // ... with this many members (reduced where there are fewer correspondences)
+    bool haf_batch_now = false;           // the batch ProposeModels is about to propose is the HAF one
     bool point_only_run = false;                 // the last Process() was the point-only one
     int fixed_iterations = 0;
     int iter_hypotheses = 0, iter_max_new = 4;

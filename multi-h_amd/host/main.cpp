@@ -33,6 +33,9 @@
 //                  [--sampler uniform|local[:k[:u]]]   the sampler of the proposal batches (MultiH::SetProposalSampler): uniform
 //                                4-tuples (default) or neighbourhood-guided ones from the k nearest neighbours (32) with u of
 //                                every 16 hypotheses left uniform (4)
+//                  [--proposals dlt|haf[:members[:stride]]]   where the initial hypotheses come from (MultiH::SetProposalSource): dlt,
+//                                the default, 4-point DLT hypotheses from sampled tuples; haf one hypothesis per `stride`-th affine
+//                                correspondence (1), refitted to its consistent ones among `members` nearest neighbours (16; 0 = none)
 //                  [--ranks N]   one process per GPU (rank r on device r), the hypothesis batches sharded over the ranks and
 //                                exchanged by RCCL (host/rccl_transport.cpp: ncclAllGather on the engine's stream); this
 //                                process becomes rank 0 and starts the others before anything touches the GPU.  Every rank
@@ -112,7 +115,7 @@ int main(int argc, char** argv)
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
                      "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] [--f-estimator ls8|minimal] "
-                     "[--stages file] [--points] [--estimator haf|3pt] [--data-term reference|rising] [--tail-score count|msac] [--sampler uniform|local[:k[:u]]] [--ranks n]\n";
+                     "[--stages file] [--points] [--estimator haf|3pt] [--data-term reference|rising] [--tail-score count|msac] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]] [--ranks n]\n";
         return 2;
     }
     double thrF = 2.6, thrH = 2.2, locality = 0.005, lambda = 0.5;     // M/main.cpp:55-59
@@ -129,6 +132,7 @@ int main(int argc, char** argv)
     int tail_score = MultiH::TAIL_SCORE_COUNT;
     int select_score = MultiH::SELECTION_SCORE_COUNT;
     int sampler = MultiH::PROPOSAL_UNIFORM, sampler_k = 32, sampler_u = 4;
+    int proposals = MultiH::PROPOSAL_SOURCE_DLT, haf_members = 16, haf_stride = 1;
     for (int i = 3; i < argc; ++i) {
         const std::string k = argv[i];
         if (k == "--points") { points_only = true; continue; }      // the one option without a value
@@ -176,6 +180,32 @@ int main(int argc, char** argv)
             }
             else good = false;
             if (!good) { std::cerr << "--sampler " << sv << ": uniform, local, local:k or local:k:u with whole numbers 3 <= k <= 32, 0 <= u <= 16\n"; return 2; }
+        }
+        else if (k == "--proposals") {
+            // dlt | haf | haf:members | haf:members:stride — whole numbers, nothing behind them
+            const std::string sv = v;
+            auto whole = [](const std::string& t, int lo, int hi, int& out) {
+                if (t.empty() || t.size() > 7 || t.find_first_not_of("0123456789") != std::string::npos) return false;
+                out = atoi(t.c_str());
+                return out >= lo && out <= hi;
+            };
+            bool good = true;
+            int mm = 16, ss = 1;
+            if (sv == "dlt") proposals = MultiH::PROPOSAL_SOURCE_DLT;
+            else if (sv.compare(0, 3, "haf") == 0 && (sv.size() == 3 || sv[3] == ':')) {
+                if (sv.size() > 3) {
+                    const std::string rest = sv.substr(4);
+                    const size_t colon = rest.find(':');
+                    good = whole(rest.substr(0, colon), 0, 32, mm) && mm != 1 && mm != 2 &&
+                           (colon == std::string::npos || whole(rest.substr(colon + 1), 1, 1000000, ss));
+                }
+                if (good) { proposals = MultiH::PROPOSAL_SOURCE_HAF; haf_members = mm; haf_stride = ss; }
+            }
+            else good = false;
+            if (!good) {
+                std::cerr << "--proposals " << sv << ": dlt, haf, haf:members or haf:members:stride with whole numbers, members 0 or 3 .. 32, stride >= 1\n";
+                return 2;
+            }
         }
         else if (k == "--thrF") thrF = atof(v);
         else if (k == "--thrH") thrH = atof(v);
@@ -326,6 +356,7 @@ int main(int argc, char** argv)
     multiH->SetTailScore(tail_score);
     multiH->SetSelectionScore(select_score);
     multiH->SetProposalSampler(sampler, sampler_k, sampler_u);
+    multiH->SetProposalSource(proposals, haf_members, haf_stride);
     const bool processed = points_only ? multiH->Process(srcPointsOrig, dstPointsOrig)
                                        : multiH->Process(srcPointsOrig, dstPointsOrig, origAffines);
     if (!processed) { delete multiH; return finish(1); }
