@@ -38,8 +38,9 @@ int exchange(mh_engine* e, const void* send_dev, void* recv_dev, size_t bytes_pe
     return MH_OK;
 }
 
-// The rounds of mh_select_greedy (by_weight = false) and of mh_select_greedy_msac (true; select.hip, the k_sel_*_w kernels): one
-// loop, the same sequence of collectives with the same sizes either way.
+// The rounds of mh_select_greedy (by_weight = false) and of mh_select_greedy_msac (true): one loop over one set of round kernels
+// (select.hip), the same sequence of collectives with the same sizes either way.  by_weight chooses the scorer; the launchers get
+// the weight buffers, or null, and pick their instantiation.
 int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned char* point_mask, double* H_out,
                   long long* counters_out, int* counts_out, int* weights_out, int* selected_out, long long total_m, const bool by_weight)
 {
@@ -102,7 +103,7 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
     if (refine) {
         HIPCHK(e->labels_pts.reserve((size_t)n));
         HIPCHK(e->sel_refit.reserve(10));
-        HIPCHK(e->sel_refit_ctr.reserve(4));
+        HIPCHK(e->sel_refit_ctr.reserve(2));
         if (refit3) HIPCHK(e->r3_scratch.reserve(reestimate_3pt_scratch_ints(n, 1)));
     }
     if (!sharded && M <= 0) local_failure(MH_ERR_NOT_SET, "model set is empty");
@@ -162,6 +163,8 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
         }
     }
     int gone = 0;                                         // points the last claim took out
+    // null = ranked by count: the launchers then touch none of the weights' companions (sel_carried_w, sel_left_w) either
+    int* const weights = by_weight ? e->sel_weights.p : nullptr;
 
     int Mc = M, cur = 0, selected = 0, packed_as = -1;
     bool first = true;
@@ -169,6 +172,9 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
         const double* Hs = first ? e->H.p : e->sel_cand_H[cur].p;
         const int* orig = first ? nullptr : e->sel_orig[cur].p;
         // the rank-local part of a round: score the candidates.  A failure here does not return before the collectives.
+        auto score = [&](const Points& p, int* counts, int* wgts) -> int {
+            return by_weight ? msac_models(e, p, Hs, Mc, thr2, nullptr, counts, wgts) : score_models(e, p, Hs, Mc, thr2, nullptr, counts);
+        };
         auto score_round = [&]() -> int {
             if (e->inject_select_failure > 0 && --e->inject_select_failure == 0)
                 return fail(MH_ERR_HIP, "greedy selection: injected rank-local failure (test hook, mh_set_tuning key 18)");
@@ -178,27 +184,19 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
                 // the candidates' counts of the last round came along with them (k_sel_compact); subtract what left
                 if (gone == 0) {
                     HIPCHK(hipMemcpyAsync(e->sel_counts.p, e->sel_carried[cur].p, sizeof(int) * (size_t)Mc, hipMemcpyDeviceToDevice, s));
-                    if (by_weight) HIPCHK(hipMemcpyAsync(e->sel_weights.p, e->sel_carried_w[cur].p, sizeof(int) * (size_t)Mc, hipMemcpyDeviceToDevice, s));
+                    if (weights) HIPCHK(hipMemcpyAsync(weights, e->sel_carried_w[cur].p, sizeof(int) * (size_t)Mc, hipMemcpyDeviceToDevice, s));
                     return MH_OK;
                 }
                 Points left = e->pts();                       // (same bounding box: a superset's is valid)
                 left.x1 = e->sel_gone[0].p; left.y1 = e->sel_gone[1].p; left.x2 = e->sel_gone[2].p; left.y2 = e->sel_gone[3].p;
                 left.n = gone;
-                const int rcs = by_weight ? msac_models(e, left, Hs, Mc, thr2, nullptr, e->sel_left.p, e->sel_left_w.p)
-                                          : score_models(e, left, Hs, Mc, thr2, nullptr, e->sel_left.p);
+                const int rcs = score(left, e->sel_left.p, e->sel_left_w.p);
                 if (rcs) return rcs;
-                if (by_weight)      // both integer sums are exact: subtracting what left equals counting and weighing again
-                    HIPCHK(launch_sel_subtract_w(e->sel_carried[cur].p, e->sel_left.p, e->sel_carried_w[cur].p, e->sel_left_w.p, Mc,
-                                                 e->sel_counts.p, e->sel_weights.p, s));
-                else
-                    HIPCHK(launch_sel_subtract(e->sel_carried[cur].p, e->sel_left.p, Mc, e->sel_counts.p, s));
+                // (both integer sums are exact: subtracting what left equals counting and weighing again)
+                HIPCHK(launch_sel_subtract(e->sel_carried[cur].p, e->sel_left.p, e->sel_carried_w[cur].p, e->sel_left_w.p, Mc, e->sel_counts.p, weights, s));
                 return MH_OK;
             }
-            auto score = [&](const Points& p) -> int {
-                return by_weight ? msac_models(e, p, Hs, Mc, thr2, nullptr, e->sel_counts.p, e->sel_weights.p)
-                                 : score_models(e, p, Hs, Mc, thr2, nullptr, e->sel_counts.p);
-            };
-            if (active == n) return score(e->pts());     // every point is in the support set: no mask to read
+            if (active == n) return score(e->pts(), e->sel_counts.p, weights);     // every point is in the support set: no mask to read
             if (active > 0) {
                 HIPCHK(launch_sel_pack_points(e->pts(), e->mask.p, e->sel_pts[0].p, e->sel_pts[1].p, e->sel_pts[2].p, e->sel_pts[3].p,
                                               e->sel_pack_count.p, s));
@@ -206,10 +204,10 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
                 Points packed = e->pts();                     // (same bounding box: a superset's is valid)
                 packed.x1 = e->sel_pts[0].p; packed.y1 = e->sel_pts[1].p; packed.x2 = e->sel_pts[2].p; packed.y2 = e->sel_pts[3].p;
                 packed.n = active;
-                return score(packed);
+                return score(packed, e->sel_counts.p, weights);
             }
             HIPCHK(hipMemsetAsync(e->sel_counts.p, 0, sizeof(int) * (size_t)Mc, s));
-            if (by_weight) HIPCHK(hipMemsetAsync(e->sel_weights.p, 0, sizeof(int) * (size_t)Mc, s));
+            if (weights) HIPCHK(hipMemsetAsync(weights, 0, sizeof(int) * (size_t)Mc, s));
             return MH_OK;
         };
         if (local_rc == MH_OK) {
@@ -222,13 +220,8 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
         }
         const int local_err = local_rc != MH_OK ? 1 : 0;
         const bool gather_scores = sharded && first && longest > 0;      // north_star's exchange, once per batch
-        if (by_weight) {
-            HIPCHK(launch_sel_argmax_w(e->sel_counts.p, e->sel_weights.p, orig, Mc, need, my_off, key_local, gather_scores ? e->sel_scores.p : nullptr, s));
-            HIPCHK(launch_sel_record_w(e->sel_counts.p, e->sel_weights.p, orig, Hs, Mc, need, my_off, key_local, local_err, mode_word, my_record, s));
-        } else {
-            HIPCHK(launch_sel_argmax(e->sel_counts.p, orig, Mc, my_off, key_local, gather_scores ? e->sel_scores.p : nullptr, s));
-            HIPCHK(launch_sel_record(e->sel_counts.p, orig, Hs, Mc, my_off, key_local, local_err, mode_word, my_record, s));
-        }
+        HIPCHK(launch_sel_argmax(e->sel_counts.p, weights, orig, Mc, need, my_off, key_local, gather_scores ? e->sel_scores.p : nullptr, s));
+        HIPCHK(launch_sel_record(e->sel_counts.p, weights, orig, Hs, Mc, my_off, key_local, local_err, mode_word, my_record, s));
         if (sharded) {
             if (gather_scores) {
                 rc = exchange(e, e->sel_scores.p, e->sel_gathered.p, sizeof(int) * (size_t)longest, s);
@@ -238,49 +231,34 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
             rc = exchange(e, my_record, records, sizeof(SelRecord), s);     // 88 bytes per rank
             if (rc) return rc;
         }
-        if (by_weight)
-            HIPCHK(launch_sel_compact_w(e->sel_counts.p, e->sel_weights.p, orig, Hs, Mc, need, records, world, my_off, e->sel_orig[cur ^ 1].p,
-                                        e->sel_cand_H[cur ^ 1].p, e->sel_rec.p, decrement ? e->sel_carried[cur ^ 1].p : nullptr,
-                                        decrement ? e->sel_carried_w[cur ^ 1].p : nullptr, s));
-        else
-            HIPCHK(launch_sel_compact(e->sel_counts.p, orig, Hs, Mc, need, records, world, my_off, e->sel_orig[cur ^ 1].p,
-                                      e->sel_cand_H[cur ^ 1].p, e->sel_rec.p, decrement ? e->sel_carried[cur ^ 1].p : nullptr, s));
+        HIPCHK(launch_sel_compact(e->sel_counts.p, weights, orig, Hs, Mc, need, records, world, my_off, e->sel_orig[cur ^ 1].p,
+                                  e->sel_cand_H[cur ^ 1].p, e->sel_rec.p, decrement ? e->sel_carried[cur ^ 1].p : nullptr,
+                                  e->sel_carried_w[cur ^ 1].p, s));
         const double* refit = nullptr;
         if (refine_usable) {
             // every rank holds all the points and the same records: the refit is computed redundantly, identically
             Affines aff{ e->a11.p, e->a12.p, e->a21.p, e->a22.p };
-            if (by_weight)
-                HIPCHK(launch_sel_refit_w(e->pts(), aff, e->epi, records, world, thr2, e->mask.p, e->labels_pts.p, e->sel_refit.p,
-                                          e->sel_refit_ctr.p + 2, e->sel_refit_ctr.p + 1, s, refit3 ? e->r3_scratch.p : nullptr));
-            else
-                HIPCHK(launch_sel_refit(e->pts(), aff, e->epi, records, world, thr2, need, e->mask.p, e->labels_pts.p, e->sel_refit.p,
-                                        e->sel_refit_ctr.p, e->sel_refit_ctr.p + 1, s, symmetric, refit3 ? e->r3_scratch.p : nullptr));
+            HIPCHK(launch_sel_refit(e->pts(), aff, e->epi, records, world, thr2, e->mask.p, e->labels_pts.p, e->sel_refit.p,
+                                    e->sel_refit_ctr.p, e->sel_refit_ctr.p + 1, s, by_weight, symmetric, refit3 ? e->r3_scratch.p : nullptr));
             refit = e->sel_refit.p;
         }
         const unsigned long long* check = gather_scores && !local_err ? key_check : nullptr;
         double* gp[4] = { decrement ? e->sel_gone[0].p : nullptr, decrement ? e->sel_gone[1].p : nullptr,
                           decrement ? e->sel_gone[2].p : nullptr, decrement ? e->sel_gone[3].p : nullptr };
-        if (by_weight) {
-            HIPCHK(launch_sel_claim_w(e->pts(), records, world, check, thr2, e->mask.p, e->sel_rec.p, e->sel_out_H.p, e->sel_counter.p,
-                                      max_models, s, refit, gp[0], gp[1], gp[2], gp[3]));
-            HIPCHK(launch_sel_publish_w(e->sel_rec.p, e->sel_keys.p, my_record, e->h_sel_dev, s));
-        } else {
-            HIPCHK(launch_sel_claim(e->pts(), records, world, check, thr2, need, e->mask.p, e->sel_rec.p,
-                                    e->sel_out_H.p, e->sel_counter.p, max_models, s, symmetric, refit, gp[0], gp[1], gp[2], gp[3]));
-            HIPCHK(launch_sel_publish(e->sel_rec.p, e->sel_keys.p, my_record, need, e->h_sel_dev, s));
-        }
-        HIPCHK(hipStreamSynchronize(s));                 // the control words (six; seven by weight) through mapped memory: no copy
+        HIPCHK(launch_sel_claim(e->pts(), records, world, check, thr2, e->mask.p, e->sel_rec.p, e->sel_out_H.p, e->sel_counter.p,
+                                max_models, s, by_weight, symmetric, refit, gp[0], gp[1], gp[2], gp[3]));
+        HIPCHK(launch_sel_publish(e->sel_rec.p, e->sel_keys.p, my_record, e->h_sel_dev, s));
+        HIPCHK(hipStreamSynchronize(s));                 // the seven control words through mapped memory: no copy
         if (local_rc != MH_OK) return fail(local_rc, local_msg);     // (the others have read this rank's error word by now)
         if (e->h_sel[4] != 0)                            // every rank sees the same word, so every rank leaves here
             return fail(e->h_sel[4] == 3 ? MH_ERR_INVALID : MH_ERR_HIP,
                         e->h_sel[4] == 2 ? "greedy selection: the gathered score vector and the ranks' records disagree about the winner"
                         : e->h_sel[4] == 3 ? "greedy selection: the ranks are not in the same residual mode (mh_set_residual_mode) or do not agree on refitted winners (mh_set_tuning key 30), the estimator (mh_set_estimator), the proposer's sampler (mh_set_sampler) or the selection's score (mh_select_greedy / mh_select_greedy_msac), or proposed their shards differently (mh_propose_haf and its members)"
                                            : "greedy selection: a rank reported an error");
-        // by count: word 0 is the winner's count; by weight: its weight (-1 when nobody was eligible), its count is word 6
-        const int best = e->h_sel[0];
-        if (by_weight ? best < 0 : best < need) break;
-        if (counts_out) counts_out[selected] = by_weight ? e->h_sel[6] : best;
-        if (weights_out) weights_out[selected] = best;
+        // word 0: the winner's rank value (its count, or its weight), -1 when nobody was eligible; word 6: its count
+        if (e->h_sel[0] < 0) break;
+        if (counts_out) counts_out[selected] = e->h_sel[6];
+        if (weights_out) weights_out[selected] = e->h_sel[0];
         ++selected;
         gone = e->h_sel[5];
         active -= gone;                                   // what the claim took out of the support set (the winner's inliers, or its refit's)

@@ -318,56 +318,40 @@ hipError_t launch_argmin_labels(const int* cost, int L, int n, int* label, long 
 // packs the points with mask != 0 into cx1.. (any order); *count = their number
 hipError_t launch_sel_pack_points(const Points& p, const unsigned char* mask, double* cx1, double* cy1, double* cx2, double* cy2,
                                   int* count, hipStream_t s);
-// one rank's offer in a round of the greedy selection: 88 bytes, the unit of the sharded exchange
+// The greedy selection's round (select.hip): one set of kernels for mh_select_greedy and mh_select_greedy_msac.  Every candidate has
+// a count on the support set — count >= need makes it eligible, and carries it to the next round — and a RANK VALUE: that count,
+// or its MSAC weight when `weights` (with its next_ / carried_ / left_ companions) is given; null = ranked by count.  The key
+// rank << 32 | ~position is built for eligible candidates only; the highest key wins.
+// one rank's offer in a round: 88 bytes, the unit of the sharded exchange
 struct SelRecord { unsigned long long key; double H[9]; int err; int mode; };      // mode: bit 0 the rank's residual mode, bit 1 refitted winners (key 30), bit 2 those refits by the 3-point estimator (mh_set_estimator), bits 3-14 the proposer's sampler, bit 15 ranked by MSAC weight: mh_select_greedy_msac, bit 16 the batch is mh_propose_haf's and bits 17-22 its members (capi_select.hip); the ranks' words must agree
 static_assert(sizeof(SelRecord) == 88, "the exchanged record is 88 bytes");
-hipError_t launch_sel_argmax(const int* counts, const int* orig, int Mc, unsigned int my_off, unsigned long long* key,
-                             int* scores_full, hipStream_t s);
+// scores_full (nullable): the first round's vector for the all-gather — the rank value of an eligible candidate, -1 otherwise
+hipError_t launch_sel_argmax(const int* counts, const int* weights, const int* orig, int Mc, int need, unsigned int my_off,
+                             unsigned long long* key, int* scores_full, hipStream_t s);
 hipError_t launch_sel_argmax_gathered(const int* gathered, int world, int longest, int base, int rem, unsigned long long* key,
                                       hipStream_t s);
-hipError_t launch_sel_record(const int* counts, const int* orig, const double* Hs, int Mc, unsigned int my_off,
+hipError_t launch_sel_record(const int* counts, const int* weights, const int* orig, const double* Hs, int Mc, unsigned int my_off,
                              const unsigned long long* key_local, int err, int mode, SelRecord* record, hipStream_t s);
-hipError_t launch_sel_compact(const int* counts, const int* orig, const double* Hs, int Mc, int need, const SelRecord* records,
-                              int world, unsigned int my_off, int* next_orig, double* next_H, int* rec, int* next_counts, hipStream_t s);
-// counts[c] = carried[c] - left[c] (r05: a round of the greedy selection counts its candidates on the points the last claim
-// took away and subtracts, instead of counting them again on everything that is left)
-hipError_t launch_sel_subtract(const int* carried, const int* left, int Mc, int* counts, hipStream_t s);
+// next_counts / next_weights (nullable, key 36): what a kept candidate counted and weighed on this round's support set
+hipError_t launch_sel_compact(const int* counts, const int* weights, const int* orig, const double* Hs, int Mc, int need,
+                              const SelRecord* records, int world, unsigned int my_off, int* next_orig, double* next_H, int* rec,
+                              int* next_counts, int* next_weights, hipStream_t s);
+// counts[c] = carried_c[c] - left_c[c], weights likewise (r05: a round counts its candidates on the points the last claim took
+// away and subtracts, instead of counting them again on everything that is left)
+hipError_t launch_sel_subtract(const int* carried_c, const int* left_c, const int* carried_w, const int* left_w, int Mc, int* counts,
+                               int* weights, hipStream_t s);
+// rec: the seven control words (select.hip); cx1..cy2 (nullable): the points that leave, packed
 hipError_t launch_sel_claim(const Points& p, const SelRecord* records, int world, const unsigned long long* key_check, double thr2,
-                            int need, unsigned char* mask, int* rec, double* sel_H, long long* sel_counter, int max_models,
-                            hipStream_t s, int symmetric = 0, const double* refit = nullptr,
-                            double* cx1 = nullptr, double* cy1 = nullptr, double* cx2 = nullptr, double* cy2 = nullptr /* the points that leave, packed */);
+                            unsigned char* mask, int* rec, double* sel_H, long long* sel_counter, int max_models, hipStream_t s,
+                            bool by_weight, int symmetric, const double* refit, double* cx1, double* cy1, double* cx2, double* cy2);
 // r05 (mh_set_tuning key 30): the round's winner refitted to its inliers in the support set by the per-label HAF least squares
-// (one label); refit = 9 doubles + the refit's inlier count; launch_sel_claim takes it in the winner's place when it is finite and
-// explains at least as many points.  labels: n ints, counter / label_count: one int each (scratch).
+// (one label); refit = 9 doubles + the refit's rank value on the support set; launch_sel_claim takes it in the winner's place when
+// it is finite and that value is at least the hypothesis'.  labels: n ints, sum / label_count: one int each (scratch).
 // scratch3 non-null: the point-only 3-point fit instead (launch_reestimate_3pt, reestimate_3pt_scratch_ints(n, 1) ints; a unused)
 hipError_t launch_sel_refit(const Points& p, const Affines& a, const Epipolar& ep, const SelRecord* records, int world, double thr2,
-                            int need, const unsigned char* mask, int* labels, double* refit, int* counter, int* label_count,
-                            hipStream_t s, int symmetric, int* scratch3 = nullptr);
-hipError_t launch_sel_publish(int* rec, unsigned long long* keys, SelRecord* my_record, int need, int* h_rec_dev, hipStream_t s);
-// The rounds of mh_select_greedy_msac (select.hip, the k_sel_*_w kernels): every candidate has a count AND a weight on the support
-// set; count >= need makes it eligible (and carries it to the next round), the key is weight << 32 | ~position and is built for
-// eligible candidates only.  scores_full: the weight of an eligible candidate, -1 otherwise.  The control words are those of
-// launch_sel_publish except [0] = the winner's weight (-1: nobody eligible) and [6] = the winner's count on the support set.
-hipError_t launch_sel_argmax_w(const int* counts, const int* weights, const int* orig, int Mc, int need, unsigned int my_off,
-                               unsigned long long* key, int* scores_full, hipStream_t s);
-hipError_t launch_sel_record_w(const int* counts, const int* weights, const int* orig, const double* Hs, int Mc, int need,
-                               unsigned int my_off, const unsigned long long* key_local, int err, int mode, SelRecord* record, hipStream_t s);
-hipError_t launch_sel_compact_w(const int* counts, const int* weights, const int* orig, const double* Hs, int Mc, int need,
-                                const SelRecord* records, int world, unsigned int my_off, int* next_orig, double* next_H, int* rec,
-                                int* next_counts, int* next_weights, hipStream_t s);
-hipError_t launch_sel_subtract_w(const int* carried_c, const int* left_c, const int* carried_w, const int* left_w, int Mc, int* counts,
-                                 int* weights, hipStream_t s);
-hipError_t launch_sel_claim_w(const Points& p, const SelRecord* records, int world, const unsigned long long* key_check, double thr2,
-                              unsigned char* mask, int* rec, double* sel_H, long long* sel_counter, int max_models, hipStream_t s,
-                              const double* refit = nullptr, double* cx1 = nullptr, double* cy1 = nullptr, double* cx2 = nullptr,
-                              double* cy2 = nullptr);
-// refit[9] = the refit's WEIGHT on the support set; launch_sel_claim_w takes the refit when it is finite and weighs at least as
-// much as the hypothesis.  sums: two ints (scratch: the refit's weight and count)
-hipError_t launch_sel_refit_w(const Points& p, const Affines& a, const Epipolar& ep, const SelRecord* records, int world, double thr2,
-                              const unsigned char* mask, int* labels, double* refit, int* sums, int* label_count, hipStream_t s,
-                              int* scratch3 = nullptr);
-hipError_t launch_sel_publish_w(int* rec, unsigned long long* keys, SelRecord* my_record, int* h_rec_dev, hipStream_t s);
-hipError_t launch_best_publish(unsigned long long* key, int* h_best_dev, hipStream_t s);
+                            const unsigned char* mask, int* labels, double* refit, int* sum, int* label_count, hipStream_t s,
+                            bool by_weight, int symmetric, int* scratch3);
+hipError_t launch_sel_publish(int* rec, unsigned long long* keys, SelRecord* my_record, int* h_rec_dev, hipStream_t s);
 hipError_t launch_best_fused(int* scores, int world, int longest, int base, int rem, int* h_best_dev, int* clear,
                              int clear_count, hipStream_t s);
 hipError_t launch_pad_scores(const int* counts, int m, int longest, int* scores, hipStream_t s);

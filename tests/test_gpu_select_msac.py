@@ -1,6 +1,8 @@
-"""GPU tests of the greedy selection ranked by MSAC weight (mh_select_greedy_msac; include/multih_hip.h) against the numpy twin
-of tests/select_msac_numpy.py, which tests/test_select_msac_cpu.py pins to the oracle's sequential selection and to known
-answers.  Positions, counts, weights and masks are compared exactly, selected models bit for bit."""
+"""GPU tests of the greedy selection — ranked by MSAC weight (mh_select_greedy_msac; include/multih_hip.h) and, through the same
+round kernels, by count (mh_select_greedy) — against the numpy twin of tests/select_msac_numpy.py, which
+tests/test_select_msac_cpu.py pins to the oracle's sequential selection and to known answers.  Positions, counts, weights (where
+the entry point returns them) and masks are compared exactly, selected models bit for bit."""
+import contextlib
 import ctypes as C
 import json
 import os
@@ -27,11 +29,22 @@ def _holes(n):
     return m
 
 
+RANK_BY = ("count", "weight")
+
+
+def _select(engine, rank_by, *args, **kw):
+    """The mode's entry point, its outputs in the twin's order; mh_select_greedy returns no weights: None in their place."""
+    if rank_by == "weight":
+        return engine.select_greedy_msac(*args, **kw)
+    H, counters, counts, mask = engine.select_greedy(*args, **kw)
+    return H, counters, counts, None, mask
+
+
 def _same(got, want, where):
     H, counters, counts, weights, mask = got
     H_t, idx_t, cnt_t, wgt_t, mask_t = want
     assert np.array_equal(counters, idx_t), where
-    assert np.array_equal(counts, cnt_t) and np.array_equal(weights, wgt_t), where
+    assert np.array_equal(counts, cnt_t) and (weights is None or np.array_equal(weights, wgt_t)), where
     assert np.array_equal(mask, mask_t), where
     assert np.array_equal(H.view(np.uint64), H_t.view(np.uint64)), where
 
@@ -39,37 +52,62 @@ def _same(got, want, where):
 _twin = {}
 
 
-def _case(mh, engine, n, M, holes):
+def _case(mh, engine, n, M, holes, rank_by="weight"):
     """Loads scene n and batch M into the engine; returns (mask, the twin's selection) — the twin runs once per case."""
     sc = mh.synth.make_scene(n, 2 if n < 1000 else 3, seed=n, with_neighbours=False)
     engine.set_correspondences(sc.src, sc.dst, sc.aff)
     engine.propose_dlt4(n + M, 0, M)
     mask = _holes(n) if holes else np.ones(n, np.uint8)
-    key = (n, M, holes)
+    key = (n, M, holes, rank_by)
     if key not in _twin:
-        _twin[key] = T.select_greedy(sc.src, sc.dst, engine.get_models(), THR2, NEED, MAX_MODELS, mask)
+        _twin[key] = T.select_greedy(sc.src, sc.dst, engine.get_models(), THR2, NEED, MAX_MODELS, mask, rank_by=rank_by)
     return mask, _twin[key]
 
 
-@pytest.mark.parametrize("holes", [False, True])
-@pytest.mark.parametrize("key15", [1, 0])
-@pytest.mark.parametrize("key36", [1, 0])
-def test_parity_with_the_twin(mh, engine, key36, key15, holes):
+def _parity(mh, engine, rank_by, key36, key15, holes):
     engine.set_tuning(36, key36)
     engine.set_tuning(15, key15)
     rounds = 0
     for n in (257, 1000, 4099):
         for M in (300, 3001):
-            mask, want = _case(mh, engine, n, M, holes)
-            got = engine.select_greedy_msac(THR2, NEED, MAX_MODELS, mask)
-            _same(got, want, (key36, key15, holes, n, M))
+            mask, want = _case(mh, engine, n, M, holes, rank_by)
+            got = _select(engine, rank_by, THR2, NEED, MAX_MODELS, mask)
+            _same(got, want, (rank_by, key36, key15, holes, n, M))
             assert np.array_equal(got[0].view(np.uint64), engine.get_models()[got[1]].view(np.uint64)), "H_out: the batch's rows"
             # without a mask: all points
             if not holes:
-                H2, c2, n2, w2, m2 = engine.select_greedy_msac(THR2, NEED, MAX_MODELS)
-                assert m2 is None and np.array_equal(c2, want[1]) and np.array_equal(w2, want[3]) and np.array_equal(n2, want[2])
+                H2, c2, n2, w2, m2 = _select(engine, rank_by, THR2, NEED, MAX_MODELS)
+                assert m2 is None and np.array_equal(c2, want[1]) and np.array_equal(n2, want[2])
+                assert w2 is None or np.array_equal(w2, want[3])
             rounds += len(got[1])
     assert rounds >= 6 * 2, "the scenes must take several rounds"
+
+
+def _grid(test):
+    for name, values in (("key36", [1, 0]), ("key15", [1, 0]), ("holes", [False, True])):
+        test = pytest.mark.parametrize(name, values)(test)
+    return test
+
+
+@_grid
+def test_parity_with_the_twin(mh, engine, key36, key15, holes):
+    _parity(mh, engine, "weight", key36, key15, holes)
+
+
+@_grid
+def test_parity_with_the_twin_by_count(mh, engine, key36, key15, holes):
+    """The same shapes through mh_select_greedy.  At n = 4099 the two modes pick differently."""
+    _parity(mh, engine, "count", key36, key15, holes)
+
+
+@pytest.mark.parametrize("key36", [1, 0])
+@pytest.mark.parametrize("rank_by", RANK_BY)
+def test_batch_sizes_at_the_compaction_workgroup_edge(mh, engine, rank_by, key36):
+    """One workgroup of the compaction holds 256 candidates: a batch one short of it, exactly it, one more."""
+    engine.set_tuning(36, key36)
+    for M in (255, 256, 257):
+        mask, want = _case(mh, engine, 257, M, False, rank_by)
+        _same(_select(engine, rank_by, THR2, NEED, MAX_MODELS, mask), want, (rank_by, key36, M))
 
 
 def test_count_and_weight_differ_where_they_should(engine):
@@ -84,6 +122,43 @@ def test_count_and_weight_differ_where_they_should(engine):
         assert got[1].tolist() == by_weight
         _same(got, T.select_greedy(src, dst, H, THR2, need, 8), need)
     assert got[2].tolist() == [40] and got[4].sum() == 30          # need = 35: the tight model is never eligible
+
+
+@pytest.mark.parametrize("rank_by", RANK_BY)
+def test_hand_built_sets_in_both_modes(engine, rank_by):
+    """The eligibility rule at its edges: count == need is eligible, need - 1 is not; nobody eligible selects nothing and
+    leaves the mask as it came; an empty support set; one model only; a tie; a winner of weight 0."""
+    src, dst, H = T.tight_and_sloppy(THR2)
+    engine.set_correspondences(src, dst)
+    ones = np.ones(70, np.uint8)
+
+    def run(need, max_models=8, mask=None):
+        mask = ones if mask is None else mask
+        engine.set_models(H)
+        got = _select(engine, rank_by, THR2, need, max_models, mask)
+        _same(got, T.select_greedy(src, dst, H, THR2, need, max_models, mask, rank_by=rank_by), (rank_by, need, max_models))
+        return got
+
+    got = run(30)
+    assert got[1].tolist() == ([0, 1] if rank_by == "count" else [1, 0])
+    assert got[2].tolist() == ([40, 30] if rank_by == "count" else [30, 40])
+    for need in (31, 40):
+        got = run(need)
+        assert got[1].tolist() == [0] and got[2].tolist() == [40] and got[4].sum() == 30
+    got = run(41)
+    assert len(got[1]) == 0 and got[0].shape == (0, 9) and np.array_equal(got[4], ones)
+    assert run(20, max_models=1)[1].tolist() == ([0] if rank_by == "count" else [1])
+    got = run(20, mask=np.zeros(70, np.uint8))
+    assert len(got[1]) == 0 and not got[4].any()
+    src, dst, H = T.tie(THR2)
+    engine.set_correspondences(src, dst)
+    ones = np.ones(40, np.uint8)
+    assert run(NEED)[1].tolist() == [3]
+    src, dst, H = T.weight_zero(THR2)
+    engine.set_correspondences(src, dst)
+    ones = np.ones(25, np.uint8)
+    got = run(NEED)
+    assert got[1].tolist() == [1] and got[2].tolist() == [25]
 
 
 def test_ties_go_to_the_lowest_position(engine):
@@ -188,7 +263,8 @@ def test_refusals(mh, engine):
     assert engine.profile_get(2)[0] == launches
 
 
-def test_a_one_rank_transport_gives_the_unsharded_outputs(mh, engine):
+@contextlib.contextmanager
+def _one_rank_comm(mh, engine):
     """The pattern of tests/test_gpu_pipeline.py: RCCL's ncclAllGather on a one-rank communicator runs the whole protocol."""
     rl = C.CDLL(os.path.join(os.path.dirname(mh.LIB_PATH), "libmultih_rccl.so"))
     rl.mhr_last_error.restype = C.c_char_p
@@ -198,6 +274,14 @@ def test_a_one_rank_transport_gives_the_unsharded_outputs(mh, engine):
     comm = C.c_void_p()
     assert rl.mhr_init(C.byref(comm), 0, 1, uid, 0) == 0, rl.mhr_last_error()
     try:
+        yield rl, comm
+    finally:
+        engine.set_transport(0, 1)
+        rl.mhr_destroy(comm)
+
+
+def test_a_one_rank_transport_gives_the_unsharded_outputs(mh, engine):
+    with _one_rank_comm(mh, engine) as (rl, comm):
         sc = mh.synth.make_scene(4000, 4, seed=31, with_neighbours=False)
         engine.set_correspondences(sc.src, sc.dst, sc.aff)
         engine.propose_dlt4(77, 0, 3001)
@@ -212,9 +296,21 @@ def test_a_one_rank_transport_gives_the_unsharded_outputs(mh, engine):
         assert len(plain[1]) >= 4
         rounds = len(via[1]) + (1 if len(via[1]) < MAX_MODELS else 0)
         assert used == rounds + 1, "one record per round and the first round's score vector: mh_select_greedy's collectives"
-    finally:
-        engine.set_transport(0, 1)
-        rl.mhr_destroy(comm)
+
+
+@pytest.mark.parametrize("rank_by", RANK_BY)
+def test_nobody_eligible_behind_a_transport(mh, engine, rank_by):
+    """No candidate reaches `need`: no key on any rank, -1 throughout the gathered vector; zero models and no error."""
+    src, dst, H = T.tight_and_sloppy(THR2)
+    ones = np.ones(70, np.uint8)
+    with _one_rank_comm(mh, engine) as (rl, comm):
+        engine.set_correspondences(src, dst)
+        engine.set_models(H)
+        engine.set_transport(0, 1, stream_fn=rl.mhr_allgather, ctx=comm)
+        calls = rl.mhr_calls(comm)
+        got = _select(engine, rank_by, THR2, 41, 8, ones, total_m=2)
+        assert rl.mhr_calls(comm) - calls == 2, "the first round's score vector and its record"
+        assert len(got[1]) == 0 and np.array_equal(got[4], ones)
 
 
 def _free_port():

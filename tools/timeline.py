@@ -19,7 +19,7 @@ steps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 
 
 def short(n):
-    for k in ("k_residual", "k_dlt4", "k_sel_argmax_gathered", "k_sel_argmax", "k_best_publish", "k_best_fused", "k_pad_scores", "ncclDevKernel", "fillBuffer", "k_model32", "COPY"):
+    for k in ("k_residual", "k_dlt4", "k_sel_argmax_gathered", "k_sel_argmax", "k_best_fused", "k_pad_scores", "ncclDevKernel", "fillBuffer", "k_model32", "COPY"):
         if k in n:
             return n[:28] if k == "COPY" else k
     return n[:40]
