@@ -265,7 +265,7 @@ struct mh_engine {
     ExpandStats last_expand{};
 
     double bbox[4] = { NAN, NAN, NAN, NAN };   // xmin xmax ymin ymax of the source points
-    // FP32 pre-test of the score kernels (score32.hip): usable when every coordinate is finite and below 2^20
+    // FP32 pre-test of the score kernels (pretest32.hpp): usable when every coordinate is finite and below 2^20
     bool coords32_ok = false;
     double absmax_x = NAN, absmax_y = NAN, absmax_dst = NAN;
     int tune_score32_tiling = 0;               // key 16: points per lane / models per workgroup of the pre-test kernel (schedule only)
@@ -331,10 +331,11 @@ int quiesce(mh_engine* e);
 int join_xchg(mh_engine* e);
 // inlier counts of m models over the points p: FP32 pre-test where its preconditions hold, the FP64 sweep otherwise (capi_score.hip)
 int score_models(mh_engine* e, const Points& p, const double* Hs, int m, double thr2, const unsigned char* dmask, int* counts_dev);
-// the score_models of the selection ranked by weight: counts and MSAC weights, k_msac32 behind the pre-test where score_models'
-// preconditions hold, k_msac64 otherwise (capi_score.hip).  Forward residual; the caller has checked 256 n against int32.
+// counts and MSAC weights, k_msac32 behind the pre-test where it is usable, k_msac64 otherwise (capi_score.hip).  Forward
+// residual; the caller has checked 256 n against int32.  plain_variant_only: true for the selection ranked by weight, which
+// follows score_models' preconditions to the letter; false for mh_score_msac (pretest_usable, capi_score.hip).
 int msac_models(mh_engine* e, const Points& p, const double* Hs, int m, double thr2, const unsigned char* dmask, int* counts_dev,
-                int* weights_dev);
+                int* weights_dev, bool plain_variant_only);
 // the engine's re-estimator over labels_dev (n ints) for models H_dev (Nh x 9, in place) — HAF or 3-point (capi_label.hip)
 int launch_estimator(mh_engine* e, const int* labels_dev, int Nh, double* H_dev, int* counts_dev);
 // the exchange's stream and events (capi_select.hip); the second stream of the prefetch queue (capi_score.hip)

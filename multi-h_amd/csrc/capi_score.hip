@@ -3,22 +3,40 @@
 
 namespace mhe {
 
+// May the FP32 pre-test (pretest32.hpp) decide pairs at this threshold?  Key 15, every coordinate finite and below 2^20,
+// thr2 in [2^-40, 2^40].  plain_variant_only: score_models and msac_models — what the selections call — also step aside for a
+// measurement variant of the FP64 score kernel (key 1); mh_score_msac and mh_cost_matrix never have.  (An asymmetry kept
+// as found.)
+static bool pretest_usable(const mh_engine* e, double thr2, bool plain_variant_only)
+{
+    if (plain_variant_only && e->tune_score_variant != 0) return false;
+    return e->tune_score32 && e->coords32_ok && thr2 >= 0x1p-40 && thr2 <= 0x1p40;
+}
+
+// the two control words of a resident grid (the launch itself leaves them zero again)
+static int ensure_sweep_ctl(mh_engine* e)
+{
+    if (!e->sweep_ctl.p) {
+        HIPCHK(e->sweep_ctl.reserve(2));
+        HIPCHK(hipMemsetAsync(e->sweep_ctl.p, 0, sizeof(int) * 2, e->stream));
+    }
+    return MH_OK;
+}
+
 // Inlier counts of `m` models (device array Hs) over the points `p`: the FP32 pre-test kernel where its preconditions
 // hold (forward residual, bounded coordinates), the FP64 sweep otherwise.  Same counts either way.
 int score_models(mh_engine* e, const Points& p, const double* Hs, int m, double thr2, const unsigned char* dmask, int* counts_dev)
 {
     const bool fwd = e->residual_mode != MH_RESIDUAL_SYMMETRIC;
-    if (fwd && e->tune_score32 && e->tune_score_variant == 0 && e->coords32_ok && m > 0 && thr2 >= 0x1p-40 && thr2 <= 0x1p40) {
+    if (fwd && m > 0 && pretest_usable(e, thr2, true)) {
         HIPCHK(e->H32.reserve((size_t)m * 16));
         HIPCHK(e->fb_pairs.reserve(1));
         if (e->score_pairs == 0) HIPCHK(hipMemsetAsync(e->fb_pairs.p, 0, sizeof(unsigned long long), e->stream));
         HIPCHK(launch_model32(Hs, m, e->absmax_x, e->absmax_y, e->absmax_dst, e->H32.p, e->stream));
         int* ctl = nullptr;
         if (e->tune_score32_resident != 0) {
-            if (!e->sweep_ctl.p) {
-                HIPCHK(e->sweep_ctl.reserve(2));
-                HIPCHK(hipMemsetAsync(e->sweep_ctl.p, 0, sizeof(int) * 2, e->stream));
-            }
+            int rc = ensure_sweep_ctl(e);
+            if (rc) return rc;
             ctl = e->sweep_ctl.p;
         }
         HIPCHK(launch_score32(p, Hs, e->H32.p, m, thr2, e->absmax_dst, dmask, counts_dev, e->fb_pairs.p, e->tune_score32_tiling, e->stream,
@@ -30,16 +48,17 @@ int score_models(mh_engine* e, const Points& p, const double* Hs, int m, double 
     return MH_OK;
 }
 
-// Counts and MSAC weights of `m` models (device array Hs) over the points `p` — mh_score_msac's two forms for an arbitrary
-// candidate list and point set (the rounds of mh_select_greedy_msac): the H32 table is rebuilt for these models, the pairs go
-// into the statistics of mh_get_score_stats as there.
+// Counts and MSAC weights of `m` models (device array Hs) over the points `p` — mh_score_msac's two forms, for the engine's
+// own batch (plain_variant_only = false) and for an arbitrary candidate list and point set (the rounds of
+// mh_select_greedy_msac, true: see pretest_usable): the H32 table is rebuilt for these models, the pairs go into the
+// statistics of mh_get_score_stats.
 int msac_models(mh_engine* e, const Points& p, const double* Hs, int m, double thr2, const unsigned char* dmask, int* counts_dev,
-                int* weights_dev)
+                int* weights_dev, bool plain_variant_only)
 {
     if (m <= 0 || p.n <= 0) return MH_OK;
     HIPCHK(e->fb_pairs.reserve(1));        // (both forms add to score_pairs, which decides when the device counter is cleared)
     if (e->score_pairs == 0) HIPCHK(hipMemsetAsync(e->fb_pairs.p, 0, sizeof(unsigned long long), e->stream));
-    if (e->tune_score32 && e->tune_score_variant == 0 && e->coords32_ok && thr2 >= 0x1p-40 && thr2 <= 0x1p40) {
+    if (pretest_usable(e, thr2, plain_variant_only)) {
         HIPCHK(e->H32.reserve((size_t)m * 16));
         HIPCHK(launch_model32(Hs, m, e->absmax_x, e->absmax_y, e->absmax_dst, e->H32.p, e->stream));
         HIPCHK(launch_msac32(p, Hs, e->H32.p, m, thr2, e->absmax_dst, dmask, counts_dev, weights_dev, e->fb_pairs.p, e->stream));
@@ -236,18 +255,8 @@ int mh_score_msac(mh_engine* e, double thr2, const unsigned char* point_mask, in
     e->weights_models_seq = -1;
     {
         ScopedTimer t(e, MH_K_SCORE);
-        // the form: score_models' preconditions for the FP32 pre-test (key 15, bounded coordinates, thr2 in [2^-40, 2^40])
-        HIPCHK(e->fb_pairs.reserve(1));        // (both forms add to score_pairs, which decides when the device counter is cleared)
-        if (e->score_pairs == 0) HIPCHK(hipMemsetAsync(e->fb_pairs.p, 0, sizeof(unsigned long long), e->stream));
-        if (e->tune_score32 && e->coords32_ok && thr2 >= 0x1p-40 && thr2 <= 0x1p40) {
-            HIPCHK(e->H32.reserve((size_t)e->m * 16));
-            HIPCHK(launch_model32(e->H.p, e->m, e->absmax_x, e->absmax_y, e->absmax_dst, e->H32.p, e->stream));
-            HIPCHK(launch_msac32(e->pts(), e->H.p, e->H32.p, e->m, thr2, e->absmax_dst, dmask, e->counts.p, e->weights.p, e->fb_pairs.p, e->stream));
-        } else {
-            HIPCHK(launch_msac64(e->pts(), e->H.p, e->m, thr2, dmask, e->counts.p, e->weights.p, e->stream));
-            e->score_pairs_plain_fp64 += (long long)e->m * e->n;
-        }
-        e->score_pairs += (long long)e->m * e->n;
+        rc = msac_models(e, e->pts(), e->H.p, e->m, thr2, dmask, e->counts.p, e->weights.p, false);
+        if (rc) return rc;
     }
     // mh_select_best_msac reports the winner's count too, and the counts buffer may be handed to an exchange before it is asked
     HIPCHK(hipMemcpyAsync(e->weights_counts.p, e->counts.p, sizeof(int) * (size_t)e->m, hipMemcpyDeviceToDevice, e->stream));
@@ -289,9 +298,9 @@ int mh_residual_matrix(mh_engine* e, double thr2, double* R_host, int* counts)
         const int headroom = e->tune_sweep_headroom > 0 ? e->tune_sweep_headroom : (e->t_stream_fn && e->t_world > 1 ? 32 : 0);
         resident = e->sweep_wg_per_cu * e->cu_count - headroom;
         if (resident < e->cu_count) resident = 0;
-        if (resident > 0 && !e->sweep_ctl.p) {
-            HIPCHK(e->sweep_ctl.reserve(2));
-            HIPCHK(hipMemsetAsync(e->sweep_ctl.p, 0, sizeof(int) * 2, e->stream));
+        if (resident > 0) {
+            rc = ensure_sweep_ctl(e);
+            if (rc) return rc;
         }
     }
     // ... and it starts behind the DLT's dispatch, not beside it: a sweep that reaches the chip first fills every
@@ -335,15 +344,13 @@ int mh_cost_matrix(mh_engine* e, int* C_host, int* counts)
     {
         ScopedTimer t(e, MH_K_COSTMATRIX);
         const double thr2 = e->thr_H * e->thr_H;
-        if (e->tune_score32 && e->coords32_ok && thr2 >= 0x1p-40 && thr2 <= 0x1p40) {      // the FP32 pre-test (score32.hip); same matrix
+        if (pretest_usable(e, thr2, false)) {      // the FP32 pre-test (k_cost32, score32.hip); same matrix
             HIPCHK(e->H32.reserve((size_t)e->m * 16));
             HIPCHK(launch_model32(e->H.p, e->m, e->absmax_x, e->absmax_y, e->absmax_dst, e->H32.p, e->stream));
             int* ctl = nullptr;
             if (e->tune_cost32_resident != 0) {
-                if (!e->sweep_ctl.p) {
-                    HIPCHK(e->sweep_ctl.reserve(2));
-                    HIPCHK(hipMemsetAsync(e->sweep_ctl.p, 0, sizeof(int) * 2, e->stream));
-                }
+                rc = ensure_sweep_ctl(e);
+                if (rc) return rc;
                 ctl = e->sweep_ctl.p;
             }
             HIPCHK(launch_cost32(e->pts(), e->H.p, e->H32.p, e->m, e->lambda, thr2, e->absmax_dst, e->C.p, e->ldc, e->counts.p, e->stream,

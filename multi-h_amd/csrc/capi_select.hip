@@ -173,7 +173,7 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
         const int* orig = first ? nullptr : e->sel_orig[cur].p;
         // the rank-local part of a round: score the candidates.  A failure here does not return before the collectives.
         auto score = [&](const Points& p, int* counts, int* wgts) -> int {
-            return by_weight ? msac_models(e, p, Hs, Mc, thr2, nullptr, counts, wgts) : score_models(e, p, Hs, Mc, thr2, nullptr, counts);
+            return by_weight ? msac_models(e, p, Hs, Mc, thr2, nullptr, counts, wgts, true) : score_models(e, p, Hs, Mc, thr2, nullptr, counts);
         };
         auto score_round = [&]() -> int {
             if (e->inject_select_failure > 0 && --e->inject_select_failure == 0)

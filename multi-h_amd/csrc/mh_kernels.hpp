@@ -51,7 +51,7 @@ hipError_t launch_residual(const Points& p, const double* H, int M, double thr2,
 int residual_workgroups_per_cu();
 hipError_t launch_score(const Points& p, const double* H, int M, double thr2,
                         const unsigned char* mask, int* counts, int variant, hipStream_t s);
-// --- score32.hip: the same counts through an FP32 pre-test with a rigorous error bound (FP64 only for the pairs it cannot decide)
+// --- score32.hip: the same counts through an FP32 pre-test with a rigorous error bound (pretest32.hpp; FP64 only for the pairs it cannot decide)
 hipError_t launch_model32(const double* H, int M, double X, double Y, double Cmax, float* H32 /* M x 16 */, hipStream_t s);
 // Cmax: the bound on |x2|, |y2| the table was made with; thr2 in [2^-40, 2^40]
 hipError_t launch_score32(const Points& p, const double* H, const float* H32, int M, double thr2, double Cmax, const unsigned char* mask,
@@ -62,7 +62,7 @@ hipError_t launch_cost32(const Points& p, const double* H, const float* H32, int
                          int* C, long long ldc, int* counts, hipStream_t s, int* resident_ctl = nullptr, int cu_count = 256,
                          int psplit_override = 0, int slice_major = 0, int batched = 0, int* occ_cache = nullptr, int rising = 0);
 // --- msac32.hip: per model the inlier count AND the sum of the inliers' MSAC gains (include/multih_hip.h, mh_score_msac) —
-// launch_msac32 behind score32.hip's pre-test (same H32 / Cmax / thr2 preconditions as launch_score32; fp64_pairs, nullable:
+// launch_msac32 behind the same pre-test (same H32 / Cmax / thr2 preconditions as launch_score32; fp64_pairs, nullable:
 // device counter of the pairs that went through the FP64 formula), launch_msac64 with every pair in FP64
 hipError_t launch_msac32(const Points& p, const double* H, const float* H32, int M, double thr2, double Cmax, const unsigned char* mask,
                          int* counts, int* weights, unsigned long long* fp64_pairs, hipStream_t s);

@@ -1,67 +1,8 @@
-// score32.hip — inlier scoring with an FP32 pre-test, gfx950.  Counts are the reference's, bit for bit.
-//
-// A score needs, per (point, model) pair, only the DECISION  d2 < thr^2  of the reference's FP64 formula
-// (M/MultiH.cpp:434-443), never d2 itself.  This kernel evaluates the forward transfer error in FP32 (fused
-// multiply-adds, hardware reciprocal: about a third of the FP64 sweep's issue cycles per pair) together with a RIGOROUS
-// bound B on |d2_fp32 - d2_fp64|, decides the pairs for which the bound leaves no doubt
-//         d2_fp32 + B <  thr^2   ->  inlier            d2_fp32 - B >= thr^2   ->  not an inlier
-// (evaluated as |d2_fp32 - thr^2| > B with the sign of the difference telling which)
-// and recomputes the others — pairs within B of the threshold, pairs near a model's horizon, anything that produced a
-// NaN or an infinity on the way — with the FP64 formula in the reference's own operation order.  The result is the count
-// the FP64 kernel (residual.hip) gives; the tests compare the two and put thresholds exactly ON residual values.
-//
-// The bound.  u = 2^-24.  Inputs are rounded to FP32 (relative error u each).  With X, Y = max |x|, |y| over all source
-// points, per MODEL (k_model32, in FP64, rounded up):
-//     E_s = 5u (|h6| X + |h7| Y + |h8|)          bounds |s_fp32 - s|   (two fmas on rounded inputs: (1+u)^4 - 1 < 5u)
-//     E_n = 5u max(|h0| X + |h1| Y + |h2|, |h3| X + |h4| Y + |h5|)     the same for both numerators
-// per PAIR, from the FP32 values (sigma = |s_fp32|, r = rcp(s_fp32) with |r sigma - 1| <= 3u, m = max(|u|, |v|)):
-//     a pair is only decided in FP32 if sigma >= 64 E_s  (then the true |s| >= 63/64 sigma and the quotient's error is
-//     first-order); the quotient n/s computed as n_fp32 * r then errs by at most
-//         E_q = 1.1 (E_n + m E_s) |r| + 5u m                                     (1.1 covers 64/63, the reciprocal's
-//                                                                                 3u and the second-order term)
-//     dx = x2 - u errs by   E = E_q + u max(|x2|, |y2|) + 1.01u max(|dx|, |dy|)  (input rounding, the subtraction)
-//     d2 = dx^2 + dy^2 errs by   B32 <= 2 E (2 max(|dx|, |dy|) + E) + 2.2u d2
-// The FP64 value the reference computes differs from the exact one by the same expressions with 2^-53 for u (a few more
-// roundings, no fma): less than 2^-27 B32.  B = 1.01 B32 covers that and the rounding of the bound's own evaluation (a
-// dozen FP32 operations, every term non-negative).  Models or points outside the magnitudes for which "relative error
-// u per operation" holds (overflow, underflow to subnormals) are not eligible: a model with a coefficient >= 2^100, not
-// finite, or with E_s or E_n below 2^-80 gets tau = NaN (every comparison against it is false) and all its pairs go to FP64; the launcher uses this kernel
-// only when every coordinate is finite and below 2^20 in magnitude.  A NaN anywhere makes both comparisons false, which
-// also sends the pair to FP64.
-//
-// Most pairs are nowhere near the threshold — a random hypothesis maps a point hundreds of pixels from its match — and
-// for them a much cheaper sufficient test decides "not an inlier" before d2, or even a quotient, is formed.  It works on
-//         Wx = x2 s - nx = s dx,     Wy = y2 s - ny = s dy          (one fma each; no reciprocal)
-// With Cmax = max |x2|, |y2| over all points, the computed Wx^ = fl(x2~ s~ - nx~) satisfies
-//         |Wx^ - Wx| <= Cmax (1+u) E_s + E_n + u Cmax |s| + 1.01u |Wx^|         (s~, nx~ as above, x2~ = fl32(x2), the fma's rounding)
-// so with the per-model constant A = 1.01 (Cmax E_s + E_n) and W^ = max(|Wx^|, |Wy^|), if
-//         sigma >= 64 E_s,     W^ >= 1.12 thr sigma,     W^ >= 25 A,     W^ >= 25.4 u Cmax sigma
-// then (|s| <= 65/64 sigma) the true max(|dx|, |dy|) = max(|Wx|, |Wy|) / |s| is at least
-//         W^ (1 - 1.01u - 0.04 - 0.04) / (65/64 sigma) >= 0.9057 W^ / sigma >= 1.014 thr
-// and the true d2 at least 1.028 thr^2 — a margin of 2.8 % against the 2^-50 by which the reference's own roundings can move
-// d2.  (The factor was 2.5 at first; hypotheses fitted to four matches are often nearly right for a whole plane, 3 % of
-// the pairs of a DLT batch lie within 5 pixels, and every pair that fails this test costs the full bound below.)  The second and fourth condition are one comparison against k1 sigma with the
-// per-launch constant k1 = max(1.12 thr, 25.4 u Cmax) (rounded up); the third against the per-model constant 25.2 A.
-// Products cannot overflow: eligible models have |h6| X + |h7| Y + |h8| and both numerators' sums below 2^100 and
-// coordinates are below 2^20; they do not underflow into the subnormals either where it matters: W^ >= k1 sigma with
-// sigma >= 2^-74 (E_s >= 2^-80) and thr^2 >= 2^-40 (the launcher's precondition) is a normal number.  When all 64 lanes
-// of a wave pass this for a pair, the wave moves on (a wave-uniform branch); otherwise the pair takes the full bound.
-// (Until late r03 this test was formed on the quotient, with a reciprocal and two multiplies more per pair.)
-//
-// An FP32 instruction with a scalar-register operand issues in 4 cycles, with vector operands only in 2
-// (tools/ubench/valu_cost.hip), so the per-model constants are staged in LDS once per workgroup and broadcast into
-// VGPRs per model (LDS instructions do not take VALU issue slots).
-//
-// Work split as k_residual: a 256-thread workgroup owns MC models (64 by default) and sweeps a slice of the points, a lane
-// holds PPL = 4 points.
-#include "mh_kernels.hpp"
-#include "mh_device.hpp"
-
-#include <cmath>
+// score32.hip — inlier scoring and the int32 data-cost matrix behind the FP32 pre-test, gfx950 (the test, its bound and
+// its derivation: pretest32.hpp).  Counts are the reference's, bit for bit.
+#include "pretest32.hpp"
 
 namespace mh {
-
-constexpr float U32 = 5.9604644775390625e-08f;       // 2^-24
 
 // per model: 9 coefficients in FP32, then 1.1 E_s, 1.1 E_n, tau = 64 E_s (or NaN: not eligible), 25.2 A (the cheap test), 3 pad
 __global__ void __launch_bounds__(256)
@@ -102,83 +43,37 @@ score32_wg(const double* __restrict__ x1, const double* __restrict__ y1, const d
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m0 = bx * MC;
     __shared__ float4 s_m[MC * 4];               // this workgroup's rows of the model table
-    for (int i = threadIdx.x; i < MC * 4; i += 256) {
-        const size_t g = (size_t)m0 * 4 + i;
-        s_m[i] = g < (size_t)M * 4 ? reinterpret_cast<const float4*>(H32)[g] : make_float4(0.f, 0.f, 0.f, NAN);
-    }
+    stage_model32<MC, 256>(s_m, H32, m0, M);
     __syncthreads();
-    // kernel-argument constants that enter FP32 instructions: VGPR copies, made once
-    float vthr2, vc_thr, vk1;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(vthr2) : "s"(thr2_f));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(vc_thr) : "s"(c_thr));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(vk1) : "s"(k1));
+    const float vthr2 = vgpr_copy(thr2_f), vc_thr = vgpr_copy(c_thr), vk1 = vgpr_copy(k1);
     int cnt = 0;                                 // lane mi of each wave counts model m0 + mi
     unsigned long long fb = 0;                   // pairs this lane sent to FP64 (diagnostic)
     for (int base = by * TILE; base < N; base += psplit * TILE) {
         const int n0 = base + wave * WAVE_PTS + lane * PPL;
-        // only the FP32 copies of the points stay in registers; the rare FP64 decision reloads its point (L2-resident)
         float fx[PPL], fy[PPL], gx[PPL], gy[PPL], cx[PPL];
         unsigned long long okm[PPL];
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) {
-            const int n = n0 + q;
-            bool ok = n < N;
-            const double px = ok ? x1[n] : 1.0, py = ok ? y1[n] : 1.0, qx = ok ? x2[n] : 1.0, qy = ok ? y2[n] : 1.0;
-            if (MASK && ok) ok = mask[n] != 0;
-            okm[q] = __builtin_amdgcn_ballot_w64(ok);
-            fx[q] = (float)px; fy[q] = (float)py; gx[q] = (float)qx; gy[q] = (float)qy;
-            cx[q] = U32 * fmaxf(fabsf(gx[q]), fabsf(gy[q])) * 1.0000002f;
-        }
+        load_tile32<PPL, MASK>(x1, y1, x2, y2, N, n0, mask, fx, fy, gx, gy, cx, okm);
 #pragma unroll 1
         for (int mi = 0; mi < MC; ++mi) {
             const int m = m0 + mi;
             if (m >= M) break;
-            // broadcast LDS reads: every lane gets the model's constants in VGPRs
-            const float4 ma = s_m[4 * mi], mb = s_m[4 * mi + 1], mc = s_m[4 * mi + 2], md = s_m[4 * mi + 3];
-            const float h0 = ma.x, h1 = ma.y, h2 = ma.z, h3 = ma.w, h4 = mb.x, h5 = mb.y, h6 = mb.z, h7 = mb.w, h8 = mc.x;
-            const float es = mc.y, en = mc.z, tau = mc.w, a25 = md.x;
-            // Pass one, all PPL pairs: the cheap test.  Nothing but the PPL lane masks survives it, so it needs few registers.
+            const Model32 mod = model32_from_lds(s_m, mi);
             unsigned long long farq[PPL], all_far = ~0ull;
 #pragma unroll
             for (int q = 0; q < PPL; ++q) {
-                const float s = __builtin_fmaf(h6, fx[q], __builtin_fmaf(h7, fy[q], h8));
-                const float nx = __builtin_fmaf(h0, fx[q], __builtin_fmaf(h1, fy[q], h2));
-                const float ny = __builtin_fmaf(h3, fx[q], __builtin_fmaf(h4, fy[q], h5));
-                const float wx = __builtin_fmaf(gx[q], s, -nx), wy = __builtin_fmaf(gy[q], s, -ny);      // s dx, s dy
-                const float W = fmaxf(fabsf(wx), fabsf(wy));
-                farq[q] = __builtin_amdgcn_ballot_w64(fabsf(s) >= tau) &
-                          __builtin_amdgcn_ballot_w64(W >= fmaxf(vk1 * fabsf(s), a25));
+                farq[q] = cheap_far(mod, fx[q], fy[q], gx[q], gy[q], vk1);
                 all_far &= farq[q];
             }
             int c_m = 0;
             if (all_far != ~0ull) {
-                // Pass two, only for the pairs in which some lane is not provably far out: the full bound (the few FP32
-                // operations of pass one are simply done again; this is the rare path)
 #pragma unroll
                 for (int q = 0; q < PPL; ++q) {
                     if (farq[q] == ~0ull) continue;
                     asm volatile("; score32: full bound");           // (keeps the two passes' arithmetic apart)
-                    const float s = __builtin_fmaf(h6, fx[q], __builtin_fmaf(h7, fy[q], h8));
-                    const float nx = __builtin_fmaf(h0, fx[q], __builtin_fmaf(h1, fy[q], h2));
-                    const float ny = __builtin_fmaf(h3, fx[q], __builtin_fmaf(h4, fy[q], h5));
-                    const float r = __builtin_amdgcn_rcpf(s);
-                    const float uu = nx * r, vv = ny * r;
-                    const float dx = gx[q] - uu, dy = gy[q] - vv;
-                    const float w = fmaxf(fabsf(dx), fabsf(dy));
-                    const float d2 = __builtin_fmaf(dx, dx, dy * dy);
-                    // the bound (every term >= 0); B0 = everything but the 2.2u d2 term, which the constant c_thr absorbs: a pair
-                    // decided as inlier has d2 < thr^2, and "d2 - B0 >= thr^2 (1 + 3u)" implies "d2 (1 - 2.2u) - B0 >= thr^2"
-                    const float mm = fmaxf(fabsf(uu), fabsf(vv));
-                    const float eq = __builtin_fmaf(__builtin_fmaf(mm, es, en), fabsf(r), (5.0f * U32) * mm);
-                    const float E = __builtin_fmaf(1.01f * U32, w, eq + cx[q]);
-                    const float B0 = __builtin_fmaf(2.02f * E, __builtin_fmaf(2.0f, w, E), vc_thr);
-                    const float t = d2 - vthr2;
-                    // lane masks straight from the compares; the logic on them is scalar
-                    const unsigned long long trust = __builtin_amdgcn_ballot_w64(fabsf(s) >= tau);
-                    const unsigned long long clear = __builtin_amdgcn_ballot_w64(fabsf(t) > B0);       // (false for NaN)
-                    const unsigned long long below = __builtin_amdgcn_ballot_w64(t < 0.0f);
-                    const unsigned long long decided = (trust & clear) | farq[q];
-                    unsigned long long inl = trust & clear & below;
+                    const Bound32 b = full_bound(mod, fx[q], fy[q], gx[q], gy[q], cx[q], vthr2, vc_thr);
+                    const unsigned long long below = __builtin_amdgcn_ballot_w64(b.t < 0.0f);
+                    const unsigned long long decided = (b.trust & b.clear) | farq[q];      // (the logic on the lane masks is scalar)
+                    unsigned long long inl = b.trust & b.clear & below;
                     if (decided != ~0ull) {                               // rarer still: some lane's pair is too close to call
                         const bool need = ((decided >> lane) & 1ull) == 0ull;
                         bool in64 = false;
@@ -194,10 +89,11 @@ score32_wg(const double* __restrict__ x1, const double* __restrict__ y1, const d
                     c_m += __builtin_popcountll(inl & okm[q]);
                 }
             }
-            const int c_new = __builtin_amdgcn_readlane(cnt, mi) + c_m;
-            asm("s_mov_b32 m0, %2\n\ts_nop 0\n\tv_writelane_b32 %0, %1, m0" : "+v"(cnt) : "s"(c_new), "s"(mi) : "m0");
+            cnt = lane_acc_add(cnt, mi, c_m);
         }
     }
+    // (finish32 written out: through the shared helper the tile loop's latch of the 64-model kernels comes out with the other
+    // branch polarity, and a row of the probe then left the parent's spread — DESIGN 3.2)
     __shared__ int s_cnt[4][MC];
     if (lane < MC) s_cnt[wave][lane] = cnt;
     __syncthreads();
@@ -207,11 +103,7 @@ score32_wg(const double* __restrict__ x1, const double* __restrict__ y1, const d
         if (psplit == 1) counts[m0 + t] = c;
         else atomicAdd(&counts[m0 + t], c);
     }
-    if (fallback_pairs) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) fb += __shfl_xor(fb, o, 64);
-        if (lane == 0 && fb) atomicAdd(fallback_pairs, fb);
-    }
+    add_fp64_pairs(fallback_pairs, fb);
 }
 
 template <int PPL, int MC, bool MASK, int MINW = 1>
@@ -224,7 +116,7 @@ k_score32(const double* __restrict__ x1, const double* __restrict__ y1, const do
     score32_wg<PPL, MC, MASK>(x1, y1, x2, y2, N, H, H32, M, thr2, thr2_f, c_thr, k1, counts, mask, psplit, fallback_pairs, blockIdx.x, blockIdx.y);
 }
 
-// The same work items walked by a resident grid that hands them out through a counter (as k_residual_resident, residual.hip).
+// The same work items walked by a resident grid that hands them out through a counter (resident_items).
 template <int PPL, int MC, bool MASK, int MINW = 1>
 __global__ void __launch_bounds__(256, MINW)
 k_score32_resident(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
@@ -232,30 +124,18 @@ k_score32_resident(const double* __restrict__ x1, const double* __restrict__ y1,
                    double thr2, float thr2_f, float c_thr, float k1, int* __restrict__ counts, const unsigned char* __restrict__ mask,
                    int psplit, unsigned long long* __restrict__ fallback_pairs, int gx, int nitems, int* __restrict__ ctl)
 {
-    __shared__ int s_item;
-#pragma unroll 1
-    for (;;) {
-        if (threadIdx.x == 0) s_item = atomicAdd(&ctl[0], 1);
-        __syncthreads();
-        const int item = s_item;
-        if (item >= nitems) break;
-        const int by = item / gx, bx = item - by * gx;
+    resident_items(ctl, gx, psplit, nitems, 0, [&](int bx, int by) {
         score32_wg<PPL, MC, MASK>(x1, y1, x2, y2, N, H, H32, M, thr2, thr2_f, c_thr, k1, counts, mask, psplit, fallback_pairs, bx, by);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && atomicAdd(&ctl[1], 1) == (int)gridDim.x - 1) {
-        ctl[1] = 0;
-        __hip_atomic_store(&ctl[0], 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------
 // k_cost32 — the materialised int32 data-cost matrix (k_cost_matrix of datacost.hip: the s = 4 variant of SURVEY 8(d))
 // behind the same pre-test.  dataEnergy (M/MultiH.cpp:473-504) of a pair whose d2 is at least T = thr^2 81/16 is the
-// constant 2 round(lam T), and for a random hypothesis that is nearly every pair: the cheap test above with
-// k1 = max(1.12 x 9/4 thr, 25.4 u Cmax) (launch_cost32) proves max(|dx|, |dy|) >= 1.014 x 9/4 thr, i.e. d2 >= 1.028 T — a
-// 2.8 % margin beyond the truncation threshold — per LANE; the other lanes (both |dx| and |dy| within 1.12 x 9/4 thr, models
-// not eligible for FP32, NaN anywhere) evaluate the reference's
+// constant 2 round(lam T), and for a random hypothesis that is nearly every pair: the cheap test (cheap_far) with
+// k1 = max(1.12 x 9/4 thr, 25.4 u Cmax) (Pretest32Launch with far_factor 9/4) proves max(|dx|, |dy|) >= 1.014 x 9/4 thr, i.e.
+// d2 >= 1.028 T — a 2.8 % margin beyond the truncation threshold — per LANE; the other lanes (both |dx| and |dy| within
+// 1.12 x 9/4 thr, models not eligible for FP32, NaN anywhere) evaluate the reference's
 // FP64 formula — fwd_d2, the IEEE division d2 / T, C round() — exactly as k_cost_matrix does.  Same matrix, same fused
 // inlier counts, bit for bit.  Measured at 50k x 100k DLT hypotheses: 7.7 -> 4.2 ms (the store stream alone would take 3.6 ms:
 // 3.3 % of the pairs of such a batch are near — hypotheses fitted to four matches are often nearly right for a whole
@@ -273,13 +153,16 @@ __device__ __forceinline__ void wave_lds_handover()
     asm volatile("" ::: "memory");
 }
 
+#define MH_COST32_ARGS                                                                                                          \
+    const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2, const double* __restrict__ y2, \
+    int N, const double* __restrict__ H, const float* __restrict__ H32, int M, double lam, double T, double thr2, float k1,     \
+    int* __restrict__ C, long long ldc, int* __restrict__ counts, int psplit
+#define MH_COST32_PASS x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit
+
 // cost32_wg: the work of ONE workgroup — model block bx (MC models), point slice by.
 template <int MC, int WAVES, bool RISING>
 __device__ __forceinline__ void
-cost32_wg(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
-          const double* __restrict__ y2, int N, const double* __restrict__ H, const float* __restrict__ H32, int M,
-          double lam, double T, double thr2, float k1, int* __restrict__ C, long long ldc, int* __restrict__ counts, int psplit,
-          const int bx, const int by)
+cost32_wg(MH_COST32_ARGS, const int bx, const int by)
 {
     constexpr int PPL = 4, WAVE_PTS = 64 * PPL, TILE = WAVES * WAVE_PTS, THREADS = 64 * WAVES;
     const int lane = threadIdx.x & 63;
@@ -288,14 +171,8 @@ cost32_wg(const double* __restrict__ x1, const double* __restrict__ y1, const do
     __shared__ float4 s_m[MC * 4];
     __shared__ double s_h[MC * 9];               // the FP64 coefficients, for the lanes that need the reference's formula
     __shared__ double s_p[WAVES * PPL * 4 * 64];     // [wave][point of the lane][x1 y1 x2 y2][lane]: every lane's own points in FP64
-    for (int i = threadIdx.x; i < MC * 4; i += THREADS) {
-        const size_t g = (size_t)m0 * 4 + i;
-        s_m[i] = g < (size_t)M * 4 ? reinterpret_cast<const float4*>(H32)[g] : make_float4(0.f, 0.f, 0.f, NAN);
-    }
-    for (int i = threadIdx.x; i < MC * 9; i += THREADS) {
-        const size_t g = (size_t)m0 * 9 + i;
-        s_h[i] = g < (size_t)M * 9 ? H[g] : 0.0;
-    }
+    stage_model32<MC, THREADS>(s_m, H32, m0, M);
+    stage_model64<MC, THREADS>(s_h, H, m0, M);
     __syncthreads();
     double* wave_p = s_p + (size_t)wave * (PPL * 4 * 64);           // + (q * 4 + component) * 64 + lane
     double* my_p = wave_p + lane;
@@ -303,41 +180,27 @@ cost32_wg(const double* __restrict__ x1, const double* __restrict__ y1, const do
     __shared__ int s_c[WAVES * 64 * PPL];                               // per wave: their costs, on the way back to the owning lane
     unsigned char* my_list = s_list + wave * (64 * PPL);
     int* my_c = s_c + wave * (64 * PPL);
-    float vk1;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(vk1) : "s"(k1));
+    const float vk1 = vgpr_copy(k1);
     const int beyond = 2 * (int)round(lam * T);
     int cnt = 0;                                 // lane mi of each wave counts model m0 + mi
     for (int base = by * TILE; base < N; base += psplit * TILE) {
         const int base_n = base + wave * WAVE_PTS;
         const int n0 = base_n + lane * PPL;
         float fx[PPL], fy[PPL], gx[PPL], gy[PPL];
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) {
-            const int n = n0 + q;
-            const bool ok = n < N;
-            const double px = ok ? x1[n] : 1.0, py = ok ? y1[n] : 1.0, qx = ok ? x2[n] : 1.0, qy = ok ? y2[n] : 1.0;
+        load_points32<PPL>(x1, y1, x2, y2, N, n0, fx, fy, gx, gy, [&](int q, bool, double px, double py, double qx, double qy) {
             my_p[(q * 4 + 0) * 64] = px; my_p[(q * 4 + 1) * 64] = py; my_p[(q * 4 + 2) * 64] = qx; my_p[(q * 4 + 3) * 64] = qy;
-            fx[q] = (float)px; fy[q] = (float)py; gx[q] = (float)qx; gy[q] = (float)qy;
-        }
+        });
         wave_lds_handover();                     // the FP64 copies are read by OTHER lanes of this wave below
 #pragma unroll 1
         for (int mi = 0; mi < MC; ++mi) {
             const int m = m0 + mi;
             if (m >= M) break;
-            const float4 ma = s_m[4 * mi], mb = s_m[4 * mi + 1], mc = s_m[4 * mi + 2], md = s_m[4 * mi + 3];
-            const float h0 = ma.x, h1 = ma.y, h2 = ma.z, h3 = ma.w, h4 = mb.x, h5 = mb.y, h6 = mb.z, h7 = mb.w, h8 = mc.x;
-            const float tau = mc.w, a25 = md.x;
+            const Model32 mod = model32_from_lds(s_m, mi);
             int c[PPL];
             unsigned long long nearq[PPL], any_near = 0ull;
 #pragma unroll
             for (int q = 0; q < PPL; ++q) {
-                const float s = __builtin_fmaf(h6, fx[q], __builtin_fmaf(h7, fy[q], h8));
-                const float nx = __builtin_fmaf(h0, fx[q], __builtin_fmaf(h1, fy[q], h2));
-                const float ny = __builtin_fmaf(h3, fx[q], __builtin_fmaf(h4, fy[q], h5));
-                const float wx = __builtin_fmaf(gx[q], s, -nx), wy = __builtin_fmaf(gy[q], s, -ny);
-                const float W = fmaxf(fabsf(wx), fabsf(wy));
-                nearq[q] = ~(__builtin_amdgcn_ballot_w64(fabsf(s) >= tau) &
-                             __builtin_amdgcn_ballot_w64(W >= fmaxf(vk1 * fabsf(s), a25)));
+                nearq[q] = ~cheap_far(mod, fx[q], fy[q], gx[q], gy[q], vk1);
                 any_near |= nearq[q];
                 c[q] = beyond;
             }
@@ -384,23 +247,10 @@ cost32_wg(const double* __restrict__ x1, const double* __restrict__ y1, const do
             }
             else
                 for (int q = 0; q < PPL; ++q) if (n0 + q < N) dst[q] = c[q];
-            if (any_near) {
-                const int c_new = __builtin_amdgcn_readlane(cnt, mi) + c_m;
-                asm("s_mov_b32 m0, %2\n\ts_nop 0\n\tv_writelane_b32 %0, %1, m0" : "+v"(cnt) : "s"(c_new), "s"(mi) : "m0");
-            }
+            if (any_near) cnt = lane_acc_add(cnt, mi, c_m);
         }
     }
-    __shared__ int s_cnt[WAVES][MC];
-    if (lane < MC) s_cnt[wave][lane] = cnt;
-    __syncthreads();
-    if (threadIdx.x < MC && m0 + (int)threadIdx.x < M) {
-        const int t = threadIdx.x;
-        int cc = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) cc += s_cnt[w][t];
-        if (psplit == 1) counts[m0 + t] = cc;
-        else atomicAdd(&counts[m0 + t], cc);
-    }
+    finish32<MC, WAVES, 1>({ cnt }, wave, m0, M, psplit, { counts });
 }
 
 // cost32_wg_batched (r04 EXPERIMENT, mh_set_tuning key 28 = 1; not the default): the same matrix with the near pairs of
@@ -420,10 +270,7 @@ cost32_wg(const double* __restrict__ x1, const double* __restrict__ y1, const do
 // the two writes of an address arrive in order.  Inlier counts go through an LDS counter per (wave, model).
 template <int MC, int WAVES, bool RISING>
 __device__ __forceinline__ void
-cost32_wg_batched(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
-                  const double* __restrict__ y2, int N, const double* __restrict__ H, const float* __restrict__ H32, int M,
-                  double lam, double T, double thr2, float k1, int* __restrict__ C, long long ldc, int* __restrict__ counts, int psplit,
-                  const int bx, const int by)
+cost32_wg_batched(MH_COST32_ARGS, const int bx, const int by)
 {
     constexpr int PPL = 4, WAVE_PTS = 64 * PPL, TILE = WAVES * WAVE_PTS, THREADS = 64 * WAVES, LCAP = 64 + 64 * PPL;
     static_assert(MC <= 64, "a list entry carries the model in 6 bits");
@@ -434,22 +281,15 @@ cost32_wg_batched(const double* __restrict__ x1, const double* __restrict__ y1, 
     __shared__ double s_h[MC * 9];
     __shared__ double s_p[WAVES * PPL * 4 * 64];          // [wave][point of the lane][x1 y1 x2 y2][lane]
     __shared__ unsigned short s_list[WAVES * LCAP];       // per wave: (model << 8 | point slot << 6 | lane) of the pending near pairs
-    __shared__ int s_cnt[WAVES][MC];
-    for (int i = threadIdx.x; i < MC * 4; i += THREADS) {
-        const size_t g = (size_t)m0 * 4 + i;
-        s_m[i] = g < (size_t)M * 4 ? reinterpret_cast<const float4*>(H32)[g] : make_float4(0.f, 0.f, 0.f, NAN);
-    }
-    for (int i = threadIdx.x; i < MC * 9; i += THREADS) {
-        const size_t g = (size_t)m0 * 9 + i;
-        s_h[i] = g < (size_t)M * 9 ? H[g] : 0.0;
-    }
-    for (int i = threadIdx.x; i < WAVES * MC; i += THREADS) (&s_cnt[0][0])[i] = 0;
+    __shared__ int s_cnt[1][WAVES][MC];
+    stage_model32<MC, THREADS>(s_m, H32, m0, M);
+    stage_model64<MC, THREADS>(s_h, H, m0, M);
+    for (int i = threadIdx.x; i < WAVES * MC; i += THREADS) (&s_cnt[0][0][0])[i] = 0;
     __syncthreads();
     double* wave_p = s_p + (size_t)wave * (PPL * 4 * 64);
     double* my_p = wave_p + lane;
     unsigned short* my_list = s_list + wave * LCAP;
-    float vk1;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(vk1) : "s"(k1));
+    const float vk1 = vgpr_copy(k1);
     const int beyond = 2 * (int)round(lam * T);
     typedef int i4v __attribute__((ext_vector_type(4)));
     const i4v vbeyond = { beyond, beyond, beyond, beyond };
@@ -457,14 +297,9 @@ cost32_wg_batched(const double* __restrict__ x1, const double* __restrict__ y1, 
         const int base_n = base + wave * WAVE_PTS;
         const int n0 = base_n + lane * PPL;
         float fx[PPL], fy[PPL], gx[PPL], gy[PPL];
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) {
-            const int n = n0 + q;
-            const bool ok = n < N;
-            const double px = ok ? x1[n] : 1.0, py = ok ? y1[n] : 1.0, qx = ok ? x2[n] : 1.0, qy = ok ? y2[n] : 1.0;
+        load_points32<PPL>(x1, y1, x2, y2, N, n0, fx, fy, gx, gy, [&](int q, bool, double px, double py, double qx, double qy) {
             my_p[(q * 4 + 0) * 64] = px; my_p[(q * 4 + 1) * 64] = py; my_p[(q * 4 + 2) * 64] = qx; my_p[(q * 4 + 3) * 64] = qy;
-            fx[q] = (float)px; fy[q] = (float)py; gx[q] = (float)qx; gy[q] = (float)qy;
-        }
+        });
         wave_lds_handover();                     // the FP64 copies are read by OTHER lanes of this wave below
         // One pass of the IEEE formula over the list entries [first, first + 64) (those below `count`).
         auto evaluate = [&](int first, int count) {
@@ -477,7 +312,7 @@ cost32_wg_batched(const double* __restrict__ x1, const double* __restrict__ y1, 
                 const int n = base_n + l2 * PPL + q2;
                 if (n < N) {
                     C[(size_t)(m0 + mi2) * ldc + n] = cost;
-                    if (d2 < thr2) atomicAdd(&s_cnt[wave][mi2], 1);
+                    if (d2 < thr2) atomicAdd(&s_cnt[0][wave][mi2], 1);
                 }
             }
         };
@@ -486,19 +321,11 @@ cost32_wg_batched(const double* __restrict__ x1, const double* __restrict__ y1, 
         for (int mi = 0; mi < MC; ++mi) {
             const int m = m0 + mi;
             if (m >= M) break;
-            const float4 ma = s_m[4 * mi], mb = s_m[4 * mi + 1], mc = s_m[4 * mi + 2], md = s_m[4 * mi + 3];
-            const float h0 = ma.x, h1 = ma.y, h2 = ma.z, h3 = ma.w, h4 = mb.x, h5 = mb.y, h6 = mb.z, h7 = mb.w, h8 = mc.x;
-            const float tau = mc.w, a25 = md.x;
+            const Model32 mod = model32_from_lds(s_m, mi);
             unsigned long long nearq[PPL], any_near = 0ull;
 #pragma unroll
             for (int q = 0; q < PPL; ++q) {
-                const float s = __builtin_fmaf(h6, fx[q], __builtin_fmaf(h7, fy[q], h8));
-                const float nx = __builtin_fmaf(h0, fx[q], __builtin_fmaf(h1, fy[q], h2));
-                const float ny = __builtin_fmaf(h3, fx[q], __builtin_fmaf(h4, fy[q], h5));
-                const float wx = __builtin_fmaf(gx[q], s, -nx), wy = __builtin_fmaf(gy[q], s, -ny);
-                const float W = fmaxf(fabsf(wx), fabsf(wy));
-                nearq[q] = ~(__builtin_amdgcn_ballot_w64(fabsf(s) >= tau) &
-                             __builtin_amdgcn_ballot_w64(W >= fmaxf(vk1 * fabsf(s), a25)));
+                nearq[q] = ~cheap_far(mod, fx[q], fy[q], gx[q], gy[q], vk1);
                 any_near |= nearq[q];
             }
             int* dst = C + (size_t)m * ldc + n0;
@@ -533,77 +360,33 @@ cost32_wg_batched(const double* __restrict__ x1, const double* __restrict__ y1, 
         }
         wave_lds_handover();                     // (the next tile's points and list overwrite these)
     }
-    __syncthreads();
-    if (threadIdx.x < MC && m0 + (int)threadIdx.x < M) {
-        const int t = threadIdx.x;
-        int cc = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) cc += s_cnt[w][t];
-        if (psplit == 1) counts[m0 + t] = cc;
-        else atomicAdd(&counts[m0 + t], cc);
-    }
+    sums_to_global<MC, WAVES, 1>(s_cnt, m0, M, psplit, { counts });
 }
 
-// The data term (mh_set_data_term) is a template argument of the workgroup functions above, not of k_cost32 / k_cost32_resident:
-// the product's two kernels keep their names and their code, and the rising term runs in kernels of its own name below.
+// One work item in the default form or the key-28 experiment's.  The data term (mh_set_data_term) is a template argument of
+// the workgroup functions, not of k_cost32 / k_cost32_resident: the product's two kernels keep their names and their code,
+// and the rising term runs in kernels of its own name below.
 template <int MC, int WAVES, bool BATCH, bool RISING>
 __device__ __forceinline__ void
-cost32_grid(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
-            const double* __restrict__ y2, int N, const double* __restrict__ H, const float* __restrict__ H32, int M,
-            double lam, double T, double thr2, float k1, int* __restrict__ C, long long ldc, int* __restrict__ counts, int psplit)
+cost32_item(MH_COST32_ARGS, const int bx, const int by)
 {
-    if (BATCH) cost32_wg_batched<MC, WAVES, RISING>(x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit, blockIdx.x, blockIdx.y);
-    else cost32_wg<MC, WAVES, RISING>(x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit, blockIdx.x, blockIdx.y);
+    if (BATCH) cost32_wg_batched<MC, WAVES, RISING>(MH_COST32_PASS, bx, by);
+    else cost32_wg<MC, WAVES, RISING>(MH_COST32_PASS, bx, by);
 }
-
-// The same work items walked by a resident grid that hands them out through a counter (as k_residual_resident, residual.hip).
-template <int MC, int WAVES, bool BATCH, bool RISING>
-__device__ __forceinline__ void
-cost32_resident_grid(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
-                     const double* __restrict__ y2, int N, const double* __restrict__ H, const float* __restrict__ H32, int M,
-                     double lam, double T, double thr2, float k1, int* __restrict__ C, long long ldc, int* __restrict__ counts, int psplit,
-                     int gx, int nitems, int* __restrict__ ctl, int slice_major)
-{
-    __shared__ int s_item;
-#pragma unroll 1
-    for (;;) {
-        if (threadIdx.x == 0) s_item = atomicAdd(&ctl[0], 1);
-        __syncthreads();
-        const int item = s_item;
-        if (item >= nitems) break;
-        // slice_major: consecutive items are the point slices of one model block — the workgroups at work write a compact
-        // window of C (tools/ubench/store_order.hip: the store stream alone gains 9 % from that order)
-        int bx, by;
-        if (slice_major) { bx = item / psplit; by = item - bx * psplit; }
-        else { by = item / gx; bx = item - by * gx; }
-        if (BATCH) cost32_wg_batched<MC, WAVES, RISING>(x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit, bx, by);
-        else cost32_wg<MC, WAVES, RISING>(x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit, bx, by);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && atomicAdd(&ctl[1], 1) == (int)gridDim.x - 1) {
-        ctl[1] = 0;
-        __hip_atomic_store(&ctl[0], 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-#define MH_COST32_ARGS                                                                                                          \
-    const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2, const double* __restrict__ y2, \
-    int N, const double* __restrict__ H, const float* __restrict__ H32, int M, double lam, double T, double thr2, float k1,     \
-    int* __restrict__ C, long long ldc, int* __restrict__ counts, int psplit
-#define MH_COST32_PASS x1, y1, x2, y2, N, H, H32, M, lam, T, thr2, k1, C, ldc, counts, psplit
 
 template <int MC, int WAVES, bool BATCH>
 __global__ void __launch_bounds__(64 * WAVES)
 k_cost32(MH_COST32_ARGS)
 {
-    cost32_grid<MC, WAVES, BATCH, false>(MH_COST32_PASS);
+    cost32_item<MC, WAVES, BATCH, false>(MH_COST32_PASS, blockIdx.x, blockIdx.y);
 }
 
+// The same work items walked by a resident grid that hands them out through a counter (resident_items).
 template <int MC, int WAVES, bool BATCH>
 __global__ void __launch_bounds__(64 * WAVES)
 k_cost32_resident(MH_COST32_ARGS, int gx, int nitems, int* __restrict__ ctl, int slice_major)
 {
-    cost32_resident_grid<MC, WAVES, BATCH, false>(MH_COST32_PASS, gx, nitems, ctl, slice_major);
+    resident_items(ctl, gx, psplit, nitems, slice_major, [&](int bx, int by) { cost32_item<MC, WAVES, BATCH, false>(MH_COST32_PASS, bx, by); });
 }
 
 // MH_DATA_TERM_RISING: the same pre-test, lists and stores around round(lam * (d2 / T)) for the near pairs.
@@ -611,14 +394,14 @@ template <int MC, int WAVES, bool BATCH>
 __global__ void __launch_bounds__(64 * WAVES)
 k_rising32(MH_COST32_ARGS)
 {
-    cost32_grid<MC, WAVES, BATCH, true>(MH_COST32_PASS);
+    cost32_item<MC, WAVES, BATCH, true>(MH_COST32_PASS, blockIdx.x, blockIdx.y);
 }
 
 template <int MC, int WAVES, bool BATCH>
 __global__ void __launch_bounds__(64 * WAVES)
 k_rising32_resident(MH_COST32_ARGS, int gx, int nitems, int* __restrict__ ctl, int slice_major)
 {
-    cost32_resident_grid<MC, WAVES, BATCH, true>(MH_COST32_PASS, gx, nitems, ctl, slice_major);
+    resident_items(ctl, gx, psplit, nitems, slice_major, [&](int bx, int by) { cost32_item<MC, WAVES, BATCH, true>(MH_COST32_PASS, bx, by); });
 }
 #undef MH_COST32_ARGS
 #undef MH_COST32_PASS
@@ -635,41 +418,20 @@ static hipError_t launch_cost32_t(const Points& p, const double* H, const float*
     // 256-thread workgroups got 12 waves onto a CU (4.7 ms), one 1 024-thread workgroup 16 again but 4.8 ms; this: 4.2 ms
     constexpr int WAVES = 8;
     const int gx = (M + MC - 1) / MC, ntiles = (p.n + 256 * WAVES - 1) / (256 * WAVES);
-    int psplit = gx < 1024 ? (2048 + gx - 1) / gx : (ntiles >= 8 ? 2 : 1);
-    if (psplit > ntiles) psplit = ntiles;
-    if (psplit < 1) psplit = 1;
-    if (psplit > 1) {
-        hipError_t e = hipMemsetAsync(counts, 0, sizeof(int) * (size_t)M, s);
-        if (e != hipSuccess) return e;
-    }
-    // far = beyond T = (9/4 thr)^2 with a 2 % margin: the cheap test's k1 with 1.12 x 9/4 thr in place of 2.5 thr
-    const float k1 = (float)(std::fmax(1.12 * 2.25 * std::sqrt(std::fabs(thr2)), 25.4 * 5.9604644775390625e-08 * Cmax) * (1.0 + 1e-6)) + 1e-30f;
+    const float k1 = Pretest32Launch(thr2, Cmax, 2.25).k1;
     const auto k_plain = RISING ? k_rising32<MC, WAVES, BATCH> : k_cost32<MC, WAVES, BATCH>;
     const auto k_resident = RISING ? k_rising32_resident<MC, WAVES, BATCH> : k_cost32_resident<MC, WAVES, BATCH>;
-    if (resident_ctl) {
-        // resident grid: as many workgroups as the chip holds, ~37 500 items (r04 experiment: mh_set_tuning key 23)
-        // workgroups a compute unit holds: asked once per ENGINE (the caller's cache; a function-local static would be shared
-        // by every engine, device and host thread, and would keep a failed query for ever — r04 advisor finding)
-        int per_cu = occ_cache ? *occ_cache : -1;
-        if (per_cu < 0) {
-            int q = 0;
-            per_cu = hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, (const void*)k_resident, 64 * WAVES, 0) == hipSuccess ? q : 0;
-            if (per_cu > 0 && occ_cache) *occ_cache = per_cu;
-        }
-        const int grid = per_cu * cu_count;
-        int ps = psplit_override > 0 ? psplit_override : (37500 + gx - 1) / gx;
-        if (ps > ntiles) ps = ntiles;
-        if (ps < 1) ps = 1;
-        if (grid > 0 && gx * ps > grid) {
-            hipError_t e = hipMemsetAsync(counts, 0, sizeof(int) * (size_t)M, s);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k_resident, dim3(grid), dim3(64 * WAVES), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, H32, M,
-                               100.0 / lambda, thr2 * 81.0 / 16.0, thr2, k1, C, ldc, counts, ps, gx, gx * ps, resident_ctl, slice_major);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL(k_plain, dim3(gx, psplit), dim3(64 * WAVES), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, H32, M, 100.0 / lambda,
-                       thr2 * 81.0 / 16.0, thr2, k1, C, ldc, counts, psplit);
+    // resident grid: as many workgroups as the chip holds, ~37 500 items (r04 experiment: mh_set_tuning key 23)
+    int psplit = 0;
+    const int grid = resident_ctl ? resident_grid((const void*)k_resident, 64 * WAVES, occ_cache, cu_count, psplit_override, gx, ntiles, &psplit) : 0;
+    hipError_t e = point_slices(gx, ntiles, 8, 2, grid > 0 ? psplit : 0, M, counts, nullptr, s, &psplit);
+    if (e != hipSuccess) return e;
+    if (grid > 0)
+        hipLaunchKernelGGL(k_resident, dim3(grid), dim3(64 * WAVES), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, H32, M,
+                           100.0 / lambda, thr2 * 81.0 / 16.0, thr2, k1, C, ldc, counts, psplit, gx, gx * psplit, resident_ctl, slice_major);
+    else
+        hipLaunchKernelGGL(k_plain, dim3(gx, psplit), dim3(64 * WAVES), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, H32, M, 100.0 / lambda,
+                           thr2 * 81.0 / 16.0, thr2, k1, C, ldc, counts, psplit);
     return hipGetLastError();
 }
 
@@ -707,39 +469,19 @@ static hipError_t launch_score32_t(const Points& p, const double* H, const float
                                    int cu_count = 256, int resident_slices = 0, int* occ_cache = nullptr)
 {
     const int gx = (M + MC - 1) / MC, ntiles = (p.n + 256 * PPL - 1) / (256 * PPL);
-    int psplit = gx < 1024 ? (2048 + gx - 1) / gx : (ntiles >= 16 ? 4 : 1);
-    int resident = 0;
-    if (resident_ctl && resident_slices != 0 && !mask) {
-        int per_cu = occ_cache ? *occ_cache : -1;              // per engine, and a failed query is not kept (see launch_cost32_t)
-        if (per_cu < 0) {
-            int q = 0;
-            per_cu = hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, (const void*)k_score32_resident<PPL, MC, false, MINW>, 256, 0) == hipSuccess ? q : 0;
-            if (per_cu > 0 && occ_cache) *occ_cache = per_cu;
-        }
-        int ps = resident_slices > 0 ? resident_slices : (37500 + gx - 1) / gx;
-        if (ps > ntiles) ps = ntiles;
-        if (ps < 1) ps = 1;
-        if (per_cu * cu_count > 0 && gx * ps > per_cu * cu_count) { resident = per_cu * cu_count; psplit = ps; }
-    }
-    if (psplit > ntiles) psplit = ntiles;
-    if (psplit < 1) psplit = 1;
-    if (psplit > 1) {
-        hipError_t e = hipMemsetAsync(counts, 0, sizeof(int) * (size_t)M, s);
-        if (e != hipSuccess) return e;
-    }
-    // the threshold in FP32 and the constant part of the bound: the rounding of the threshold itself (one ulp covers it
-    // either way) plus the 2.2u d2 term for d2 up to thr^2 (1 + 3u) (see the kernel)
-    const float tf = (float)thr2;
-    const float c_thr = (float)(std::fabs((double)tf - thr2) * 1.01 + 3.5 * 5.9604644775390625e-08 * std::fabs(thr2) * 1.01) + 1e-45f;
-    // the cheap test's k1 = max(1.12 thr, 25.4 u Cmax), rounded up (the product k1 sigma is rounded once more in the kernel)
-    const float k1 = (float)(std::fmax(1.12 * std::sqrt(std::fabs(thr2)), 25.4 * 5.9604644775390625e-08 * Cmax) * (1.0 + 1e-6)) + 1e-30f;
+    int psplit = 0, resident = 0;
+    if (resident_ctl && resident_slices != 0 && !mask)
+        resident = resident_grid((const void*)k_score32_resident<PPL, MC, false, MINW>, 256, occ_cache, cu_count, resident_slices, gx, ntiles, &psplit);
+    hipError_t e = point_slices(gx, ntiles, 16, 4, resident > 0 ? psplit : 0, M, counts, nullptr, s, &psplit);
+    if (e != hipSuccess) return e;
+    const Pretest32Launch c(thr2, Cmax, 1.0);
     if (resident > 0) {
-        hipLaunchKernelGGL((k_score32_resident<PPL, MC, false, MINW>), dim3(resident), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, H32, M, thr2, tf,
-                           c_thr, k1, counts, mask, psplit, fallback_pairs, gx, gx * psplit, resident_ctl);
+        hipLaunchKernelGGL((k_score32_resident<PPL, MC, false, MINW>), dim3(resident), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, H32, M, thr2, c.thr2_f,
+                           c.c_thr, c.k1, counts, mask, psplit, fallback_pairs, gx, gx * psplit, resident_ctl);
         return hipGetLastError();
     }
-    if (mask) hipLaunchKernelGGL((k_score32<PPL, MC, true, MINW>), dim3(gx, psplit), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, H32, M, thr2, tf, c_thr, k1, counts, mask, psplit, fallback_pairs);
-    else hipLaunchKernelGGL((k_score32<PPL, MC, false, MINW>), dim3(gx, psplit), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, H32, M, thr2, tf, c_thr, k1, counts, mask, psplit, fallback_pairs);
+    if (mask) hipLaunchKernelGGL((k_score32<PPL, MC, true, MINW>), dim3(gx, psplit), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, H32, M, thr2, c.thr2_f, c.c_thr, c.k1, counts, mask, psplit, fallback_pairs);
+    else hipLaunchKernelGGL((k_score32<PPL, MC, false, MINW>), dim3(gx, psplit), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, H32, M, thr2, c.thr2_f, c.c_thr, c.k1, counts, mask, psplit, fallback_pairs);
     return hipGetLastError();
 }
 

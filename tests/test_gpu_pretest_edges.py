@@ -1,4 +1,4 @@
-"""Directed tests on the edges of the FP32 pre-test of the score kernels (csrc/score32.hip:32-48).
+"""Directed tests on the edges of the FP32 pre-test of the score kernels (csrc/pretest32.hpp:34-50).
 The cheap sufficient test declares a pair "provably not an inlier" when, in FP32,
     sigma = |s^| >= tau = 64 E_s      and      W^ = max(|Wx^|, |Wy^|) >= max(k1 sigma, 25.2 A)
 with Wx^ = fl(x2~ s^ - nx^).  The pass-one arithmetic is re-enacted here in exact rational arithmetic rounded to FP32 once
@@ -96,6 +96,31 @@ def _check(engine, oracle, src, dst, H, thr2):
         assert np.array_equal(engine.score(thr2), want)
     finally:
         engine.set_tuning(15, 1)
+    # The same edges seen by the pre-test's two other consumers, each behind the pre-test (key 15 = 1) and without it: the MSAC
+    # score (counts as above, weights as the numpy twin of test_gpu_msac.py) and the cost matrix with thr_hom^2 = thr2, whose
+    # key-15 = 0 form is k_cost_matrix of datacost.hip.  The engine squares thr_hom itself, so the matrix's fused counts are
+    # the oracle's at exactly that square (thr2 itself wherever the square root is exact).
+    import msac_numpy as W
+    thr_h = float(np.sqrt(thr2))
+    with np.errstate(all="ignore"):
+        want_w = W.score_msac(src, dst, H, thr2)[1]
+        want_c = want if thr_h * thr_h == thr2 else oracle.score(src, dst, H, thr_h * thr_h)
+    old_thr, lam, mats = engine.thr_hom, engine.lam, []
+    for key15 in (1, 0):
+        engine.set_tuning(15, key15)
+        try:
+            cnt, wgt = engine.score_msac(thr2)
+            assert np.array_equal(cnt, want), f"MSAC counts, key 15 = {key15}"
+            assert np.array_equal(wgt, want_w), f"MSAC weights, key 15 = {key15}"
+            engine.set_params(2.6, thr_h, 0.005, lam, 20)           # (the engine fixture's other parameters)
+            try:
+                mats.append(engine.cost_matrix())
+            finally:
+                engine.set_params(2.6, old_thr, 0.005, lam, 20)
+        finally:
+            engine.set_tuning(15, 1)
+    assert np.array_equal(mats[0][0], mats[1][0]), "cost matrix behind the pre-test against k_cost_matrix"
+    assert np.array_equal(mats[0][1], mats[1][1]) and np.array_equal(mats[0][1], want_c), "the cost matrix's fused counts"
     return pairs, in_fp64
 
 
