@@ -195,7 +195,7 @@ MH_API int mh_get_models(mh_engine* e, double* H /* m x 9 */);
 MH_API int mh_get_model_count(mh_engine* e, int* m);
 /* One model of the current set (9 doubles): what a caller who wants a single winner copies instead of all m. */
 MH_API int mh_get_model(mh_engine* e, int idx, double H[9]);
-MH_API int mh_get_samples(mh_engine* e, int* idx /* m x 4, valid after mh_propose_dlt4 */);
+MH_API int mh_get_samples(mh_engine* e, int* idx /* m x 4, valid after mh_propose_dlt4 and mh_propose_3pt (there the fourth column is -1) */);
 /* The sampler of mh_propose_dlt4 and mh_prefetch_dlt4.  Sticky per engine; mh_set_correspondences does not reset it.
  *   MH_SAMPLER_UNIFORM  every index uniform over all correspondences (default; uniform_per_16 is ignored).
  *   MH_SAMPLER_LOCAL    neighbourhood-guided: needs the sampling table (mh_build_sample_neighbours); both entry points answer
@@ -246,11 +246,38 @@ MH_API int mh_get_sample_neighbours(mh_engine* e, int* nbr /* n x k, nullable */
  * The counters are global and the table is a function of the correspondences, so rank r of a sharded batch proposes its shard with
  * first + (its offset into the batch).  The ranks of a sharded selection must agree on "proposed by mh_propose_haf" and on
  * `members`: the records' mode word carries both (bit 16, bits 17-22; what the RESIDENT batch was proposed with — mh_set_models,
- * mh_propose_dlt4 and mh_adopt_prefetched clear it), and ranks that disagree all return the mode-mismatch MH_ERR_INVALID. */
+ * mh_propose_dlt4, mh_adopt_prefetched and mh_propose_3pt clear it), and ranks that disagree all return the mode-mismatch MH_ERR_INVALID. */
 MH_API int mh_propose_haf(mh_engine* e, long long first, int m, int stride, int members, double thr2);
 /* Per hypothesis of the resident batch, the bit mask of its consistent neighbours (bit j = column j of the anchor's table row).
  * MH_ERR_NOT_SET unless the resident model set came from mh_propose_haf. */
 MH_API int mh_get_haf_support(mh_engine* e, unsigned* used /* m */);
+/* 3-point proposals: with F a homography needs only THREE point correspondences, H = [e']x F + e' v^T (GetHomography3PT,
+ * M/MultiH.cpp:995-1050).  Such a hypothesis is compatible with F by construction, needs one same-plane draw fewer than a 4-point
+ * DLT and no affinities.  Fills the engine's current model set with m hypotheses, replacing it exactly as mh_propose_dlt4 does: the
+ * data cost and the MSAC weights go stale, the HAF record is cleared (mh_get_haf_support answers MH_ERR_NOT_SET).  mh_score,
+ * mh_score_msac, mh_select_best, mh_select_greedy and mh_select_greedy_msac work on the batch unchanged, refitted winners (key 30)
+ * under both estimators included.
+ *   1. Hypothesis s has counter c = first + s.  Its tuple t is the FIRST THREE indices of the 4-tuple the engine's sampler
+ *      (mh_set_sampler) gives counter c under `seed` in mh_propose_dlt4:
+ *        MH_SAMPLER_UNIFORM  draw j = 0, 1, .. gives r = splitmix64(seed + (c << 8) + j) (64-bit wrap-around) and the index
+ *                            ((r >> 32) * n) >> 32; an index already in the tuple is rejected; at most 64 draws; slots still empty
+ *                            then take the first index.
+ *        MH_SAMPLER_LOCAL    counters with (c & 15) < uniform_per_16 as above; the others keep the uniform first index i0 and take
+ *                            their second and third from row i0 of the sampling table, draws j = 1 .. 63, as mh_propose_dlt4 does.
+ *   2. H is GetHomography3PT WITHOUT numerical refinement on (src[t], dst[t]) and the engine's F (mh_set_epipolar): Hartley
+ *      normalisation of the three source and of the three destination points, Fn = T2^-T F T1^-1, the epipole of Fn from the
+ *      eigenvector of Fn Fn^T with the smallest eigenvalue, the third row of the normalised H from the 6 x 3 system's normal
+ *      equations by an eigen-decomposition (eigenvalues within 2 eps sum |w| of zero dropped), rows 1-2 from it, H = T2^-1 Hn T1 —
+ *      operation for operation the host's Homography3PTLinear (what the post-filter's trials fit with).
+ *   3. A fit with an entry that is not finite stores NINE QUIET NaNs (0x7ff8000000000000): it scores 0 everywhere.
+ * mh_get_samples returns m x 4: the three indices and -1 in the fourth column.
+ * m == 0 leaves an empty set, like mh_set_models(NULL, 0).  No correspondences or no epipolar geometry: MH_ERR_NOT_SET; the local
+ * sampler without its table: MH_ERR_NOT_SET; fewer than 3 correspondences, m < 0, first < 0: MH_ERR_INVALID.
+ * The counters are global, so rank r of a sharded batch proposes its shard with first + (its offset into the batch).  The ranks of
+ * a sharded selection must agree on "proposed by mh_propose_3pt": bit 23 of the records' mode word says so of the RESIDENT batch
+ * (mh_set_models, mh_propose_dlt4, mh_adopt_prefetched and mh_propose_haf clear it), and ranks that disagree all return the
+ * mode-mismatch MH_ERR_INVALID.  The prefetch pipeline (mh_prefetch_dlt4) stays DLT-only. */
+MH_API int mh_propose_3pt(mh_engine* e, unsigned long long seed, long long first, int m);
 
 /* ---- score -------------------------------------------------------------- */
 /* Residual definition used by mh_score / mh_residual_matrix / mh_get_residual_rows:
@@ -355,7 +382,8 @@ MH_API int mh_set_transport(mh_engine* e, int rank, int world, mh_allgather_stre
  * own error, the others with MH_ERR_HIP "a rank reported an error".  Arguments (thr2, need, max_models, total_m) must be
  * the same on every rank, and so must the settings the records' mode word carries: the residual mode, refitted winners and their
  * estimator, the sampler, (bit 15) whether the rank ranks by count — this entry point — or by weight
- * (mh_select_greedy_msac), and (bit 16, bits 17-22) whether the resident batch is mh_propose_haf's and with how many members;
+ * (mh_select_greedy_msac), (bit 16, bits 17-22) whether the resident batch is mh_propose_haf's and with how many members, and
+ * (bit 23) whether it is mh_propose_3pt's;
  * ranks that disagree all return MH_ERR_INVALID after the first exchange. */
 MH_API int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned char* point_mask,
                             double* H_out, long long* counters_out, int* counts_out, int* selected_out, long long total_m);

@@ -30,7 +30,7 @@ SYMBOLS = [
     "mh_set_neighbors_csr", "mh_build_neighbors_knn", "mh_build_neighbors_knn_radius", "mh_build_neighbors_radius", "mh_get_sym_graph", "mh_set_fundamental_metric", "mh_propose_fund8",
     "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_propose_fund7", "mh_get_fund7_samples", "mh_estimate_fundamental_minimal", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons", "mh_refine_points",
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
-    "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_propose_haf", "mh_get_haf_support", "mh_set_residual_mode", "mh_score", "mh_score_msac", "mh_select_best_msac",
+    "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_propose_haf", "mh_get_haf_support", "mh_propose_3pt", "mh_set_residual_mode", "mh_score", "mh_score_msac", "mh_select_best_msac",
     "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_select_greedy_msac", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
     "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
     "mh_profile_get", "mh_set_tuning",
@@ -335,6 +335,11 @@ class Engine:
         """mh_propose_haf: m hypotheses, one per affine correspondence (anchors (first + s) * stride), refitted to the consistent
         ones among the first `members` neighbours of the sampling table (members = 0: the single correspondence)."""
         self._check(self.lib.mh_propose_haf(self._h, C.c_longlong(int(first)), int(m), int(stride), int(members), C.c_double(thr2)))
+
+    def propose_3pt(self, seed: int, first: int, m: int):
+        """mh_propose_3pt: m F-constrained 3-point hypotheses, counters first .. first + m - 1; the tuple of a counter is the
+        first three indices of the 4-tuple the sampler (set_sampler) gives it.  Needs set_epipolar."""
+        self._check(self.lib.mh_propose_3pt(self._h, C.c_ulonglong(seed), C.c_longlong(first), int(m)))
 
     def get_haf_support(self):
         """mh_get_haf_support: per hypothesis of the resident HAF batch the bit mask of its consistent neighbours (uint32)."""

@@ -518,7 +518,7 @@ int mh_set_correspondences(mh_engine* e, const double* src_xy, const double* dst
     if (n != e->n) {
         // everything sized by the previous point set is stale: the residual matrix and its pitch, the sampled batch,
         // the fundamental-matrix hypotheses
-        e->m = 0; e->ldr = 0; e->have_samples = false; e->haf_batch = false; e->fm = 0; e->f7_m = 0;
+        e->m = 0; e->ldr = 0; e->have_samples = false; e->haf_batch = false; e->p3_batch = false; e->fm = 0; e->f7_m = 0;
         e->counts_fresh = false; ++e->models_seq;
     }
     {

@@ -3,7 +3,7 @@
 //   capi.hip          life cycle, parameters, correspondences, neighbourhood graph, buffers, profiling, tuning keys
 //   capi_front.hip    epipolar front half, per-point homographies, mean shift          
 //   capi_score.hip    propose, model sets, score / residual matrix / cost matrix, prefetch queue, inlier read-outs
-//   capi_propose.hip  HAF proposals: a hypothesis per affine correspondence (mh_propose_haf, mh_get_haf_support)
+//   capi_propose.hip  HAF proposals: a hypothesis per affine correspondence (mh_propose_haf, mh_get_haf_support); 3-point proposals (mh_propose_3pt)
 //   capi_select.hip   transport, greedy selection, best model of a batch (the score exchange)
 //   capi_label.hip    data cost, alpha-expansion, re-estimation, LabelingStep, post-filter statistics
 #pragma once
@@ -91,6 +91,7 @@ struct mh_engine {
     // the selection records carry it (bit 16 and bits 17-22 of their mode word)
     bool haf_batch = false;
     int haf_members = 0;
+    bool p3_batch = false;                   // the resident batch is mh_propose_3pt's (bit 23 of the mode word); cleared by the same three and by mh_propose_haf
     DevBuf<unsigned> haf_used;               // per hypothesis of a HAF batch, the mask of consistent neighbours (mh_get_haf_support)
     DevBuf<double> R;
     long long ldr = 0;

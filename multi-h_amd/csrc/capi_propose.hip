@@ -1,6 +1,7 @@
 // capi_propose.hip: HAF proposals — a hypothesis per affine correspondence as the engine's model set (mh_propose_haf) and the
-// neighbours each of them was refitted to (mh_get_haf_support) — part of the C ABI of include/multih_hip.h (see capi_engine.hpp
-// for the split).  The kernel is csrc/haf_propose.hip.
+// neighbours each of them was refitted to (mh_get_haf_support) — and 3-point proposals — a hypothesis per sampled triple and F
+// (mh_propose_3pt) — part of the C ABI of include/multih_hip.h (see capi_engine.hpp for the split).  The kernels are
+// csrc/haf_propose.hip and csrc/propose3pt.hip.
 #include "capi_engine.hpp"
 
 extern "C" {
@@ -24,6 +25,7 @@ int mh_propose_haf(mh_engine* e, long long first, int m, int stride, int members
     e->cost_L = 0;
     e->m = 0;
     e->haf_members = members;
+    e->p3_batch = false;
     e->haf_batch = (m == 0);                                   // an empty batch is one already; a full one once its launch is accepted
     if (m == 0) return MH_OK;                                  // an empty model set, as mh_set_models(NULL, 0) leaves one
     HIPCHK(e->H.reserve((size_t)m * 9));
@@ -34,6 +36,33 @@ int mh_propose_haf(mh_engine* e, long long first, int m, int stride, int members
                               e->H.p, e->haf_used.p, e->stream));
     e->m = m;
     e->haf_batch = true;
+    return MH_OK;
+    });
+}
+
+int mh_propose_3pt(mh_engine* e, unsigned long long seed, long long first, int m)
+{
+    return guarded([&]() -> int {
+    int rc = require_points(e);
+    if (rc) return rc;
+    if (m < 0 || first < 0) return fail(MH_ERR_INVALID, "mh_propose_3pt: m >= 0 and first >= 0");
+    if (e->n < 3) return fail(MH_ERR_INVALID, "mh_propose_3pt: need at least 3 correspondences");
+    if (!e->have_epi) return fail(MH_ERR_NOT_SET, "fundamental matrix / epipole are not set");
+    if (e->sampler == MH_SAMPLER_LOCAL && e->smp_k <= 0) return fail(MH_ERR_NOT_SET, "the local sampler has no table; call mh_build_sample_neighbours");
+    e->counts_fresh = false; ++e->models_seq;
+    e->have_samples = false;
+    e->haf_batch = false;
+    e->cost_L = 0;
+    e->m = 0;
+    e->p3_batch = (m == 0);                                    // (as mh_propose_haf: an empty batch is one already)
+    if (m == 0) return MH_OK;                                  // an empty model set, as mh_set_models(NULL, 0) leaves one
+    HIPCHK(e->H.reserve((size_t)m * 9));
+    HIPCHK(e->samples.reserve((size_t)m * 4));
+    HIPCHK(reserve_counts(e, (size_t)m + 1));
+    HIPCHK(launch_propose_3pt(e->pts(), e->epi.F, seed, first, m, e->samples.p, e->H.p, e->stream, e->dlt_local()));
+    e->m = m;
+    e->have_samples = true;
+    e->p3_batch = true;
     return MH_OK;
     });
 }

@@ -113,7 +113,7 @@ int mh_propose_dlt4(mh_engine* e, unsigned long long seed, long long first, int 
     }
     e->m = m;
     e->have_samples = true;
-    e->haf_batch = false;
+    e->haf_batch = false; e->p3_batch = false;
     e->cost_L = 0;
     e->counts_fresh = false; ++e->models_seq;
     return MH_OK;
@@ -138,7 +138,7 @@ int mh_set_models(mh_engine* e, const double* H, int m)
     if (!e || m < 0 || (m > 0 && !H)) return fail(MH_ERR_INVALID, "null argument or m < 0");
     HIPCHK(hipSetDevice(e->device));
     e->counts_fresh = false; ++e->models_seq;
-    e->haf_batch = false;
+    e->haf_batch = false; e->p3_batch = false;
     if (m == 0) { e->m = 0; e->have_samples = false; e->cost_L = 0; return MH_OK; }     // an empty model set
     HIPCHK(e->H.reserve((size_t)m * 9));
     HIPCHK(reserve_counts(e, (size_t)m + 1));
@@ -441,7 +441,7 @@ int mh_adopt_prefetched(mh_engine* e)
     e->pf_head = (e->pf_head + 1) % mh_engine::PF_DEPTH;
     --e->pf_count;
     e->have_samples = true;
-    e->haf_batch = false;
+    e->haf_batch = false; e->p3_batch = false;
     e->cost_L = 0;
     e->counts_fresh = false; ++e->models_seq;
     return MH_OK;

@@ -95,7 +95,9 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
     // other batch, so those records are what they were.  A rank that proposed DLT hypotheses beside one that proposed HAF ones
     // leaves with the others through the same mismatch.
     const int haf_bits = e->haf_batch ? (1 << 16) | (e->haf_members << 17) : 0;
-    const int mode_word = symmetric | (refine ? 2 : 0) | (refine && refit3 ? 4 : 0) | sampler_bits | (by_weight ? 1 << 15 : 0) | haf_bits;
+    // ... bit 23 = by mh_propose_3pt, on the same terms
+    const int p3_bit = e->p3_batch ? 1 << 23 : 0;
+    const int mode_word = symmetric | (refine ? 2 : 0) | (refine && refit3 ? 4 : 0) | sampler_bits | (by_weight ? 1 << 15 : 0) | haf_bits | p3_bit;
     if (refine && !refine_usable)
         local_failure(MH_ERR_NOT_SET, std::string(by_weight ? "mh_select_greedy_msac" : "mh_select_greedy") +
                                       (refit3 ? " with refitted winners (mh_set_tuning key 30) needs the epipolar geometry"
@@ -253,7 +255,7 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
         if (e->h_sel[4] != 0)                            // every rank sees the same word, so every rank leaves here
             return fail(e->h_sel[4] == 3 ? MH_ERR_INVALID : MH_ERR_HIP,
                         e->h_sel[4] == 2 ? "greedy selection: the gathered score vector and the ranks' records disagree about the winner"
-                        : e->h_sel[4] == 3 ? "greedy selection: the ranks are not in the same residual mode (mh_set_residual_mode) or do not agree on refitted winners (mh_set_tuning key 30), the estimator (mh_set_estimator), the proposer's sampler (mh_set_sampler) or the selection's score (mh_select_greedy / mh_select_greedy_msac), or proposed their shards differently (mh_propose_haf and its members)"
+                        : e->h_sel[4] == 3 ? "greedy selection: the ranks are not in the same residual mode (mh_set_residual_mode) or do not agree on refitted winners (mh_set_tuning key 30), the estimator (mh_set_estimator), the proposer's sampler (mh_set_sampler) or the selection's score (mh_select_greedy / mh_select_greedy_msac), or proposed their shards differently (mh_propose_haf and its members, mh_propose_3pt)"
                                            : "greedy selection: a rank reported an error");
         // word 0: the winner's rank value (its count, or its weight), -1 when nobody was eligible; word 6: its count
         if (e->h_sel[0] < 0) break;

@@ -50,61 +50,8 @@ __device__ __forceinline__ void insert_large3(u64 (&tp)[3], u64 k)         // tp
 // 2 eps sum |w| of zero dropped), the other two rows from it, H = T2^-1 Hn T1.  Operation for operation the host's
 // Homography3PTLinear (host/merge_step.cpp: mat3_mul, jacobi3 = jacobi_sym_dev(3), sums from 0.0 in index order) — the fits are
 // bit-identical, which tests/test_gpu_postfilter.py holds them to.  One thread per (cluster, trial).
+// normalize3_dev and homography_3pt_linear_dev live in mh_device.hpp: the 3-point proposer (propose3pt.hip) fits with them too.
 // ---------------------------------------------------------------------------
-namespace {
-
-__device__ __forceinline__ void normalize3_dev(const double* pts, double* out, double* T)
-{
-    double cx = 0.0, cy = 0.0;
-    for (int i = 0; i < 3; ++i) { cx = cx + pts[2 * i]; cy = cy + pts[2 * i + 1]; }
-    const double invn = 1.0 / 3.0;
-    cx = invn * cx; cy = invn * cy;
-    double avg = 0.0;
-    for (int i = 0; i < 3; ++i) {
-        out[2 * i] = pts[2 * i] - cx;
-        out[2 * i + 1] = pts[2 * i + 1] - cy;
-        avg = avg + sqrt(out[2 * i] * out[2 * i] + out[2 * i + 1] * out[2 * i + 1]);
-    }
-    avg = avg / 3.0;
-    const double ratio = sqrt(2.0) / avg;
-    for (int i = 0; i < 6; ++i) out[i] = out[i] * ratio;
-    T[0] = ratio; T[1] = 0; T[2] = -cx * ratio; T[3] = 0; T[4] = ratio; T[5] = -cy * ratio; T[6] = 0; T[7] = 0; T[8] = 1;
-}
-
-__device__ inline bool homography_3pt_linear_dev(const double* pts1, const double* pts2, const double* F, double* H)
-{
-    double p1[6], p2[6], T1[9], T2[9], T2i[9], Fn[9], e0, e1;
-    normalize3_dev(pts1, p1, T1);
-    normalize3_dev(pts2, p2, T2);
-    normalised_epipolar_dev(F, T1, T2, T2i, Fn, e0, e1);
-    double A[18], rhs[6];
-    for (int i = 0; i < 3; ++i) {
-        const double x1 = p1[2 * i], y1 = p1[2 * i + 1], x2 = p2[2 * i], y2 = p2[2 * i + 1];
-        double* r = &A[6 * i];
-        r[0] = e0 * x1 - x2 * x1; r[1] = e0 * y1 - x2 * y1; r[2] = e0 - x2;
-        r[3] = e1 * x1 - y2 * x1; r[4] = e1 * y1 - y2 * y1; r[5] = e1 - y2;
-        rhs[2 * i] = -(x1 * Fn[3] + y1 * Fn[4] + Fn[5]);
-        rhs[2 * i + 1] = (x1 * Fn[0] + y1 * Fn[1] + Fn[2]);
-    }
-    double AtA[9], Atb[3];
-    for (int a = 0; a < 3; ++a) {
-        for (int c = 0; c < 3; ++c) {
-            double s = 0.0;
-            for (int i = 0; i < 6; ++i) s = s + A[3 * i + a] * A[3 * i + c];
-            AtA[3 * a + c] = s;
-        }
-        double s = 0.0;
-        for (int i = 0; i < 6; ++i) s = s + A[3 * i + a] * rhs[i];
-        Atb[a] = s;
-    }
-    double h3[3];
-    sym_eig_solve3_dev(AtA, Atb, h3);                      // x = pinv(AtA) Atb
-    return assemble_3pt_dev(h3, e0, e1, Fn, T1, T2i, H);
-}
-
-} // namespace
-
-struct Fund9 { double f[9]; };
 
 __global__ void __launch_bounds__(128)
 k_compat_fit(const double* __restrict__ pts, const int* __restrict__ begin, const int* __restrict__ tri, Fund9 F, int trials, int total,

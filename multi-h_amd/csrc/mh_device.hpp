@@ -236,8 +236,8 @@ __device__ inline void jacobi_sym_dev(int n, double* a, double* v, double* d)
 }
 
 // ---------------------------------------------------------------------------
-// Pieces of GetHomography3PT without refinement (M/MultiH.cpp:995-1050) shared by the device's two 3-point fits — the
-// post-filter's trials (compat.hip) and the per-label point-only re-estimator (reestimate3pt.hip) — operation for operation the
+// Pieces of GetHomography3PT without refinement (M/MultiH.cpp:995-1050) shared by the device's 3-point fits — the
+// post-filter's trials (compat.hip), the 3-point proposer (propose3pt.hip) and the per-label point-only re-estimator (reestimate3pt.hip) — operation for operation the
 // host's Homography3PTLinear (host/merge_step.cpp: mat3_mul, similarity_inverse, jacobi3 = jacobi_sym_dev(3), sym_eig_solve3).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void mat3_mul_dev(const double* a, const double* b, double* c)
@@ -311,5 +311,59 @@ __device__ inline bool assemble_3pt_dev(const double* h3, double e0, double e1, 
     for (int i = 0; i < 9; ++i) if (!(fabs(H[i]) <= 1.7976931348623157e308)) ok = false;      // std::isfinite
     return ok;
 }
+
+// GetHomography3PT without refinement, whole: Hartley normalisation of the three source and the three destination points
+// (Homography_Refine3PTCallback.h:161-196), then the pieces above.  The post-filter's trials (compat.hip, k_compat_fit) and the
+// 3-point proposer (propose3pt.hip, k_propose_3pt) call it; false when the result is not finite.
+__device__ __forceinline__ void normalize3_dev(const double* pts, double* out, double* T)
+{
+    double cx = 0.0, cy = 0.0;
+    for (int i = 0; i < 3; ++i) { cx = cx + pts[2 * i]; cy = cy + pts[2 * i + 1]; }
+    const double invn = 1.0 / 3.0;
+    cx = invn * cx; cy = invn * cy;
+    double avg = 0.0;
+    for (int i = 0; i < 3; ++i) {
+        out[2 * i] = pts[2 * i] - cx;
+        out[2 * i + 1] = pts[2 * i + 1] - cy;
+        avg = avg + sqrt(out[2 * i] * out[2 * i] + out[2 * i + 1] * out[2 * i + 1]);
+    }
+    avg = avg / 3.0;
+    const double ratio = sqrt(2.0) / avg;
+    for (int i = 0; i < 6; ++i) out[i] = out[i] * ratio;
+    T[0] = ratio; T[1] = 0; T[2] = -cx * ratio; T[3] = 0; T[4] = ratio; T[5] = -cy * ratio; T[6] = 0; T[7] = 0; T[8] = 1;
+}
+
+__device__ inline bool homography_3pt_linear_dev(const double* pts1, const double* pts2, const double* F, double* H)
+{
+    double p1[6], p2[6], T1[9], T2[9], T2i[9], Fn[9], e0, e1;
+    normalize3_dev(pts1, p1, T1);
+    normalize3_dev(pts2, p2, T2);
+    normalised_epipolar_dev(F, T1, T2, T2i, Fn, e0, e1);
+    double A[18], rhs[6];
+    for (int i = 0; i < 3; ++i) {
+        const double x1 = p1[2 * i], y1 = p1[2 * i + 1], x2 = p2[2 * i], y2 = p2[2 * i + 1];
+        double* r = &A[6 * i];
+        r[0] = e0 * x1 - x2 * x1; r[1] = e0 * y1 - x2 * y1; r[2] = e0 - x2;
+        r[3] = e1 * x1 - y2 * x1; r[4] = e1 * y1 - y2 * y1; r[5] = e1 - y2;
+        rhs[2 * i] = -(x1 * Fn[3] + y1 * Fn[4] + Fn[5]);
+        rhs[2 * i + 1] = (x1 * Fn[0] + y1 * Fn[1] + Fn[2]);
+    }
+    double AtA[9], Atb[3];
+    for (int a = 0; a < 3; ++a) {
+        for (int c = 0; c < 3; ++c) {
+            double s = 0.0;
+            for (int i = 0; i < 6; ++i) s = s + A[3 * i + a] * A[3 * i + c];
+            AtA[3 * a + c] = s;
+        }
+        double s = 0.0;
+        for (int i = 0; i < 6; ++i) s = s + A[3 * i + a] * rhs[i];
+        Atb[a] = s;
+    }
+    double h3[3];
+    sym_eig_solve3_dev(AtA, Atb, h3);                      // x = pinv(AtA) Atb
+    return assemble_3pt_dev(h3, e0, e1, Fn, T1, T2i, H);
+}
+
+struct Fund9 { double f[9]; };          // F by value to a kernel
 
 } // namespace mh

@@ -143,6 +143,12 @@ hipError_t launch_haf_point(const Points& p, const Affines& a, const Epipolar& e
 hipError_t launch_haf_propose(const Points& p, const Affines& a, const Epipolar& ep, const int* nbr, int k, int members,
                               double thr2, long long first, int m, int stride, double* H_out, unsigned* used_out, hipStream_t s);
 
+// --- propose3pt.hip: F-constrained 3-point hypotheses (mh_propose_3pt) ---
+// hypothesis s: the first three indices of the sampler's 4-tuple for counter first + s (local as for launch_dlt4) and
+// GetHomography3PT without refinement on them; idx_out: M x 4 (the fourth column is -1); a fit that fails stores nine quiet NaNs
+hipError_t launch_propose_3pt(const Points& p, const double F[9], unsigned long long seed, long long first, int M,
+                              int* idx_out, double* H_out, hipStream_t s, Dlt4Local local = Dlt4Local{});
+
 // --- refine.hip -------------------------------------------------------------
 // points_only: step 1 alone (no affinity is read, a may be null), out is n x 4 (x1 y1 x2 y2) and every triangulated row is kept
 hipError_t launch_refine_points(const Points& p, const Affines& a, const double F[9], const double e1[2],
@@ -323,7 +329,7 @@ hipError_t launch_sel_pack_points(const Points& p, const unsigned char* mask, do
 // or its MSAC weight when `weights` (with its next_ / carried_ / left_ companions) is given; null = ranked by count.  The key
 // rank << 32 | ~position is built for eligible candidates only; the highest key wins.
 // one rank's offer in a round: 88 bytes, the unit of the sharded exchange
-struct SelRecord { unsigned long long key; double H[9]; int err; int mode; };      // mode: bit 0 the rank's residual mode, bit 1 refitted winners (key 30), bit 2 those refits by the 3-point estimator (mh_set_estimator), bits 3-14 the proposer's sampler, bit 15 ranked by MSAC weight: mh_select_greedy_msac, bit 16 the batch is mh_propose_haf's and bits 17-22 its members (capi_select.hip); the ranks' words must agree
+struct SelRecord { unsigned long long key; double H[9]; int err; int mode; };      // mode: bit 0 the rank's residual mode, bit 1 refitted winners (key 30), bit 2 those refits by the 3-point estimator (mh_set_estimator), bits 3-14 the proposer's sampler, bit 15 ranked by MSAC weight: mh_select_greedy_msac, bit 16 the batch is mh_propose_haf's and bits 17-22 its members, bit 23 the batch is mh_propose_3pt's (capi_select.hip); the ranks' words must agree
 static_assert(sizeof(SelRecord) == 88, "the exchanged record is 88 bytes");
 // scores_full (nullable): the first round's vector for the all-gather — the rank value of an eligible candidate, -1 otherwise
 hipError_t launch_sel_argmax(const int* counts, const int* weights, const int* orig, int Mc, int need, unsigned int my_off,

@@ -37,6 +37,8 @@
 #pragma weak mh_select_greedy_msac
 // ... and for the HAF proposals (SetProposalSource): without its entry point that source fails with a message.
 #pragma weak mh_propose_haf
+// ... and for the 3-point proposals (PROPOSAL_SOURCE_3PT): the same.
+#pragma weak mh_propose_3pt
 
 namespace {
 
@@ -280,8 +282,15 @@ bool MultiH::Run(bool points_only)
     }
     // where the initial batch comes from (looked at only where a batch is proposed)
     proposal_haf_run = false;
+    proposal_3pt_run = false;
     if (initial_homographies.empty() && init_mode != INIT_STABLE_SETS) {
-        if (proposal_source != PROPOSAL_SOURCE_DLT && proposal_source != PROPOSAL_SOURCE_HAF) {
+        if (proposal_source == PROPOSAL_SOURCE_3PT) {      // points and F are all it needs: the point-only Process() may use it
+            if (!mh_propose_3pt) {
+                std::cerr << "Error: the engine library has no 3-point proposals (mh_propose_3pt)\n";
+                return false;
+            }
+            proposal_3pt_run = true;
+        } else if (proposal_source != PROPOSAL_SOURCE_DLT && proposal_source != PROPOSAL_SOURCE_HAF) {
             std::cerr << "Error: unknown proposal source " << proposal_source << " (PROPOSAL_SOURCE_DLT or PROPOSAL_SOURCE_HAF)\n";
             return false;
         }
@@ -719,7 +728,9 @@ bool MultiH::ProposeInitialModels()
         return ok;
     }
     const bool ok = ProposeModels(proposal_seed, 0, proposal_hypotheses, proposal_max_models, mask);
-    if (ok && log_to_console)
+    if (ok && proposal_3pt_run && (log_to_console || std::getenv("MULTIH_TIMING") != nullptr))      // (part of the stage log too)
+        printf("[Multi-H] Proposed %d models from %d 3PT hypotheses\n", (int)cluster_homographies.size(), proposal_hypotheses);
+    else if (ok && log_to_console)
         printf("[Multi-H] Proposed %d models from %d DLT hypotheses\n", (int)cluster_homographies.size(),
                proposal_hypotheses);
     return ok;
@@ -733,7 +744,7 @@ bool MultiH::ApplyProposalSampler(bool local)
 }
 
 // `mask`: 1 = point still unexplained (in/out).  Appends the selected models to cluster_homographies.
-// One hypothesis batch -> mh_propose_dlt4 (this rank's shard of it) -> mh_select_greedy: scoring, arg-max, claiming
+// One hypothesis batch -> mh_propose_dlt4 (this rank's shard of it; mh_propose_3pt under PROPOSAL_SOURCE_3PT) -> mh_select_greedy: scoring, arg-max, claiming
 // the winner's inliers and pruning the candidates all stay on the device; per round the host reads three control
 // words.  Sharded (SetSharding): rank r owns counters [first + off_r, first + off_r + m_r); the ranks all-gather
 // their int32 score vectors and the H each offers through the caller's transport on DEVICE buffers, and the selection
@@ -749,6 +760,8 @@ bool MultiH::ProposeModels(uint64_t seed, long long first, int M, int max_models
     if (haf_batch_now) {      // an empty shard too: mh_propose_haf(.., 0, ..) keeps the batch's record, which every rank's selection compares
         if (!Check(mh_propose_haf(engine, first + off, mine, proposal_haf_stride, haf_members_run, sqr_threshold_homography), "mh_propose_haf"))
             return false;
+    } else if (proposal_3pt_run) {      // the initial and the iterative batches alike; an empty shard keeps the batch's record here too
+        if (!Check(mh_propose_3pt(engine, seed, first + off, mine), "mh_propose_3pt")) return false;
     } else if (mine > 0) {
         if (!Check(mh_propose_dlt4(engine, seed, first + off, mine), "mh_propose_dlt4")) return false;
     } else if (!Check(mh_set_models(engine, nullptr, 0), "mh_set_models")) {

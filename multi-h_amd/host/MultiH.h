@@ -170,7 +170,11 @@ public:
     // as a DLT batch is.  With members > 0 Process() builds the neighbour table once; if the local sampler is set as well the table
     // is the sampler's and members must not exceed its k.  The iterative batches and the degenerate tail stay DLT;
     // INIT_STABLE_SETS and SetInitialHomographies ignore the source; the point-only Process() refuses it (no affinities).
-    enum { PROPOSAL_SOURCE_DLT = 0, PROPOSAL_SOURCE_HAF = 1 };
+    // PROPOSAL_SOURCE_3PT (mh_propose_3pt): F-constrained 3-point hypotheses — the first three indices of the tuples the DLT route
+    // would draw (the same counters, seeds and SetProposalSampler), fitted with F by GetHomography3PT without refinement.  The INITIAL
+    // AND THE ITERATIVE batches come from it, with SetProposal's counts; members and stride are ignored.  It needs no affinities, so
+    // the point-only Process() accepts it.  The degenerate tail stays DLT.
+    enum { PROPOSAL_SOURCE_DLT = 0, PROPOSAL_SOURCE_HAF = 1, PROPOSAL_SOURCE_3PT = 2 };
     void SetProposalSource(int source, int members = 16, int stride = 1)
     {
         proposal_source = source; proposal_haf_members = members; proposal_haf_stride = stride;
@@ -274,6 +278,7 @@ protected:
     bool proposal_haf_run = false;        // this Process() call proposes its initial batch with mh_propose_haf
     int haf_members_run = 0;              // ... with this many members (reduced where there are fewer correspondences)
     bool haf_batch_now = false;           // the batch ProposeModels is about to propose is the HAF one
+    bool proposal_3pt_run = false;        // this Process() call proposes its batches with mh_propose_3pt
     bool point_only_run = false;                 // the last Process() was the point-only one
     int fixed_iterations = 0;
     int iter_hypotheses = 0, iter_max_new = 4;

@@ -33,9 +33,11 @@
 //                  [--sampler uniform|local[:k[:u]]]   the sampler of the proposal batches (MultiH::SetProposalSampler): uniform
 //                                4-tuples (default) or neighbourhood-guided ones from the k nearest neighbours (32) with u of
 //                                every 16 hypotheses left uniform (4)
-//                  [--proposals dlt|haf[:members[:stride]]]   where the initial hypotheses come from (MultiH::SetProposalSource): dlt,
+//                  [--proposals dlt|haf[:members[:stride]]|3pt]   where the initial hypotheses come from (MultiH::SetProposalSource): dlt,
 //                                the default, 4-point DLT hypotheses from sampled tuples; haf one hypothesis per `stride`-th affine
-//                                correspondence (1), refitted to its consistent ones among `members` nearest neighbours (16; 0 = none)
+//                                correspondence (1), refitted to its consistent ones among `members` nearest neighbours (16; 0 = none);
+//                                3pt (no arguments) F-constrained 3-point hypotheses from the first three indices of the DLT route's
+//                                tuples, for the initial and the iterative batches; works with --points
 //                  [--ranks N]   one process per GPU (rank r on device r), the hypothesis batches sharded over the ranks and
 //                                exchanged by RCCL (host/rccl_transport.cpp: ncclAllGather on the engine's stream); this
 //                                process becomes rank 0 and starts the others before anything touches the GPU.  Every rank
@@ -115,7 +117,7 @@ int main(int argc, char** argv)
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
                      "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] [--f-estimator ls8|minimal] "
-                     "[--stages file] [--points] [--estimator haf|3pt] [--data-term reference|rising] [--tail-score count|msac] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]] [--ranks n]\n";
+                     "[--stages file] [--points] [--estimator haf|3pt] [--data-term reference|rising] [--tail-score count|msac] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
         return 2;
     }
     double thrF = 2.6, thrH = 2.2, locality = 0.005, lambda = 0.5;     // M/main.cpp:55-59
@@ -182,7 +184,7 @@ int main(int argc, char** argv)
             if (!good) { std::cerr << "--sampler " << sv << ": uniform, local, local:k or local:k:u with whole numbers 3 <= k <= 32, 0 <= u <= 16\n"; return 2; }
         }
         else if (k == "--proposals") {
-            // dlt | haf | haf:members | haf:members:stride — whole numbers, nothing behind them
+            // dlt | haf | haf:members | haf:members:stride | 3pt — whole numbers, nothing behind them
             const std::string sv = v;
             auto whole = [](const std::string& t, int lo, int hi, int& out) {
                 if (t.empty() || t.size() > 7 || t.find_first_not_of("0123456789") != std::string::npos) return false;
@@ -192,6 +194,7 @@ int main(int argc, char** argv)
             bool good = true;
             int mm = 16, ss = 1;
             if (sv == "dlt") proposals = MultiH::PROPOSAL_SOURCE_DLT;
+            else if (sv == "3pt") proposals = MultiH::PROPOSAL_SOURCE_3PT;
             else if (sv.compare(0, 3, "haf") == 0 && (sv.size() == 3 || sv[3] == ':')) {
                 if (sv.size() > 3) {
                     const std::string rest = sv.substr(4);
@@ -203,7 +206,7 @@ int main(int argc, char** argv)
             }
             else good = false;
             if (!good) {
-                std::cerr << "--proposals " << sv << ": dlt, haf, haf:members or haf:members:stride with whole numbers, members 0 or 3 .. 32, stride >= 1\n";
+                std::cerr << "--proposals " << sv << ": dlt, 3pt, haf, haf:members or haf:members:stride with whole numbers, members 0 or 3 .. 32, stride >= 1\n";
                 return 2;
             }
         }
