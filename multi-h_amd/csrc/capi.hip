@@ -1,7 +1,8 @@
 // capi.hip — implementation of the C ABI declared in include/multih_hip.h.
-// Owns device buffers, the HIP stream and the per-kernel event timers; every
-// computation is a launch of a gfx950 kernel from this directory.  There is no
+// Every computation is a launch of a gfx950 kernel from this directory.  There is no
 // CPU fallback: without a usable HIP device mh_create fails (MH_ERR_NO_DEVICE).
+// The engine's device buffers, pinned blocks, streams and events are members that free themselves (the owners of
+// capi_engine.hpp): this file creates the engine and deletes it, and releases nothing by name.
 // r05: one translation unit per entry-point family; this one holds the life cycle, the inputs, the neighbourhood graph,
 // buffers, profiling and the tuning keys, and defines the helpers the families share (capi_engine.hpp).
 
@@ -22,10 +23,8 @@ void resolve_timers(mh_engine* e)
                 t.total_ms += ms;
                 t.launches += 1;
             }
-            (void)hipEventDestroy(pr.first);
-            (void)hipEventDestroy(pr.second);
         }
-        t.pending.clear();
+        t.pending.clear();                             // (destroys the events)
     }
 }
 
@@ -373,7 +372,7 @@ int mh_create(mh_engine** out, int device)
     if (!e) return fail(MH_ERR_INVALID, "out of host memory");
     e->device = device;
     e->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    hipError_t he = hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking);
+    hipError_t he = e->own_stream.ensure();
     if (he != hipSuccess) { delete e; return fail(MH_ERR_HIP, hipGetErrorString(he)); }
     e->stream = e->own_stream;
     *out = e;
@@ -381,63 +380,13 @@ int mh_create(mh_engine** out, int device)
     });
 }
 
+// Nothing is released by name: every resource is a member that frees itself (capi_engine.hpp).
 void mh_destroy(mh_engine* e)
 {
     if (!e) return;
     (void)hipSetDevice(e->device);
     (void)quiesce(e);
     resolve_timers(e);
-    e->x1.release(); e->y1.release(); e->x2.release(); e->y2.release();
-    e->a11.release(); e->a12.release(); e->a21.release(); e->a22.release();
-    e->d_rowptr.release(); e->d_col.release(); e->d_w.release(); e->d_rev.release();
-    e->H.release(); e->samples.release(); e->counts.release(); e->R.release(); e->C.release(); e->mask.release();
-    e->moments.release(); e->min_eig.release();
-    e->cp_pts.release(); e->cp_H.release(); e->cp_out.release(); e->cp_begin.release(); e->cp_tri.release(); e->cp_ok.release();
-    e->fund.release(); e->fund_one.release(); e->fund_samples.release(); e->fund_counts.release(); e->fund_nvalid.release(); e->fund_stop.release();
-    e->fund_inl.release(); e->fund_mask.release(); e->ref_keep.release(); e->ref_in.release(); e->ref_out.release();
-    e->loc_H.release(); e->loc_feat.release(); e->ms_data.release(); e->ms_mean.release();
-    e->ms_votes.release(); e->ms_out.release(); e->ms_list.release(); e->ms_pcnt.release(); e->ms_heads.release(); e->ms_tickets.release(); e->ms_partial.release();
-    e->cost.release(); e->labels_in.release(); e->labels_pts.release(); e->label_counts.release();
-    e->ew_label.release(); e->ew_cur.release(); e->ew_cap.release(); e->ew_excess.release();
-    e->ew_sink.release(); e->ew_height.release(); e->ew_decided.release(); e->ew_flags.release(); e->ew_acc.release();
-    e->ew_comp.release(); e->ew_comp_out.release();
-    e->ew_took.release(); e->ew_core.release(); e->ew_sent.release(); e->ew_trace.release(); e->ew_saved.release(); e->d_order.release(); e->d_wsum.release();
-    for (int k = 0; k < EXPAND_MAX_CTX - 1; ++k) { e->ewx_arcs[k].release(); e->ewx_sites[k].release(); e->ewx_core[k].release(); e->ewx_flags[k].release(); e->ewx_acc[k].release(); e->ewx_took[k].release(); }
-    e->ew_bctl.release(); e->ew_took_list.release();
-    if (e->h_batch) (void)hipHostFree(e->h_batch);
-    e->knn_tmp.release(); e->knn_part_i.release(); e->knn_part_d.release();
-    e->knn_cell.release(); e->knn_count.release(); e->knn_start.release(); e->knn_P.release(); e->knn_orig.release();
-    e->smp_nbr.release(); e->haf_used.release();
-    for (int c = 0; c < 4; ++c) e->sel_pts[c].release();
-    e->sel_pack_count.release();
-    for (int c = 0; c < 4; ++c) e->sel_gone[c].release();
-    e->sel_carried[0].release(); e->sel_carried[1].release(); e->sel_left.release();
-    e->sel_weights.release(); e->sel_carried_w[0].release(); e->sel_carried_w[1].release(); e->sel_left_w.release();
-    e->gb_deg.release(); e->gb_start.release(); e->gb_cursor.release(); e->gb_raw.release(); e->gb_mult.release();
-    e->gb_uniq.release(); e->gb_info.release(); e->gb_hits_rp.release(); e->gb_hits_col.release();
-    if (e->h_flags) (void)hipHostFree(e->h_flags);
-    if (e->h_ms) (void)hipHostFree(e->h_ms);
-    if (e->h_ms_list) (void)hipHostFree(e->h_ms_list);
-    if (e->h_acc) (void)hipHostFree(e->h_acc);
-    if (e->h_sel) (void)hipHostFree(e->h_sel);
-    for (int b = 0; b < 2; ++b) { e->sel_orig[b].release(); e->sel_cand_H[b].release(); }
-    e->sel_counts.release(); e->sel_rec.release(); e->sel_scores.release(); e->sel_gathered.release(); e->sel_out_H.release();
-    e->sel_records.release(); e->sel_counter.release(); e->sel_keys.release(); e->sel_refit.release(); e->sel_refit_ctr.release(); e->r3_scratch.release();
-    e->ms_partial2.release(); e->ms_ctl.release(); e->ms_pcnt2.release(); e->ms_ticks.release();
-    for (int q = 0; q < mh_engine::PF_DEPTH; ++q) { e->pf_H[q].release(); e->pf_samples[q].release(); if (e->pf_ev[q]) (void)hipEventDestroy(e->pf_ev[q]); }
-    e->best_key.release(); e->H32.release(); e->fb_pairs.release();
-    e->weights.release(); e->weights_counts.release();
-    if (e->h_best) (void)hipHostFree(e->h_best);
-    if (e->h_best_w) (void)hipHostFree(e->h_best_w);
-    if (e->ev_main) (void)hipEventDestroy(e->ev_main);
-    if (e->ev_side_pre) (void)hipEventDestroy(e->ev_side_pre);
-    if (e->side_stream) { (void)hipStreamSynchronize(e->side_stream); (void)hipStreamDestroy(e->side_stream); }
-    if (e->xchg_stream) { (void)hipStreamSynchronize(e->xchg_stream); (void)hipStreamDestroy(e->xchg_stream); }
-    if (e->ev_sweep) (void)hipEventDestroy(e->ev_sweep);
-    for (int b = 0; b < 3; ++b) if (e->ev_x[b]) (void)hipEventDestroy(e->ev_x[b]);
-    e->counts_alt[0].release(); e->counts_alt[1].release(); e->sweep_ctl.release();
-    for (hipStream_t d : e->dummy_streams) (void)hipStreamDestroy(d);
-    if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
     delete e;
 }
 
@@ -461,7 +410,7 @@ int mh_set_stream(mh_engine* e, void* hip_stream, int external)
     int rcq = quiesce(e);
     if (rcq) return rcq;
     resolve_timers(e);
-    e->stream = external ? (hipStream_t)hip_stream : e->own_stream;
+    e->stream = external ? (hipStream_t)hip_stream : e->own_stream.s;
     return MH_OK;
     });
 }
@@ -500,8 +449,7 @@ int mh_set_correspondences(mh_engine* e, const double* src_xy, const double* dst
     HIPCHK(e->x2.reserve(cap)); HIPCHK(e->y2.reserve(cap));
     HIPCHK(e->a11.reserve(cap)); HIPCHK(e->a12.reserve(cap));
     HIPCHK(e->a21.reserve(cap)); HIPCHK(e->a22.reserve(cap));
-    struct Staging { DevBuf<double> b; ~Staging() { b.release(); } } st_s, st_d, st_a;   // freed on every return path
-    DevBuf<double>&s = st_s.b, &d = st_d.b, &a = st_a.b;
+    DevBuf<double> s, d, a;                             // staging, freed on every return path
     HIPCHK(s.reserve((size_t)n * 2));
     HIPCHK(d.reserve((size_t)n * 2));
     HIPCHK(hipMemcpyAsync(s.p, src_xy, sizeof(double) * 2 * n, hipMemcpyHostToDevice, e->stream));
@@ -518,8 +466,8 @@ int mh_set_correspondences(mh_engine* e, const double* src_xy, const double* dst
     if (n != e->n) {
         // everything sized by the previous point set is stale: the residual matrix and its pitch, the sampled batch,
         // the fundamental-matrix hypotheses
-        e->m = 0; e->ldr = 0; e->have_samples = false; e->haf_batch = false; e->p3_batch = false; e->fm = 0; e->f7_m = 0;
-        e->counts_fresh = false; ++e->models_seq;
+        drop_models(e);
+        e->ldr = 0; e->fm = 0; e->f7_m = 0;
     }
     {
         double xmin = src_xy[0], xmax = src_xy[0], ymin = src_xy[1], ymax = src_xy[1], dmax = 0.0;
@@ -704,8 +652,7 @@ int mh_build_neighbors_radius(mh_engine* e, double radius, long long max_hits, l
         return fail(MH_ERR_OVERFLOW, msg);
     }
     for (int i = 0; i < n; ++i) rowptr[i + 1] = rowptr[i] + cnt[i];
-    struct Scratch { DevBuf<int> b; ~Scratch() { b.release(); } } s_rp, s_col;
-    DevBuf<int>&d_rp = s_rp.b, &d_col = s_col.b;
+    DevBuf<int> d_rp, d_col;
     HIPCHK(d_rp.reserve((size_t)n + 1));
     HIPCHK(d_col.reserve((size_t)std::max<long long>(total, 1)));
     HIPCHK(hipMemcpyAsync(d_rp.p, rowptr.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, e->stream));

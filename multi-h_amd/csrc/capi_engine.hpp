@@ -6,6 +6,15 @@
 //   capi_propose.hip  HAF proposals: a hypothesis per affine correspondence (mh_propose_haf, mh_get_haf_support); 3-point proposals (mh_propose_3pt)
 //   capi_select.hip   transport, greedy selection, best model of a batch (the score exchange)
 //   capi_label.hip    data cost, alpha-expansion, re-estimation, LabelingStep, post-filter statistics
+//
+// Ownership: every HIP resource of an engine sits in an owner defined here (DevBuf, PinnedBuf, Stream, Event) whose destructor
+// gives it back; the capi*.hip files allocate, create, free and destroy nothing themselves, and mh_destroy is: set the device,
+// quiesce, resolve the timers, delete the engine.  (e->stream is a raw handle: it may be the caller's.)
+// The resident batch: what the model set is — how many models, who proposed them, whether their samples are resident — is one
+// record (ResidentBatch); drop_models and install_models are the only code that writes it and what hangs on it (cost_L,
+// counts_fresh, models_seq).  Every entry point that installs a model set validates its arguments with the resident set
+// untouched, then: drop_models, reserve, launch or copy, install_models.  So after a failed allocation or launch inside an
+// installer the engine holds an EMPTY model set, on every route: never a record of buffers that were freed or swapped.
 #pragma once
 #include "../../include/multih_hip.h"
 #include "mh_kernels.hpp"
@@ -41,10 +50,21 @@ inline int fail(int code, const std::string& msg)
             return fail(MH_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
     } while (0)
 
+// No owner can be copied (a copy would give its resource back twice); DevBuf and Event can be moved, and a moved-from one holds nothing.
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy&) = delete;
+    NoCopy& operator=(const NoCopy&) = delete;
+};
+
 template <class T>
-struct DevBuf {
+struct DevBuf : NoCopy {
     T* p = nullptr;
     size_t cap = 0;        // elements
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }     // (o frees what this held)
+    ~DevBuf() { if (p) (void)hipFree(p); }
     hipError_t reserve(size_t n)
     {
         if (n <= cap) return hipSuccess;
@@ -53,18 +73,79 @@ struct DevBuf {
         if (e == hipSuccess) cap = n;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// A pinned host block: device-mapped (the device's address of it in d) or plain pinned (the target of copies; d stays null).
+// Allocated on first use, zeroed; a larger request later replaces it (contents are not kept).
+template <class T>
+struct PinnedBuf : NoCopy {
+    T* h = nullptr;
+    T* d = nullptr;
+    size_t cap = 0;        // elements
+    ~PinnedBuf() { if (h) (void)hipHostFree(h); }
+    hipError_t ensure(size_t n, bool mapped = true)
+    {
+        if (n <= cap) return hipSuccess;
+        if (h) { (void)hipHostFree(h); h = d = nullptr; cap = 0; }
+        hipError_t e = hipHostMalloc((void**)&h, n * sizeof(T), mapped ? hipHostMallocMapped : hipHostMallocDefault);
+        if (e == hipSuccess && mapped) e = hipHostGetDevicePointer((void**)&d, h, 0);
+        if (e != hipSuccess) { if (h) (void)hipHostFree(h); h = d = nullptr; return e; }
+        std::memset(h, 0, n * sizeof(T));
+        cap = n;
+        return hipSuccess;
+    }
+};
+
+struct Event : NoCopy {
+    hipEvent_t ev = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : ev(o.ev) { o.ev = nullptr; }
+    Event& operator=(Event&& o) noexcept { std::swap(ev, o.ev); return *this; }
+    ~Event() { if (ev) (void)hipEventDestroy(ev); }
+    hipError_t ensure(unsigned flags = hipEventDisableTiming) { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, flags); }
+    operator hipEvent_t() const { return ev; }
+};
+
+struct Stream : NoCopy {
+    hipStream_t s = nullptr;
+    ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    hipError_t ensure(bool highest_priority = false)
+    {
+        if (s) return hipSuccess;
+        if (!highest_priority) return hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+        int lo = 0, hi = 0;
+        hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
+        return e != hipSuccess ? e : hipStreamCreateWithPriority(&s, hipStreamNonBlocking, hi);
+    }
+    operator hipStream_t() const { return s; }
 };
 
 struct KernelTimer {
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+    std::vector<std::pair<Event, Event>> pending;
     int launches = 0;
     double total_ms = 0.0;
 };
 
-struct mh_engine {
+// The resident model set: the one record of it.  Written by drop_models / install_models (below) and by nothing else.
+enum class BatchOrigin { GIVEN, DLT4, HAF, P3 };      // the caller's models (mh_set_models), or none; mh_propose_dlt4 / mh_adopt_prefetched; mh_propose_haf; mh_propose_3pt
+struct ResidentBatch {
+    int m = 0;
+    BatchOrigin origin = BatchOrigin::GIVEN;           // travels in the selection records' mode word (the table beside SelRecord, mh_kernels.hpp)
+    int haf_members = 0;                               // of a HAF batch: the `members` it was proposed with
+    bool have_samples = false;                         // `samples` holds the batch's index tuples (mh_get_samples)
+};
+
+// A counts buffer that waits for its turn: two of them beside the current one (mh_engine::counts, counts_zeroed)
+struct CountsSlot {
+    DevBuf<int> buf;
+    bool zeroed = false;                               // cleared behind the exchange that last read it (the next sweep skips its memset)
+    int wait = -1;                                     // which ev_x that exchange records (-1: none)
+};
+
+struct mh_engine : ResidentBatch {                    // (e->m, e->origin, e->haf_members, e->have_samples: read anywhere)
     int device = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    Stream own_stream;
+    hipStream_t stream = nullptr;                      // where the engine enqueues: own_stream, or the caller's (mh_set_stream) — not owned
     // MultiH ctor members, M/MultiH.cpp:10-21
     double thr_F = 3.0, thr_H = 2.5, locality = 0.002, lambda = 0.5;
     int min_inliers = 0;
@@ -82,16 +163,9 @@ struct mh_engine {
     int order_n = -1;                        // d_order holds the solver's site order for this many sites
     DevBuf<int> d_rowptr, d_col, d_w, d_rev;
 
-    // model set
-    int m = 0;
-    bool have_samples = false;
+    // model set (its record: ResidentBatch)
     DevBuf<double> H, H_one;
     DevBuf<int> samples, counts;
-    // how the resident batch was proposed (mh_propose_haf): mh_set_models, mh_propose_dlt4 and mh_adopt_prefetched clear the record;
-    // the selection records carry it (bit 16 and bits 17-22 of their mode word)
-    bool haf_batch = false;
-    int haf_members = 0;
-    bool p3_batch = false;                   // the resident batch is mh_propose_3pt's (bit 23 of the mode word); cleared by the same three and by mh_propose_haf
     DevBuf<unsigned> haf_used;               // per hypothesis of a HAF batch, the mask of consistent neighbours (mh_get_haf_support)
     DevBuf<double> R;
     long long ldr = 0;
@@ -115,8 +189,8 @@ struct mh_engine {
     mh_allgather_dev_fn t_host_fn = nullptr;
     void* t_ctx = nullptr;
     // pipelined propose (mh_prefetch_dlt4): the spare batch and the second stream it is prepared on
-    hipStream_t side_stream = nullptr;
-    hipEvent_t ev_main = nullptr, ev_side_pre = nullptr;
+    Stream side_stream;
+    Event ev_main, ev_side_pre;
     int tune_score32_resident = 12;          // key 24: the FP32 pre-test score as a resident grid with n point slices (12: 1.98 ms against 2.14 hardware-dispatched at 50k x 100k, tools/score32_probe.py); 0 = hardware dispatch, -1 = ~37 500 items
     int occ_score32 = -1, occ_cost32 = -1;   // workgroups per compute unit of the resident score / cost kernels on THIS engine's device (-1: not asked yet)
     int tune_cost32_batched = 0;             // key 28: 1 = experiment: k_cost32 evaluates the near pairs of several models together (score32.hip, cost32_wg_batched; slower: 4.45 vs 4.10 ms)
@@ -125,7 +199,7 @@ struct mh_engine {
     int tune_dlt_variant = 0;                // key 25: 0 = by context (below), 1 = the LDS-staged proposer everywhere, 2 = the register-resident one everywhere (same bits)
     int tune_cost32_resident = 8;            // key 23: the int32 cost matrix as a resident grid with n point slices (8: 4.12 ms against 4.25 hardware-dispatched at 50k x 100k, tools/cost32_probe.py); 0 = hardware dispatch, -1 = ~37 500 items
     int tune_stream_shift = 0;               // key 22 (experiment): dummy streams created in front of the second / third stream (shifts their hardware queue / pipe)
-    std::vector<hipStream_t> dummy_streams;
+    Stream dummy_streams[16];                // (key 22 admits 0 .. 16)
     int tune_dlt_first = 1;                  // key 20: the sweep waits until the second stream has reached the pending DLT's dispatch (1) or not (0)
     // up to two prefetched batches wait in a FIFO (r04: with the batch after next prepared too, the DLT a sweep has to wait
     // for was dispatched a whole sweep earlier — nothing is handed from stream to stream between two sweeps)
@@ -133,29 +207,25 @@ struct mh_engine {
     DevBuf<double> pf_H[PF_DEPTH];
     DevBuf<int> pf_samples[PF_DEPTH];
     int pf_m[PF_DEPTH] = { 0, 0 };
-    hipEvent_t pf_ev[PF_DEPTH] = { nullptr, nullptr };   // recorded behind the slot's DLT on the second stream
+    Event pf_ev[PF_DEPTH];                               // recorded behind the slot's DLT on the second stream
     int pf_head = 0, pf_count = 0;                       // oldest queued slot, number of queued batches
     // best model of a scored batch (mh_select_best).  The (all-gather +) arg-max of batch i runs on a third stream behind an
     // event of sweep i, so sweep i+1 starts at once: the batch's counts buffer goes to the exchange and the next sweep
     // writes the other one (r04)
-    hipStream_t xchg_stream = nullptr;
-    hipEvent_t ev_sweep = nullptr, ev_x[3] = { nullptr, nullptr, nullptr };
-    // two counts buffers wait in a FIFO beside the current one: a buffer handed to exchange k comes back for sweep k + 3, so an
-    // exchange has TWO sweeps to finish in before anything waits for it (with one spare buffer it had one)
-    DevBuf<int> counts_alt[2];
-    int counts_alt_wait[2] = { -1, -1 };          // which ev_x the buffer's last exchange records (-1: none)
+    Stream xchg_stream;
+    Event ev_sweep, ev_x[3];
+    // two counts buffers wait in a FIFO beside the current one ([0] the longer): a buffer handed to exchange k comes back for sweep
+    // k + 3, so an exchange has TWO sweeps to finish in before anything waits for it (with one spare buffer it had one).
+    // hand_counts_to_exchange (below) is the hand-over.
+    CountsSlot counts_waiting[2];
     long long xchg_calls = 0;                  // exchanges enqueued on xchg_stream so far (parity selects ev_x)
     long long models_seq = 0, best_models_seq = -1;   // model-set generation; the one the last mh_select_best result belongs to
-    bool counts_zeroed_alt[2] = { false, false };   // the same for the two waiting buffers
     bool counts_zeroed = false;                // the current counts buffer was cleared behind the exchange that last read it (the next sweep skips its memset)
     bool counts_fresh = false;                 // the current counts buffer holds the scores of the current model set (a scoring call wrote it)
     bool xchg_pending = false;                 // something enqueued on xchg_stream since the last host wait for it
-    DevBuf<unsigned long long> best_key;
-    int* h_best = nullptr;                     // mapped pinned: count, global index, sequence number
-    int* h_best_dev = nullptr;
+    PinnedBuf<int> h_best;                     // count, global index, sequence number, error word
     int best_seq = 0;
-    int* h_sel = nullptr;                      // mapped pinned mirror of the control words
-    int* h_sel_dev = nullptr;
+    PinnedBuf<int> h_sel;                      // mirror of the control words
     long long copies_h2d = 0, copies_d2h = 0;  // explicit host<->device copies issued by mh_select_greedy (mh_get_copy_stats)
 
     // epipolar front half
@@ -207,8 +277,7 @@ struct mh_engine {
     DevBuf<long long> ewx_acc[EXPAND_MAX_CTX - 1];
     DevBuf<unsigned char> ewx_took[EXPAND_MAX_CTX - 1];
     DevBuf<int> ew_bctl, ew_took_list;
-    int* h_batch = nullptr;                  // mapped pinned: k_commit's publication
-    int* h_batch_dev = nullptr;
+    PinnedBuf<int> h_batch;                  // k_commit's publication
     int tune_expand_ctx = 16;                // key 37: alpha-moves solved together (1 = one after the other, the form until r05)
     int tune_batch_min_labels = 16;          // key 38: label sets of at least this many labels are batched from the first cycle on (smaller ones from the second)
     int tune_batch_spw = 0;                  // key 39: sites per wave in the setup and reduction launches of a batch of moves (16 / 32 / 64; 0 = by the size of the launch); schedule only
@@ -225,14 +294,10 @@ struct mh_engine {
     int inject_barrier_timeouts = 0;         // test hook: the next n expansions' first attempts count as timed out
     int inject_solve_failure = 0;            // test hook (key 40): (group << 4) | context of the next expansion's solve marked failed
     DevBuf<long long> ew_acc;
-    int* h_flags = nullptr;
-    MeanShiftResultBlock* h_ms = nullptr;      // mapped pinned result block of the mean-shift climbs
-    MeanShiftResultBlock* h_ms_dev = nullptr;
-    int* h_ms_list = nullptr;                  // pinned: the (row, votes) lists of a batch's climbs, packed (grows with the need)
-    size_t h_ms_list_pairs = 0;
-    long long* h_acc = nullptr;
-    int* h_flags_dev = nullptr;
-    long long* h_acc_dev = nullptr;
+    PinnedBuf<int> h_flags;
+    PinnedBuf<long long> h_acc;
+    PinnedBuf<MeanShiftResultBlock> h_ms;      // the result blocks of the mean-shift climbs, then 3 ints per climb (seed rows, list offsets, list lengths)
+    PinnedBuf<int> h_ms_list;                  // not mapped: the (row, votes) lists of a batch's climbs, packed (grows with the need)
     DevBuf<double> sel_pts[4];               // the active points of a greedy-selection round, packed (select.hip)
     DevBuf<int> sel_pack_count;
     DevBuf<double> sel_gone[4];              // the points the last claim of a greedy-selection round took out of the support set, packed
@@ -279,8 +344,7 @@ struct mh_engine {
     // and the model-set generation both were computed for (-1: none; mh_set_correspondences resets it)
     DevBuf<int> weights, weights_counts;
     long long weights_models_seq = -1;
-    int* h_best_w = nullptr;                   // mapped pinned: mh_select_best_msac's weight, index, sequence number, error word
-    int* h_best_w_dev = nullptr;
+    PinnedBuf<int> h_best_w;                   // mh_select_best_msac's weight, index, sequence number, error word
     Points pts() const { return Points{ x1.p, y1.p, x2.p, y2.p, n, bbox[0], bbox[1], bbox[2], bbox[3] }; }
 };
 
@@ -306,20 +370,56 @@ struct ScopedTimer {
     mh_engine* e;
     int k;
     hipStream_t st;
-    hipEvent_t a = nullptr, b = nullptr;
-    ScopedTimer(mh_engine* e_, int k_, hipStream_t on = nullptr) : e(e_), k(k_), st(on ? on : e_->stream)
+    Event a, b;
+    bool on = false;                                   // both events exist and `a` is recorded
+    ScopedTimer(mh_engine* e_, int k_, hipStream_t on_stream = nullptr) : e(e_), k(k_), st(on_stream ? on_stream : e_->stream)
     {
-        if (!e->profiling) return;
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
+        if (!e->profiling || a.ensure(hipEventDefault) != hipSuccess || b.ensure(hipEventDefault) != hipSuccess) return;
         (void)hipEventRecord(a, st);
+        on = true;
     }
     ~ScopedTimer()
     {
-        if (!a) return;
+        if (!on) return;
         (void)hipEventRecord(b, st);
-        e->timers[k].pending.emplace_back(a, b);
+        e->timers[k].pending.emplace_back(std::move(a), std::move(b));
     }
 };
+
+// ---- the resident batch: the two functions that change it ----
+// No model set: what every installer leaves behind when it fails after this point, and what mh_set_correspondences leaves for a
+// new point count.  One new generation (models_seq) per installing call — install_models does not count again.
+inline void drop_models(mh_engine* e)
+{
+    static_cast<ResidentBatch&>(*e) = ResidentBatch{};
+    e->cost_L = 0;
+    e->counts_fresh = false;
+    ++e->models_seq;
+}
+
+// The buffers hold the batch: commit its record (behind drop_models, the reservations and the launch or copy).
+inline void install_models(mh_engine* e, int m, BatchOrigin origin, bool have_samples, int haf_members = 0)
+{
+    static_cast<ResidentBatch&>(*e) = ResidentBatch{ m, origin, haf_members, have_samples };
+}
+
+// ---- the counts buffers ----
+// a scoring call has written the current buffer
+inline void counts_scored(mh_engine* e) { e->counts_fresh = true; e->counts_zeroed = false; }
+
+// The current buffer stays with the exchange that records ev_x[par] and clears it; the buffer that has waited longest becomes the
+// current one.  Returns which ev_x the main stream has to wait for before it writes that one (-1: none).
+inline int hand_counts_to_exchange(mh_engine* e, int par)
+{
+    CountsSlot* w = e->counts_waiting;
+    const int wait = w[0].wait;
+    std::swap(e->counts, w[0].buf);
+    e->counts_zeroed = w[0].zeroed;
+    w[0].zeroed = true;
+    w[0].wait = par;
+    std::swap(w[0], w[1]);
+    return wait;
+}
 
 // ---- shared helpers (defined in capi.hip unless noted) ----
 void resolve_timers(mh_engine* e);
@@ -339,7 +439,7 @@ int msac_models(mh_engine* e, const Points& p, const double* Hs, int m, double t
                 int* weights_dev, bool plain_variant_only);
 // the engine's re-estimator over labels_dev (n ints) for models H_dev (Nh x 9, in place) — HAF or 3-point (capi_label.hip)
 int launch_estimator(mh_engine* e, const int* labels_dev, int Nh, double* H_dev, int* counts_dev);
-// the exchange's stream and events (capi_select.hip); the second stream of the prefetch queue (capi_score.hip)
+// the exchange's stream and events (capi_select.hip); the second stream of the prefetch queue and its events (capi_score.hip)
 int ensure_xchg_stream(mh_engine* e);
 int ensure_side_stream(mh_engine* e);
 

@@ -353,26 +353,21 @@ int mh_mean_shift(mh_engine* e, const double* data, int n, int d, double band_wi
                      e->ms_partial.p, e->ms_pcnt.p };
     const double band_sq = band_width * band_width;                 // MeanShiftClustering.h:31
     const double stop_thresh = 1e-3 * band_width;                   // :48
-    if (!e->h_ms) {                                                 // B result blocks, then the B seed rows, list offsets and list lengths
-        HIPCHK(hipHostMalloc((void**)&e->h_ms, sizeof(MeanShiftResultBlock) * B + sizeof(int) * 3 * B, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer((void**)&e->h_ms_dev, e->h_ms, 0));
-    }
+    // B result blocks, then the B seed rows, list offsets and list lengths (3 B ints, in whole blocks' worth of room)
+    HIPCHK(e->h_ms.ensure(B + (sizeof(int) * 3 * B + sizeof(MeanShiftResultBlock) - 1) / sizeof(MeanShiftResultBlock)));
+    MeanShiftResultBlock* const h_ms = e->h_ms.h;
     // the (row, votes) lists of a batch travel packed, in one copy of exactly their pairs; the pinned buffer grows with the need
     auto list_room = [&](size_t pairs) -> hipError_t {
-        if (pairs <= e->h_ms_list_pairs) return hipSuccess;
-        size_t want = std::max<size_t>(pairs, std::max<size_t>(1 << 16, 2 * e->h_ms_list_pairs));
-        if (e->h_ms_list) { (void)hipHostFree(e->h_ms_list); e->h_ms_list = nullptr; e->h_ms_list_pairs = 0; }
-        const hipError_t he = hipHostMalloc((void**)&e->h_ms_list, sizeof(int) * 2 * want, hipHostMallocDefault);
-        if (he == hipSuccess) e->h_ms_list_pairs = want;
-        return he;
+        if (2 * pairs <= e->h_ms_list.cap) return hipSuccess;
+        return e->h_ms_list.ensure(2 * std::max<size_t>(pairs, std::max<size_t>(1 << 16, e->h_ms_list.cap)), false);
     };
     HIPCHK(e->ms_tickets.reserve((size_t)B));
     HIPCHK(e->ms_ctl.reserve((size_t)3 * B));
     HIPCHK(e->ms_partial2.reserve((size_t)B * 2 * 64 * 16));
     HIPCHK(e->ms_pcnt2.reserve((size_t)B * 2 * 64));
     HIPCHK(hipMemsetAsync(e->ms_tickets.p, 0, sizeof(int) * (size_t)B, e->stream));
-    int* const starts = reinterpret_cast<int*>(e->h_ms + B);
-    const int* const starts_dev = reinterpret_cast<const int*>(e->h_ms_dev + B);
+    int* const starts = reinterpret_cast<int*>(h_ms + B);
+    const int* const starts_dev = reinterpret_cast<const int*>(e->h_ms.d + B);
     int* const list_off = starts + B;
     int* const list_len = starts + 2 * B;
 
@@ -499,33 +494,33 @@ int mh_mean_shift(mh_engine* e, const double* data, int n, int d, double band_wi
                     keep = std::min(e->tune_ms_persist, room / std::min(64, (n + 255) / 256));
                 }
                 HIPCHK(launch_ms_indexed(w, active, n_active, starts_dev, ix, band_sq, stop_thresh, MS_MAX_ITERS_PER_LAUNCH, e->tune_ms_dense,
-                                         keep, e->ms_ctl.p, e->h_ms_dev, e->stream, ms_stats ? e->ms_ticks.p + 5 : nullptr));
+                                         keep, e->ms_ctl.p, e->h_ms.d, e->stream, ms_stats ? e->ms_ticks.p + 5 : nullptr));
                 ++e->ms_indexed_launches;
             } else if (G > 0) {
                 HIPCHK(launch_ms_persist(w, active, n_active, band_sq, stop_thresh, MS_MAX_ITERS_PER_LAUNCH, e->ms_ctl.p, e->ms_partial2.p, e->ms_pcnt2.p,
-                                         e->h_ms_dev, e->stream, ms_stats ? e->ms_ticks.p : nullptr));
+                                         e->h_ms.d, e->stream, ms_stats ? e->ms_ticks.p : nullptr));
                 ++e->ms_persist_launches;
                 st_G += G;
             } else {
                 HIPCHK(launch_ms_climb(w, active, n_active, round == 0 ? starts_dev : nullptr, band_sq, stop_thresh, e->tune_ms_batch,
-                                       e->h_ms_dev, e->ms_tickets.p, e->stream));
+                                       e->h_ms.d, e->ms_tickets.p, e->stream));
             }
             HIPCHK(hipStreamSynchronize(e->stream));
             if (ms_stats) {
                 const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_round).count();
                 long long its = 0;
-                for (int a = 0; a < n_active; ++a) its = std::max<long long>(its, e->h_ms[active.climb[a]].out[0] - iters_seen[active.climb[a]]);
+                for (int a = 0; a < n_active; ++a) its = std::max<long long>(its, h_ms[active.climb[a]].out[0] - iters_seen[active.climb[a]]);
                 if (G > 0) { st_persist_us += us; st_persist_iters += its; ++st_persist_rounds; st_persist_climbs += active_in; }
                 else { st_launch_us += us; ++st_launch_rounds; if (round > 0) { st_tail_us += us; st_tail_climbs += active_in; } }
             }
             int still = 0;
             for (int a = 0; a < n_active; ++a) {
                 const int b = active.climb[a];
-                if (!e->h_ms[b].out[1] && !e->h_ms[b].out[3]) {
-                    if (G > 0 && e->h_ms[b].out[0] == iters_seen[b]) { persist_ok = false; ++e->ms_persist_fallbacks; }   // its gate closed
+                if (!h_ms[b].out[1] && !h_ms[b].out[3]) {
+                    if (G > 0 && h_ms[b].out[0] == iters_seen[b]) { persist_ok = false; ++e->ms_persist_fallbacks; }   // its gate closed
                     active.climb[still++] = (unsigned char)b;
                 }
-                iters_seen[b] = e->h_ms[b].out[0];
+                iters_seen[b] = h_ms[b].out[0];
             }
             n_active = still;
         }
@@ -540,7 +535,7 @@ int mh_mean_shift(mh_engine* e, const double* data, int n, int d, double band_wi
         int longest = 0;
         size_t total = 0;
         for (int b = 0; b < climbs; ++b) {
-            const int len = std::max(0, e->h_ms[b].out[2]);
+            const int len = std::max(0, h_ms[b].out[2]);
             list_off[b] = (int)total;
             list_len[b] = len;
             total += (size_t)len;
@@ -551,21 +546,21 @@ int mh_mean_shift(mh_engine* e, const double* data, int n, int d, double band_wi
             HIPCHK(e->ms_heads.reserve(2 * total));
             HIPCHK(list_room(total));
             HIPCHK(launch_ms_pack(w, climbs, longest, starts_dev + B, starts_dev + 2 * B, e->ms_heads.p, e->stream));
-            HIPCHK(hipMemcpyAsync(e->h_ms_list, e->ms_heads.p, sizeof(int) * 2 * total, hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(hipMemcpyAsync(e->h_ms_list.h, e->ms_heads.p, sizeof(int) * 2 * total, hipMemcpyDeviceToHost, e->stream));
             HIPCHK(hipStreamSynchronize(e->stream));
         }
         // apply the climbs in draw order; one whose seed an earlier climb of the batch has visited never started in
         // the reference's terms and is dropped
         if (ms_stats)
-            for (int b = 0; b < climbs; ++b) st_climbs.emplace_back(e->h_ms[b].out[0], e->h_ms[b].out[2]);
+            for (int b = 0; b < climbs; ++b) st_climbs.emplace_back(h_ms[b].out[0], h_ms[b].out[2]);
         const auto t_apply = std::chrono::steady_clock::now();
         for (int b = 0; b < climbs; ++b) {
             const int st = starts[b];
             if (visited[st]) continue;
-            const int* out = e->h_ms[b].out;
-            const double* mean = e->h_ms[b].mean;
+            const int* out = h_ms[b].out;
+            const double* mean = h_ms[b].mean;
             const int len = out[2];
-            const int* list = e->h_ms_list + 2 * (size_t)list_off[b];
+            const int* list = e->h_ms_list.h + 2 * (size_t)list_off[b];
             std::vector<std::pair<int, int>> mine(len);
             for (int k = 0; k < len; ++k) {
                 mine[k] = { list[2 * k], list[2 * k + 1] };

@@ -29,14 +29,8 @@ int ensure_expand_work(mh_engine* e)
     HIPCHK(e->ew_acc.reserve(EXPAND_ACC_WORDS));
     HIPCHK(e->ew_took.reserve((size_t)n + 2));
     HIPCHK(e->ew_core.reserve((size_t)EXPAND_CORE_SHARDS * n));
-    if (!e->h_flags) {
-        HIPCHK(hipHostMalloc((void**)&e->h_flags, sizeof(int) * EXPAND_HOST_WORDS, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer((void**)&e->h_flags_dev, e->h_flags, 0));
-    }
-    if (!e->h_acc) {
-        HIPCHK(hipHostMalloc((void**)&e->h_acc, sizeof(long long) * 16, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer((void**)&e->h_acc_dev, e->h_acc, 0));
-    }
+    HIPCHK(e->h_flags.ensure(EXPAND_HOST_WORDS));
+    HIPCHK(e->h_acc.ensure(16));
     // r06: the contexts of the concurrent moves (key 37).  Fresh memory is cleared once: a context's capacities and flow counters
     // are read for arcs the current move has not written only together with verdicts that make them irrelevant (expand.hip), but
     // the control words' rings and tickets must start at zero (k_ctl_init) and nothing is gained by leaving the rest to chance.
@@ -57,11 +51,7 @@ int ensure_expand_work(mh_engine* e)
     if (extra > 0) {
         HIPCHK(e->ew_bctl.reserve(8 + EXPAND_MAX_CTX));
         HIPCHK(e->ew_took_list.reserve((size_t)n + 2));
-        if (!e->h_batch) {
-            HIPCHK(hipHostMalloc((void**)&e->h_batch, sizeof(int) * 8, hipHostMallocMapped));
-            HIPCHK(hipHostGetDevicePointer((void**)&e->h_batch_dev, e->h_batch, 0));
-            for (int i = 0; i < 8; ++i) e->h_batch[i] = 0;
-        }
+        HIPCHK(e->h_batch.ensure(8));
     }
     return MH_OK;
 }
@@ -110,7 +100,7 @@ int do_expand(mh_engine* e, const int* init_dev, long long* energy, int* cycles)
     int solve_grid = std::max(1, std::min(e->tune_expand[3], e->solve_grid_max));
     ExpandWork w{ e->ew_label.p, e->ew_cur.p, e->ew_cap.p, e->ew_sent.p, e->ew_excess.p, e->ew_sink.p,
                   e->ew_height.p, e->ew_decided.p, e->ew_took.p, e->ew_core.p, e->ew_flags.p, e->ew_acc.p,
-                  e->h_flags, e->h_acc, e->h_flags_dev, e->h_acc_dev,
+                  e->h_flags.h, e->h_acc.h, e->h_flags.d, e->h_acc.d,
                   e->tune_expand[0], e->tune_expand[1], e->tune_expand[2], solve_grid, e->tune_push_mult, e->tune_reduce, e->tune_reduce_launches,
                   e->tune_cascade_iters, nullptr, 0, -1, nullptr, nullptr };
     // r06: contexts for concurrent moves (expand.hip, k_commit)
@@ -124,7 +114,7 @@ int do_expand(mh_engine* e, const int* init_dev, long long* energy, int* cycles)
     }
     if (w.n_ctx > 1) {
         w.bctl = e->ew_bctl.p;
-        w.h_batch = e->h_batch; w.h_batch_dev = e->h_batch_dev;
+        w.h_batch = e->h_batch.h; w.h_batch_dev = e->h_batch.d;
         w.took_list0 = e->ew_took_list.p;
         w.batch_min_labels = e->tune_batch_min_labels;
         w.batch_spw = e->tune_batch_spw;

@@ -20,22 +20,18 @@ int mh_propose_haf(mh_engine* e, long long first, int m, int stride, int members
     if (members > e->smp_k) return fail(MH_ERR_INVALID, "mh_propose_haf: members exceeds k of the sampling table");
     // the last anchor (first + m - 1) * stride must be a correspondence: compared by division, nothing can overflow
     if (m > 0 && first + (long long)m - 1 > (long long)(e->n - 1) / stride) return fail(MH_ERR_INVALID, "mh_propose_haf: (first + m - 1) * stride must be below n");
-    e->counts_fresh = false; ++e->models_seq;
-    e->have_samples = false;
-    e->cost_L = 0;
-    e->m = 0;
-    e->haf_members = members;
-    e->p3_batch = false;
-    e->haf_batch = (m == 0);                                   // an empty batch is one already; a full one once its launch is accepted
-    if (m == 0) return MH_OK;                                  // an empty model set, as mh_set_models(NULL, 0) leaves one
+    drop_models(e);
+    if (m == 0) {                                              // an empty model set, as mh_set_models(NULL, 0) leaves one — and a HAF batch
+        install_models(e, 0, BatchOrigin::HAF, false, members);
+        return MH_OK;
+    }
     HIPCHK(e->H.reserve((size_t)m * 9));
     HIPCHK(e->haf_used.reserve((size_t)m));
     HIPCHK(reserve_counts(e, (size_t)m + 1));
     Affines a{ e->a11.p, e->a12.p, e->a21.p, e->a22.p };
     HIPCHK(launch_haf_propose(e->pts(), a, e->epi, members > 0 ? e->smp_nbr.p : nullptr, e->smp_k, members, thr2, first, m, stride,
                               e->H.p, e->haf_used.p, e->stream));
-    e->m = m;
-    e->haf_batch = true;
+    install_models(e, m, BatchOrigin::HAF, false, members);
     return MH_OK;
     });
 }
@@ -49,20 +45,16 @@ int mh_propose_3pt(mh_engine* e, unsigned long long seed, long long first, int m
     if (e->n < 3) return fail(MH_ERR_INVALID, "mh_propose_3pt: need at least 3 correspondences");
     if (!e->have_epi) return fail(MH_ERR_NOT_SET, "fundamental matrix / epipole are not set");
     if (e->sampler == MH_SAMPLER_LOCAL && e->smp_k <= 0) return fail(MH_ERR_NOT_SET, "the local sampler has no table; call mh_build_sample_neighbours");
-    e->counts_fresh = false; ++e->models_seq;
-    e->have_samples = false;
-    e->haf_batch = false;
-    e->cost_L = 0;
-    e->m = 0;
-    e->p3_batch = (m == 0);                                    // (as mh_propose_haf: an empty batch is one already)
-    if (m == 0) return MH_OK;                                  // an empty model set, as mh_set_models(NULL, 0) leaves one
+    drop_models(e);
+    if (m == 0) {                                              // (as mh_propose_haf: an empty batch is one already)
+        install_models(e, 0, BatchOrigin::P3, false);
+        return MH_OK;
+    }
     HIPCHK(e->H.reserve((size_t)m * 9));
     HIPCHK(e->samples.reserve((size_t)m * 4));
     HIPCHK(reserve_counts(e, (size_t)m + 1));
     HIPCHK(launch_propose_3pt(e->pts(), e->epi.F, seed, first, m, e->samples.p, e->H.p, e->stream, e->dlt_local()));
-    e->m = m;
-    e->have_samples = true;
-    e->p3_batch = true;
+    install_models(e, m, BatchOrigin::P3, true);
     return MH_OK;
     });
 }
@@ -72,7 +64,7 @@ int mh_get_haf_support(mh_engine* e, unsigned* used)
     return guarded([&]() -> int {
     int rc = enter(e);
     if (rc) return rc;
-    if (!e->haf_batch) return fail(MH_ERR_NOT_SET, "the resident model set was not proposed by mh_propose_haf");
+    if (e->origin != BatchOrigin::HAF) return fail(MH_ERR_NOT_SET, "the resident model set was not proposed by mh_propose_haf");
     if (e->m <= 0) return MH_OK;
     if (!used) return fail(MH_ERR_INVALID, "null argument");
     HIPCHK(hipMemcpyAsync(used, e->haf_used.p, sizeof(unsigned) * (size_t)e->m, hipMemcpyDeviceToHost, e->stream));

@@ -73,22 +73,14 @@ int msac_models(mh_engine* e, const Points& p, const double* Hs, int m, double t
 // ---- pipelined propose -------------------------------------------------------------------------
 int ensure_side_stream(mh_engine* e)
 {
-    if (!e->side_stream) {
-        for (int k = 0; k < e->tune_stream_shift; ++k) {
-            hipStream_t d = nullptr;
-            HIPCHK(hipStreamCreateWithFlags(&d, hipStreamNonBlocking));
-            e->dummy_streams.push_back(d);
-        }
-        // highest priority: the short DLT kernel gets its compute units as soon as the sweep on the main stream frees
-        // some, so it is done early in the sweep instead of trickling in behind it and delaying the next one
-        int lo = 0, hi = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIPCHK(hipStreamCreateWithPriority(&e->side_stream, hipStreamNonBlocking, hi));
-    }
-    for (int q = 0; q < mh_engine::PF_DEPTH; ++q)
-        if (!e->pf_ev[q]) HIPCHK(hipEventCreateWithFlags(&e->pf_ev[q], hipEventDisableTiming));
-    if (!e->ev_main) HIPCHK(hipEventCreateWithFlags(&e->ev_main, hipEventDisableTiming));
-    if (!e->ev_side_pre) HIPCHK(hipEventCreateWithFlags(&e->ev_side_pre, hipEventDisableTiming));
+    if (!e->side_stream)
+        for (int k = 0; k < e->tune_stream_shift; ++k) HIPCHK(e->dummy_streams[k].ensure());
+    // highest priority: the short DLT kernel gets its compute units as soon as the sweep on the main stream frees
+    // some, so it is done early in the sweep instead of trickling in behind it and delaying the next one
+    HIPCHK(e->side_stream.ensure(true));
+    for (int q = 0; q < mh_engine::PF_DEPTH; ++q) HIPCHK(e->pf_ev[q].ensure());
+    HIPCHK(e->ev_main.ensure());
+    HIPCHK(e->ev_side_pre.ensure());
     return MH_OK;
 }
 
@@ -104,6 +96,7 @@ int mh_propose_dlt4(mh_engine* e, unsigned long long seed, long long first, int 
     if (m <= 0) return fail(MH_ERR_INVALID, "m must be positive");
     if (e->n < 4) return fail(MH_ERR_INVALID, "need at least 4 correspondences");
     if (e->sampler == MH_SAMPLER_LOCAL && e->smp_k <= 0) return fail(MH_ERR_NOT_SET, "the local sampler has no table; call mh_build_sample_neighbours");
+    drop_models(e);
     HIPCHK(e->H.reserve((size_t)m * 9));
     HIPCHK(e->samples.reserve((size_t)m * 4));
     HIPCHK(reserve_counts(e, (size_t)m + 1));
@@ -111,11 +104,7 @@ int mh_propose_dlt4(mh_engine* e, unsigned long long seed, long long first, int 
         ScopedTimer t(e, MH_K_DLT4);
         HIPCHK(launch_dlt4(e->pts(), seed, first, m, e->samples.p, e->H.p, e->stream, e->tune_dlt_variant == 1 ? 1 : 0, e->dlt_local()));   // alone on the device: the register form (0.26 against 0.40 ms per 100k)
     }
-    e->m = m;
-    e->have_samples = true;
-    e->haf_batch = false; e->p3_batch = false;
-    e->cost_L = 0;
-    e->counts_fresh = false; ++e->models_seq;
+    install_models(e, m, BatchOrigin::DLT4, true);
     return MH_OK;
     });
 }
@@ -137,16 +126,13 @@ int mh_set_models(mh_engine* e, const double* H, int m)
     return guarded([&]() -> int {
     if (!e || m < 0 || (m > 0 && !H)) return fail(MH_ERR_INVALID, "null argument or m < 0");
     HIPCHK(hipSetDevice(e->device));
-    e->counts_fresh = false; ++e->models_seq;
-    e->haf_batch = false; e->p3_batch = false;
-    if (m == 0) { e->m = 0; e->have_samples = false; e->cost_L = 0; return MH_OK; }     // an empty model set
+    drop_models(e);
+    if (m == 0) return MH_OK;                              // an empty model set
     HIPCHK(e->H.reserve((size_t)m * 9));
     HIPCHK(reserve_counts(e, (size_t)m + 1));
     HIPCHK(hipMemcpyAsync(e->H.p, H, sizeof(double) * 9 * m, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    e->m = m;
-    e->have_samples = false;
-    e->cost_L = 0;
+    install_models(e, m, BatchOrigin::GIVEN, false);
     return MH_OK;
     });
 }
@@ -225,8 +211,7 @@ int mh_score(mh_engine* e, double thr2, const unsigned char* point_mask, int* co
         rc = score_models(e, e->pts(), e->H.p, e->m, thr2, dmask, e->counts.p);
         if (rc) return rc;
     }
-    e->counts_zeroed = false;
-    e->counts_fresh = true;
+    counts_scored(e);
     if (counts) {
         HIPCHK(hipMemcpyAsync(counts, e->counts.p, sizeof(int) * e->m, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
@@ -260,8 +245,7 @@ int mh_score_msac(mh_engine* e, double thr2, const unsigned char* point_mask, in
     }
     // mh_select_best_msac reports the winner's count too, and the counts buffer may be handed to an exchange before it is asked
     HIPCHK(hipMemcpyAsync(e->weights_counts.p, e->counts.p, sizeof(int) * (size_t)e->m, hipMemcpyDeviceToDevice, e->stream));
-    e->counts_zeroed = false;
-    e->counts_fresh = true;
+    counts_scored(e);
     e->weights_models_seq = e->models_seq;
     if (counts) HIPCHK(hipMemcpyAsync(counts, e->counts.p, sizeof(int) * e->m, hipMemcpyDeviceToHost, e->stream));
     if (weights) HIPCHK(hipMemcpyAsync(weights, e->weights.p, sizeof(int) * e->m, hipMemcpyDeviceToHost, e->stream));
@@ -320,8 +304,7 @@ int mh_residual_matrix(mh_engine* e, double thr2, double* R_host, int* counts)
         HIPCHK(launch_residual(e->pts(), e->H.p, e->m, thr2, e->R.p, e->ldr, e->counts.p,
                                e->residual_mode == MH_RESIDUAL_SYMMETRIC ? -1 : e->tune_residual_variant, e->stream, how));
     }
-    e->counts_zeroed = false;
-    e->counts_fresh = true;
+    counts_scored(e);
     if (R_host)
         HIPCHK(hipMemcpy2DAsync(R_host, sizeof(double) * e->n, e->R.p, sizeof(double) * e->ldr,
                                 sizeof(double) * e->n, e->m, hipMemcpyDeviceToHost, e->stream));
@@ -360,8 +343,7 @@ int mh_cost_matrix(mh_engine* e, int* C_host, int* counts)
             HIPCHK(launch_cost_matrix(e->pts(), e->H.p, e->m, e->lambda, thr2, e->C.p, e->ldc, e->counts.p, e->stream,
                                       e->data_term == MH_DATA_TERM_RISING));
     }
-    e->counts_zeroed = false;
-    e->counts_fresh = true;
+    counts_scored(e);
     if (C_host)
         HIPCHK(hipMemcpy2DAsync(C_host, sizeof(int) * e->n, e->C.p, sizeof(int) * e->ldc, sizeof(int) * e->n, e->m,
                                 hipMemcpyDeviceToHost, e->stream));
@@ -433,17 +415,14 @@ int mh_adopt_prefetched(mh_engine* e)
     if (rc) return rc;
     if (e->pf_count <= 0) return fail(MH_ERR_NOT_SET, "no prefetched batch (mh_prefetch_dlt4)");
     const int slot = e->pf_head;
+    drop_models(e);
     HIPCHK(hipStreamWaitEvent(e->stream, e->pf_ev[slot], 0));    // main-stream work behind this point sees the new batch
+    HIPCHK(reserve_counts(e, (size_t)e->pf_m[slot] + 1));        // (before the swap: a failure leaves the queue as it was)
     std::swap(e->H, e->pf_H[slot]);
     std::swap(e->samples, e->pf_samples[slot]);
-    HIPCHK(reserve_counts(e, (size_t)e->pf_m[slot] + 1));
-    e->m = e->pf_m[slot];
     e->pf_head = (e->pf_head + 1) % mh_engine::PF_DEPTH;
     --e->pf_count;
-    e->have_samples = true;
-    e->haf_batch = false; e->p3_batch = false;
-    e->cost_L = 0;
-    e->counts_fresh = false; ++e->models_seq;
+    install_models(e, e->pf_m[slot], BatchOrigin::DLT4, true);
     return MH_OK;
     });
 }

@@ -6,16 +6,11 @@ namespace mhe {
 // ---- best model of the scored batch --------------------------------------------------------------
 int ensure_xchg_stream(mh_engine* e)
 {
-    if (!e->xchg_stream) {
-        // high priority, like the DLT's stream: the two or three short kernels of an exchange (and RCCL's own) get compute
-        // units as soon as the sweep on the main stream frees some
-        int lo = 0, hi = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIPCHK(hipStreamCreateWithPriority(&e->xchg_stream, hipStreamNonBlocking, hi));
-    }
-    if (!e->ev_sweep) HIPCHK(hipEventCreateWithFlags(&e->ev_sweep, hipEventDisableTiming));
-    for (int b = 0; b < 3; ++b)
-        if (!e->ev_x[b]) HIPCHK(hipEventCreateWithFlags(&e->ev_x[b], hipEventDisableTiming));
+    // high priority, like the DLT's stream: the two or three short kernels of an exchange (and RCCL's own) get compute
+    // units as soon as the sweep on the main stream frees some
+    HIPCHK(e->xchg_stream.ensure(true));
+    HIPCHK(e->ev_sweep.ensure());
+    for (int b = 0; b < 3; ++b) HIPCHK(e->ev_x[b].ensure());
     return MH_OK;
 }
 
@@ -36,6 +31,24 @@ int exchange(mh_engine* e, const void* send_dev, void* recv_dev, size_t bytes_pe
     if (e->t_host_fn(e->t_ctx, send_dev, recv_dev, (unsigned long long)bytes_per_rank) != 0)
         return fail(MH_ERR_INVALID, "all-gather failed (host-synchronised transport)");
     return MH_OK;
+}
+
+// The mode word of this rank's selection records (its fields: the table beside SelRecord, mh_kernels.hpp): everything the ranks of
+// a sharded batch must agree on for their claims to be the same — the engine's settings and how the resident batch was proposed
+// (an empty HAF or 3-point batch is one too).  k_sel_claim raises error 3 on any mismatch, and every rank leaves with it: also a
+// rank that called the other entry point (it runs the same collectives), or proposed DLT hypotheses beside one that proposed HAF
+// ones.  The estimator is in the word only when winners are refitted: one no refit uses cannot make the ranks' claims differ.
+int selection_mode_word(const mh_engine* e, bool by_weight)
+{
+    int w = 0;
+    if (e->residual_mode == MH_RESIDUAL_SYMMETRIC) w |= SEL_MODE_SYMMETRIC;
+    if (e->tune_select_refine != 0) w |= SEL_MODE_REFIT | (e->estimator == MH_ESTIMATOR_3PT ? SEL_MODE_REFIT_3PT : 0);
+    if (e->sampler == MH_SAMPLER_LOCAL)
+        w |= SEL_MODE_SAMPLER_LOCAL | (e->smp_k << SEL_MODE_SAMPLER_K_SHIFT) | (e->sampler_uniform_per_16 << SEL_MODE_SAMPLER_UNIFORM_SHIFT);
+    if (by_weight) w |= SEL_MODE_BY_WEIGHT;
+    if (e->origin == BatchOrigin::HAF) w |= SEL_MODE_HAF | (e->haf_members << SEL_MODE_HAF_MEMBERS_SHIFT);
+    if (e->origin == BatchOrigin::P3) w |= SEL_MODE_P3;
+    return w;
 }
 
 // The rounds of mh_select_greedy (by_weight = false) and of mh_select_greedy_msac (true): one loop over one set of round kernels
@@ -71,33 +84,17 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
     int local_rc = MH_OK;
     std::string local_msg;
     auto local_failure = [&](int code, const std::string& msg) { if (local_rc == MH_OK) { local_rc = code; local_msg = msg; } };
-    // r05: the selection follows the engine's residual mode — scores (score_models) and claims (k_sel_claim) both on the
-    // symmetric transfer error when that is set; the ranks of a sharded batch must agree (their records carry the mode)
     const int symmetric = e->residual_mode == MH_RESIDUAL_SYMMETRIC ? 1 : 0;
     // r05, key 30: each round's winner is refitted to its inliers before it claims them (select.hip, launch_sel_refit).  Needs the
     // affinities and the epipolar geometry (the per-label HAF least squares of the loop); a setting, like thr2, that the ranks share.
     // r06 (advisor): affinities / epipolar geometry missing is the state of THIS rank's engine — it goes through local_failure like
-    // every other rank-local error (returning here would leave the peers waiting in the all-gather), and the setting itself
-    // travels in the records' mode word (bit 1) beside the residual mode (bit 0): ranks that disagree about it would claim with
-    // different models, so k_sel_claim raises error 3 on any mismatch of the word.
-    // Under the 3-point estimator (mh_set_estimator) the refit is the point-only fit and needs the epipolar geometry alone; the
-    // estimator of the refit travels in the mode word too (bit 2, set only when winners are refitted: an estimator no refit uses
-    // cannot make the ranks' claims differ).
+    // every other rank-local error (returning here would leave the peers waiting in the all-gather); the setting itself travels in
+    // the records' mode word.  Under the 3-point estimator (mh_set_estimator) the refit is the point-only fit and needs the
+    // epipolar geometry alone.
     const bool refine = e->tune_select_refine != 0;
     const bool refit3 = e->estimator == MH_ESTIMATOR_3PT;
     const bool refine_usable = refine && e->have_epi && (refit3 || e->have_aff);
-    // The proposer's sampler travels in the word too: bit 3 the local sampler, bits 4-9 its k, bits 10-14 uniform_per_16 — all
-    // zero under the default, so those records are what they were.  A rank-independent batch needs the ranks to agree on it.
-    const int sampler_bits = e->sampler == MH_SAMPLER_LOCAL ? (8 | (e->smp_k << 4) | (e->sampler_uniform_per_16 << 10)) : 0;
-    // ... and so does "ranked by weight" (bit 15): a rank that called the other entry point runs the same collectives, and every
-    // rank leaves with the mode-mismatch error
-    // ... and how the resident batch was proposed: bit 16 = by mh_propose_haf, bits 17-22 its `members` (0 .. 32).  Zero for every
-    // other batch, so those records are what they were.  A rank that proposed DLT hypotheses beside one that proposed HAF ones
-    // leaves with the others through the same mismatch.
-    const int haf_bits = e->haf_batch ? (1 << 16) | (e->haf_members << 17) : 0;
-    // ... bit 23 = by mh_propose_3pt, on the same terms
-    const int p3_bit = e->p3_batch ? 1 << 23 : 0;
-    const int mode_word = symmetric | (refine ? 2 : 0) | (refine && refit3 ? 4 : 0) | sampler_bits | (by_weight ? 1 << 15 : 0) | haf_bits | p3_bit;
+    const int mode_word = selection_mode_word(e, by_weight);
     if (refine && !refine_usable)
         local_failure(MH_ERR_NOT_SET, std::string(by_weight ? "mh_select_greedy_msac" : "mh_select_greedy") +
                                       (refit3 ? " with refitted winners (mh_set_tuning key 30) needs the epipolar geometry"
@@ -128,10 +125,8 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
         HIPCHK(e->sel_scores.reserve((size_t)std::max(longest, 1)));
         HIPCHK(e->sel_gathered.reserve((size_t)world * std::max(longest, 1)));
     }
-    if (!e->h_sel) {
-        HIPCHK(hipHostMalloc((void**)&e->h_sel, sizeof(int) * 8, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer((void**)&e->h_sel_dev, e->h_sel, 0));
-    }
+    HIPCHK(e->h_sel.ensure(8));
+    const int* const h_sel = e->h_sel.h;
     hipStream_t s = e->stream;
     if (point_mask) { HIPCHK(hipMemcpyAsync(e->mask.p, point_mask, n, hipMemcpyHostToDevice, s)); ++e->copies_h2d; }
     else HIPCHK(hipMemsetAsync(e->mask.p, 1, n, s));
@@ -249,22 +244,22 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
                           decrement ? e->sel_gone[2].p : nullptr, decrement ? e->sel_gone[3].p : nullptr };
         HIPCHK(launch_sel_claim(e->pts(), records, world, check, thr2, e->mask.p, e->sel_rec.p, e->sel_out_H.p, e->sel_counter.p,
                                 max_models, s, by_weight, symmetric, refit, gp[0], gp[1], gp[2], gp[3]));
-        HIPCHK(launch_sel_publish(e->sel_rec.p, e->sel_keys.p, my_record, e->h_sel_dev, s));
+        HIPCHK(launch_sel_publish(e->sel_rec.p, e->sel_keys.p, my_record, e->h_sel.d, s));
         HIPCHK(hipStreamSynchronize(s));                 // the seven control words through mapped memory: no copy
         if (local_rc != MH_OK) return fail(local_rc, local_msg);     // (the others have read this rank's error word by now)
-        if (e->h_sel[4] != 0)                            // every rank sees the same word, so every rank leaves here
-            return fail(e->h_sel[4] == 3 ? MH_ERR_INVALID : MH_ERR_HIP,
-                        e->h_sel[4] == 2 ? "greedy selection: the gathered score vector and the ranks' records disagree about the winner"
-                        : e->h_sel[4] == 3 ? "greedy selection: the ranks are not in the same residual mode (mh_set_residual_mode) or do not agree on refitted winners (mh_set_tuning key 30), the estimator (mh_set_estimator), the proposer's sampler (mh_set_sampler) or the selection's score (mh_select_greedy / mh_select_greedy_msac), or proposed their shards differently (mh_propose_haf and its members, mh_propose_3pt)"
+        if (h_sel[4] != 0)                            // every rank sees the same word, so every rank leaves here
+            return fail(h_sel[4] == 3 ? MH_ERR_INVALID : MH_ERR_HIP,
+                        h_sel[4] == 2 ? "greedy selection: the gathered score vector and the ranks' records disagree about the winner"
+                        : h_sel[4] == 3 ? "greedy selection: the ranks are not in the same residual mode (mh_set_residual_mode) or do not agree on refitted winners (mh_set_tuning key 30), the estimator (mh_set_estimator), the proposer's sampler (mh_set_sampler) or the selection's score (mh_select_greedy / mh_select_greedy_msac), or proposed their shards differently (mh_propose_haf and its members, mh_propose_3pt)"
                                            : "greedy selection: a rank reported an error");
         // word 0: the winner's rank value (its count, or its weight), -1 when nobody was eligible; word 6: its count
-        if (e->h_sel[0] < 0) break;
-        if (counts_out) counts_out[selected] = e->h_sel[6];
-        if (weights_out) weights_out[selected] = e->h_sel[0];
+        if (h_sel[0] < 0) break;
+        if (counts_out) counts_out[selected] = h_sel[6];
+        if (weights_out) weights_out[selected] = h_sel[0];
         ++selected;
-        gone = e->h_sel[5];
+        gone = h_sel[5];
         active -= gone;                                   // what the claim took out of the support set (the winner's inliers, or its refit's)
-        Mc = e->h_sel[2];
+        Mc = h_sel[2];
         cur ^= 1;
         first = false;
     }
@@ -342,20 +337,15 @@ int mh_select_best(mh_engine* e, long long total_m, long long* best_index, int* 
     if (total_m <= 0) total_m = e->m;
     const int base = (int)(total_m / world), rem = (int)(total_m % world);
     const int longest = base + (rem ? 1 : 0);
-    HIPCHK(e->best_key.reserve(1));
-    if (!e->h_best) {
-        HIPCHK(hipHostMalloc((void**)&e->h_best, sizeof(int) * 4, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer((void**)&e->h_best_dev, e->h_best, 0));
-        e->h_best[0] = e->h_best[1] = e->h_best[2] = e->h_best[3] = 0;
-        HIPCHK(hipMemsetAsync(e->best_key.p, 0, sizeof(unsigned long long), e->stream));
-    }
+    HIPCHK(e->h_best.ensure(4));                                   // (zeroed: the device counts the sequence number up from there)
+    const int* const h_best = e->h_best.h;
     hipStream_t s = e->stream;
     const bool fetch = best_index || best_count;
     auto result = [&]() -> int {
-        if (e->h_best[2] != e->best_seq) return fail(MH_ERR_HIP, "best-model result is stale");
-        if (e->h_best[3] != 0) return fail(MH_ERR_HIP, "mh_select_best: a rank reported an error");     // (every rank reads the same word)
-        if (best_index) *best_index = e->h_best[1];
-        if (best_count) *best_count = e->h_best[0];
+        if (h_best[2] != e->best_seq) return fail(MH_ERR_HIP, "best-model result is stale");
+        if (h_best[3] != 0) return fail(MH_ERR_HIP, "mh_select_best: a rank reported an error");     // (every rank reads the same word)
+        if (best_index) *best_index = h_best[1];
+        if (best_count) *best_count = h_best[0];
         return MH_OK;
     };
     // Is this call a NEW exchange?  Decided from state that is the same on every rank (r04 advisor finding: a rank with an
@@ -393,7 +383,7 @@ int mh_select_best(mh_engine* e, long long total_m, long long* best_index, int* 
         HIPCHK(launch_pad_scores(e->counts.p, mine, longest, e->sel_scores.p, s));
         rc = exchange(e, e->sel_scores.p, e->sel_gathered.p, sizeof(int) * (size_t)longest, s);     // north_star's all-gather
         if (rc) return rc;
-        HIPCHK(launch_best_fused(e->sel_gathered.p, world, longest, base, rem, e->h_best_dev, nullptr, 0, s));
+        HIPCHK(launch_best_fused(e->sel_gathered.p, world, longest, base, rem, e->h_best.d, nullptr, 0, s));
         ++e->best_seq;
         e->best_models_seq = e->models_seq;
         e->counts_fresh = false;                                   // (a later call without a scoring call in between is a completion, on every rank)
@@ -423,9 +413,9 @@ int mh_select_best(mh_engine* e, long long total_m, long long* best_index, int* 
             if (sharded) {
                 rc = exchange(e, e->counts.p, e->sel_gathered.p, sizeof(int) * (size_t)longest, x);      // north_star's all-gather
                 if (rc) return rc;
-                HIPCHK(launch_best_fused(e->sel_gathered.p, world, longest, base, rem, e->h_best_dev, clear, clear_count, x));
+                HIPCHK(launch_best_fused(e->sel_gathered.p, world, longest, base, rem, e->h_best.d, clear, clear_count, x));
             } else {
-                HIPCHK(launch_best_fused(e->counts.p, 1, e->m, 0, 0, e->h_best_dev, clear, clear_count, x));
+                HIPCHK(launch_best_fused(e->counts.p, 1, e->m, 0, 0, e->h_best.d, clear, clear_count, x));
             }
         }
         const int par = (int)(e->xchg_calls % 3);
@@ -441,12 +431,7 @@ int mh_select_best(mh_engine* e, long long total_m, long long* best_index, int* 
         } else {
             // this batch's counts stay with the exchange; the next sweep writes the buffer that has waited longest — once the
             // exchange that was given THAT one (two calls ago) is through
-            DevBuf<int> given = e->counts;
-            const int wait = e->counts_alt_wait[0];
-            e->counts = e->counts_alt[0];
-            e->counts_zeroed = e->counts_zeroed_alt[0];
-            e->counts_alt[0] = e->counts_alt[1]; e->counts_zeroed_alt[0] = e->counts_zeroed_alt[1]; e->counts_alt_wait[0] = e->counts_alt_wait[1];
-            e->counts_alt[1] = given; e->counts_zeroed_alt[1] = true; e->counts_alt_wait[1] = par;      // (clear once ev_x[par] has passed)
+            const int wait = hand_counts_to_exchange(e, par);         // (the buffer it was given is clear once ev_x[par] has passed)
             e->counts_fresh = false;
             HIPCHK(reserve_counts(e, (size_t)e->m + 1));
             if (wait >= 0) HIPCHK(hipStreamWaitEvent(s, e->ev_x[wait], 0));
@@ -466,21 +451,18 @@ int mh_select_best_msac(mh_engine* e, long long* best_index, int* best_weight, i
     if ((e->t_stream_fn || e->t_host_fn) && e->t_world > 1) return fail(MH_ERR_INVALID, "mh_select_best_msac: one rank only (the weights are not exchanged)");
     if (e->m <= 0) return fail(MH_ERR_NOT_SET, "model set is empty");
     if (e->weights_models_seq != e->models_seq || !e->weights.p) return fail(MH_ERR_NOT_SET, "the batch has no weights (mh_score_msac)");
-    if (!e->h_best_w) {
-        HIPCHK(hipHostMalloc((void**)&e->h_best_w, sizeof(int) * 4, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer((void**)&e->h_best_w_dev, e->h_best_w, 0));
-        e->h_best_w[0] = e->h_best_w[1] = e->h_best_w[2] = e->h_best_w[3] = 0;
-    }
+    HIPCHK(e->h_best_w.ensure(4));
+    const int* const h_best_w = e->h_best_w.h;
     // mh_select_best's one-workgroup arg-max (highest score, lowest index on ties) on the weights, on the main stream
-    const int seq = e->h_best_w[2];
-    HIPCHK(launch_best_fused(e->weights.p, 1, e->m, 0, 0, e->h_best_w_dev, nullptr, 0, e->stream));
+    const int seq = h_best_w[2];
+    HIPCHK(launch_best_fused(e->weights.p, 1, e->m, 0, 0, e->h_best_w.d, nullptr, 0, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->h_best_w[2] != seq + 1 || e->h_best_w[3] != 0 || e->h_best_w[1] < 0 || e->h_best_w[1] >= e->m)
+    if (h_best_w[2] != seq + 1 || h_best_w[3] != 0 || h_best_w[1] < 0 || h_best_w[1] >= e->m)
         return fail(MH_ERR_HIP, "mh_select_best_msac: no result from the arg-max");
-    if (best_index) *best_index = e->h_best_w[1];
-    if (best_weight) *best_weight = e->h_best_w[0];
+    if (best_index) *best_index = h_best_w[1];
+    if (best_weight) *best_weight = h_best_w[0];
     if (best_count) {
-        HIPCHK(hipMemcpyAsync(best_count, e->weights_counts.p + e->h_best_w[1], sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(best_count, e->weights_counts.p + h_best_w[1], sizeof(int), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
     }
     return MH_OK;

@@ -329,7 +329,19 @@ hipError_t launch_sel_pack_points(const Points& p, const unsigned char* mask, do
 // or its MSAC weight when `weights` (with its next_ / carried_ / left_ companions) is given; null = ranked by count.  The key
 // rank << 32 | ~position is built for eligible candidates only; the highest key wins.
 // one rank's offer in a round: 88 bytes, the unit of the sharded exchange
-struct SelRecord { unsigned long long key; double H[9]; int err; int mode; };      // mode: bit 0 the rank's residual mode, bit 1 refitted winners (key 30), bit 2 those refits by the 3-point estimator (mh_set_estimator), bits 3-14 the proposer's sampler, bit 15 ranked by MSAC weight: mh_select_greedy_msac, bit 16 the batch is mh_propose_haf's and bits 17-22 its members, bit 23 the batch is mh_propose_3pt's (capi_select.hip); the ranks' words must agree
+struct SelRecord { unsigned long long key; double H[9]; int err; int mode; };
+// SelRecord::mode, built by selection_mode_word (capi_select.hip): what the ranks of a sharded batch must agree on — the claim
+// raises error 3 on any mismatch of the word.  Zero under the defaults.  This is the one table of its fields:
+constexpr int SEL_MODE_SYMMETRIC = 1 << 0;             // the rank's residual mode is the symmetric transfer error (mh_set_residual_mode)
+constexpr int SEL_MODE_REFIT = 1 << 1;                 // winners are refitted to their inliers (mh_set_tuning key 30)
+constexpr int SEL_MODE_REFIT_3PT = 1 << 2;             // ... by the 3-point estimator (mh_set_estimator); only beside SEL_MODE_REFIT
+constexpr int SEL_MODE_SAMPLER_LOCAL = 1 << 3;         // the proposer's sampler is the local one (mh_set_sampler), and then:
+constexpr int SEL_MODE_SAMPLER_K_SHIFT = 4;            //   bits 4-9   k of its sampling table (3 .. 32)
+constexpr int SEL_MODE_SAMPLER_UNIFORM_SHIFT = 10;     //   bits 10-14 its uniform_per_16 (0 .. 16)
+constexpr int SEL_MODE_BY_WEIGHT = 1 << 15;            // ranked by MSAC weight: mh_select_greedy_msac
+constexpr int SEL_MODE_HAF = 1 << 16;                  // the resident batch is mh_propose_haf's, and then:
+constexpr int SEL_MODE_HAF_MEMBERS_SHIFT = 17;         //   bits 17-22 its `members` (0 .. 32)
+constexpr int SEL_MODE_P3 = 1 << 23;                   // the resident batch is mh_propose_3pt's
 static_assert(sizeof(SelRecord) == 88, "the exchanged record is 88 bytes");
 // scores_full (nullable): the first round's vector for the all-gather — the rank value of an eligible candidate, -1 otherwise
 hipError_t launch_sel_argmax(const int* counts, const int* weights, const int* orig, int Mc, int need, unsigned int my_off,

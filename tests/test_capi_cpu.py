@@ -93,6 +93,26 @@ def test_product_tree_never_touches_the_oracle():
     assert "oracle" not in out
 
 
+def test_only_the_engine_header_allocates_and_frees():
+    """Every HIP resource of an engine is held by an owner of csrc/capi_engine.hpp that frees it in its destructor: the
+    translation units of the C ABI allocate, create, free and destroy nothing themselves (a resource they held by hand is one
+    mh_destroy has to be told about — seven buffers were not), and no buffer owner is ever copied out of the engine."""
+    csrc = os.path.join(ROOT, "multi-h_amd", "csrc")
+    calls = re.compile(r"\bhip(Malloc|Free|HostMalloc|HostFree|HostGetDevicePointer|EventCreate\w*|EventDestroy|StreamCreate\w*|StreamDestroy)\b")
+    units = sorted(f for f in os.listdir(csrc) if re.fullmatch(r"capi\w*\.hip", f))
+    assert len(units) >= 6 and "capi.hip" in units
+    bad = []
+    for f in sorted(os.listdir(csrc)):
+        for no, line in enumerate(open(os.path.join(csrc, f), errors="ignore"), 1):
+            if (f in units and calls.search(line)) or re.search(r"DevBuf\s*<[^;=]*>\s*\w+\s*=\s*e\s*->", line):
+                bad.append(f"{f}:{no}: {line.strip()}")
+    assert not bad, "\n".join(bad)
+    header = open(os.path.join(csrc, "capi_engine.hpp")).read()
+    used = {m.group(0) for m in calls.finditer(header)}
+    assert {"hipMalloc", "hipFree", "hipHostMalloc", "hipHostFree", "hipHostGetDevicePointer", "hipEventDestroy", "hipStreamDestroy"} <= used
+    assert any(u.startswith("hipEventCreate") for u in used) and any(u.startswith("hipStreamCreate") for u in used)
+
+
 def test_product_library_kernels_are_the_product_instantiations_only(mh, engine_lib):
     """the kernel templates carry measurement switches (the residual sweep's configuration: CALIB =
     store-only calibration, CONTRACT = fused multiply-adds — not bit-exact —, TILED = tile-major R, SF = asm store flavours,
