@@ -120,6 +120,47 @@ struct Stream : NoCopy {
     operator hipStream_t() const { return s; }
 };
 
+// The buffers of ONE context of the alpha-expansion (ExpandWork::Ctx, mh_kernels.hpp); the engine holds sixteen, all alike.
+// A context packs its arrays by kind: `arcs` holds cap and sent, `sites` excess, sink_cap, height, decided and — when asked
+// for — the took list, each array at a multiple of 64 ints (the 256 bytes a buffer of its own would be aligned to); core,
+// took, the control words and the accumulators are buffers of their own.  In ints that is 2 nnz + 13 n and change: the
+// figure expand_contexts (capi_label.hip) bounds.  Fresh memory is cleared once: a context's capacities and flow counters
+// are read for arcs the current move has not written only together with verdicts that make them irrelevant (expand.hip), but
+// the control words' rings and tickets must start at zero (k_ctl_init) and nothing is gained by leaving the rest to chance.
+struct ExpandCtxBufs {
+    DevBuf<int> arcs, sites, core, flags;
+    DevBuf<long long> acc;
+    DevBuf<unsigned char> took;
+    static size_t pitch(int count) { return ((size_t)count + 2 + 63) & ~(size_t)63; }
+    hipError_t reserve(int n, int nnz, bool with_took_list, hipStream_t stream)
+    {
+        auto grow = [&](auto& buf, size_t count) -> hipError_t {
+            const size_t had = buf.cap;
+            hipError_t e = buf.reserve(count);
+            if (e == hipSuccess && buf.cap != had) e = hipMemsetAsync(buf.p, 0, sizeof(*buf.p) * buf.cap, stream);
+            return e;
+        };
+        hipError_t e = grow(arcs, 2 * pitch(nnz));
+        if (e == hipSuccess) e = grow(sites, (with_took_list ? 5 : 4) * pitch(n));
+        if (e == hipSuccess) e = grow(core, (size_t)EXPAND_CORE_SHARDS * n);
+        if (e == hipSuccess) e = grow(flags, EXPAND_FLAG_WORDS);
+        if (e == hipSuccess) e = grow(acc, EXPAND_ACC_WORDS);
+        if (e == hipSuccess) e = grow(took, (size_t)n + 2);
+        return e;
+    }
+    // the eleven pointers for a graph of n sites and nnz arcs that reserve() was last called for (or a smaller one)
+    ExpandWork::Ctx view(int n, int nnz) const
+    {
+        const size_t pa = pitch(nnz), ps = pitch(n);
+        ExpandWork::Ctx x{};
+        x.cap = arcs.p; x.sent = arcs.p + pa;
+        x.excess = sites.p; x.sink_cap = sites.p + ps; x.height = sites.p + 2 * ps; x.decided = sites.p + 3 * ps;
+        x.took_list = sites.cap >= 5 * ps ? sites.p + 4 * ps : nullptr;
+        x.took = took.p; x.core = core.p; x.flags = flags.p; x.acc = acc.p;
+        return x;
+    }
+};
+
 struct KernelTimer {
     std::vector<std::pair<Event, Event>> pending;
     int launches = 0;
@@ -265,18 +306,13 @@ struct mh_engine : ResidentBatch {                    // (e->m, e->origin, e->ha
     // labeling
     int cost_L = 0;
     DevBuf<int> cost, labels_in, labels_pts, label_counts;
-    DevBuf<int> ew_label, ew_cur, ew_cap, ew_sent, ew_excess, ew_sink, ew_height, ew_decided, ew_flags, ew_core, ew_trace, ew_saved, d_order, d_wsum;
+    DevBuf<int> ew_label, ew_cur, ew_trace, ew_saved, d_order, d_wsum;
     int comp_moves = 0;                      // > 0: component diagnostic of the first n moves' cores (mh_set_tuning key 21)
     DevBuf<int> ew_comp, ew_comp_out;
     int trace_moves = 0;                     // > 0: k_solve logs 8 ints per move (mh_set_tuning key 8)
     int detail_move = -1;                    // move whose relabels are logged one by one (key 9)
-    DevBuf<unsigned char> ew_took;
-    // r06: the contexts of the concurrent alpha-moves beyond context 0 (expand.hip): per context cap + sent (2 nnz ints), excess /
-    // sink_cap / height / decided (4 n), core (8 n), control words and accumulators; took (n bytes); and the batch's own scratch
-    DevBuf<int> ewx_arcs[EXPAND_MAX_CTX - 1], ewx_sites[EXPAND_MAX_CTX - 1], ewx_core[EXPAND_MAX_CTX - 1], ewx_flags[EXPAND_MAX_CTX - 1];
-    DevBuf<long long> ewx_acc[EXPAND_MAX_CTX - 1];
-    DevBuf<unsigned char> ewx_took[EXPAND_MAX_CTX - 1];
-    DevBuf<int> ew_bctl, ew_took_list;
+    ExpandCtxBufs ew_ctx[EXPAND_MAX_CTX];    // the contexts of the alpha-moves in flight; only those in use hold memory
+    DevBuf<int> ew_bctl;                     // the batch control words
     PinnedBuf<int> h_batch;                  // k_commit's publication
     int tune_expand_ctx = 16;                // key 37: alpha-moves solved together (1 = one after the other, the form until r05)
     int tune_batch_min_labels = 16;          // key 38: label sets of at least this many labels are batched from the first cycle on (smaller ones from the second)
@@ -293,7 +329,6 @@ struct mh_engine : ResidentBatch {                    // (e->m, e->origin, e->ha
     int inject_select_failure = 0;           // test hook (key 18): the n-th scoring round of the coming greedy selections fails on this rank
     int inject_barrier_timeouts = 0;         // test hook: the next n expansions' first attempts count as timed out
     int inject_solve_failure = 0;            // test hook (key 40): (group << 4) | context of the next expansion's solve marked failed
-    DevBuf<long long> ew_acc;
     PinnedBuf<int> h_flags;
     PinnedBuf<long long> h_acc;
     PinnedBuf<MeanShiftResultBlock> h_ms;      // the result blocks of the mean-shift climbs, then 3 ints per climb (seed rows, list offsets, list lengths)

@@ -16,41 +16,15 @@ int expand_contexts(const mh_engine* e)
 
 int ensure_expand_work(mh_engine* e)
 {
-    const int n = e->n, nnz = e->g_nnz;
+    const int n = e->n, n_ctx = expand_contexts(e);
     HIPCHK(e->ew_label.reserve(n));
     HIPCHK(e->ew_cur.reserve(n));
-    HIPCHK(e->ew_cap.reserve(nnz));
-    HIPCHK(e->ew_sent.reserve(nnz));
-    HIPCHK(e->ew_excess.reserve(n));
-    HIPCHK(e->ew_sink.reserve(n));
-    HIPCHK(e->ew_height.reserve(n));
-    HIPCHK(e->ew_decided.reserve(n));
-    HIPCHK(e->ew_flags.reserve(EXPAND_FLAG_WORDS));
-    HIPCHK(e->ew_acc.reserve(EXPAND_ACC_WORDS));
-    HIPCHK(e->ew_took.reserve((size_t)n + 2));
-    HIPCHK(e->ew_core.reserve((size_t)EXPAND_CORE_SHARDS * n));
     HIPCHK(e->h_flags.ensure(EXPAND_HOST_WORDS));
     HIPCHK(e->h_acc.ensure(16));
-    // r06: the contexts of the concurrent moves (key 37).  Fresh memory is cleared once: a context's capacities and flow counters
-    // are read for arcs the current move has not written only together with verdicts that make them irrelevant (expand.hip), but
-    // the control words' rings and tickets must start at zero (k_ctl_init) and nothing is gained by leaving the rest to chance.
-    const int extra = expand_contexts(e) - 1;
-    for (int k = 0; k < extra; ++k) {
-        const size_t cap_a = e->ewx_arcs[k].cap, cap_s = e->ewx_sites[k].cap, cap_c = e->ewx_core[k].cap, cap_t = e->ewx_took[k].cap;
-        HIPCHK(e->ewx_arcs[k].reserve(2 * (size_t)nnz + 2));
-        HIPCHK(e->ewx_sites[k].reserve(5 * (size_t)n + 5));
-        HIPCHK(e->ewx_core[k].reserve((size_t)EXPAND_CORE_SHARDS * n));
-        HIPCHK(e->ewx_flags[k].reserve(EXPAND_FLAG_WORDS));
-        HIPCHK(e->ewx_acc[k].reserve(EXPAND_ACC_WORDS));
-        HIPCHK(e->ewx_took[k].reserve((size_t)n + 2));
-        if (e->ewx_arcs[k].cap != cap_a) HIPCHK(hipMemsetAsync(e->ewx_arcs[k].p, 0, sizeof(int) * e->ewx_arcs[k].cap, e->stream));
-        if (e->ewx_sites[k].cap != cap_s) HIPCHK(hipMemsetAsync(e->ewx_sites[k].p, 0, sizeof(int) * e->ewx_sites[k].cap, e->stream));
-        if (e->ewx_core[k].cap != cap_c) HIPCHK(hipMemsetAsync(e->ewx_core[k].p, 0, sizeof(int) * e->ewx_core[k].cap, e->stream));
-        if (e->ewx_took[k].cap != cap_t) HIPCHK(hipMemsetAsync(e->ewx_took[k].p, 0, e->ewx_took[k].cap, e->stream));
-    }
-    if (extra > 0) {
+    // (only batches walk a took list: a single context goes without)
+    for (int k = 0; k < n_ctx; ++k) HIPCHK(e->ew_ctx[k].reserve(n, e->g_nnz, n_ctx > 1, e->stream));
+    if (n_ctx > 1) {
         HIPCHK(e->ew_bctl.reserve(8 + EXPAND_MAX_CTX));
-        HIPCHK(e->ew_took_list.reserve((size_t)n + 2));
         HIPCHK(e->h_batch.ensure(8));
     }
     return MH_OK;
@@ -98,28 +72,23 @@ int do_expand(mh_engine* e, const int* init_dev, long long* energy, int* cycles)
     rc = solve_grid_limit(e);
     if (rc) return rc;
     int solve_grid = std::max(1, std::min(e->tune_expand[3], e->solve_grid_max));
-    ExpandWork w{ e->ew_label.p, e->ew_cur.p, e->ew_cap.p, e->ew_sent.p, e->ew_excess.p, e->ew_sink.p,
-                  e->ew_height.p, e->ew_decided.p, e->ew_took.p, e->ew_core.p, e->ew_flags.p, e->ew_acc.p,
-                  e->h_flags.h, e->h_acc.h, e->h_flags.d, e->h_acc.d,
-                  e->tune_expand[0], e->tune_expand[1], e->tune_expand[2], solve_grid, e->tune_push_mult, e->tune_reduce, e->tune_reduce_launches,
-                  e->tune_cascade_iters, nullptr, 0, -1, nullptr, nullptr };
-    // r06: contexts for concurrent moves (expand.hip, k_commit)
+    ExpandWork w;
+    w.label = e->ew_label.p; w.cur_cost = e->ew_cur.p;
     w.n_ctx = expand_contexts(e);
-    for (int k = 0; k + 1 < w.n_ctx; ++k) {
-        ExpandWork::Ctx& x = w.ctx[k];
-        x.cap = e->ewx_arcs[k].p; x.sent = e->ewx_arcs[k].p + ((size_t)g.nnz + 1);
-        x.excess = e->ewx_sites[k].p; x.sink_cap = x.excess + ((size_t)g.n + 1); x.height = x.sink_cap + ((size_t)g.n + 1); x.decided = x.height + ((size_t)g.n + 1);
-        x.took = e->ewx_took[k].p; x.core = e->ewx_core[k].p; x.flags = e->ewx_flags[k].p; x.acc = e->ewx_acc[k].p;
-        x.took_list = x.decided + ((size_t)g.n + 1);
-    }
-    if (w.n_ctx > 1) {
+    for (int k = 0; k < w.n_ctx; ++k) w.ctx[k] = e->ew_ctx[k].view(g.n, g.nnz);
+    w.h_flags = e->h_flags.h; w.h_flags_dev = e->h_flags.d;
+    w.h_acc = e->h_acc.h; w.h_acc_dev = e->h_acc.d;
+    if (w.n_ctx > 1) {                                            // batches (expand.hip, k_batch_commit)
         w.bctl = e->ew_bctl.p;
         w.h_batch = e->h_batch.h; w.h_batch_dev = e->h_batch.d;
-        w.took_list0 = e->ew_took_list.p;
-        w.batch_min_labels = e->tune_batch_min_labels;
-        w.batch_spw = e->tune_batch_spw;
     }
-    // flow recycling (expand.hip, k_solve): L x (nnz + n) ints, cleared per expansion; left out (every move starts from
+    ExpandTuning& tu = w.tune;
+    tu.relax_rounds = e->tune_expand[0]; tu.push_cycles = e->tune_expand[1]; tu.push_phases = e->tune_expand[2];
+    tu.push_mult = e->tune_push_mult;
+    tu.reduce_rounds = e->tune_reduce; tu.reduce_launches = e->tune_reduce_launches;
+    tu.cascade_iters = e->tune_cascade_iters;
+    tu.batch_min_labels = e->tune_batch_min_labels; tu.batch_spw = e->tune_batch_spw;
+    // flow recycling (expand_solve.hip, k_solve): L x (nnz + n) ints, cleared per expansion; left out (every move starts from
     // the zero flow) beyond 8 GiB.  Flows are not kept from one call to the next: measured in the alternation, the
     // re-estimated models move the problems far enough for a kept flow to cost more rounds than the zero flow.
     const size_t recycle_words = (size_t)e->cost_L * ((size_t)g.nnz + (size_t)g.n);
@@ -146,10 +115,10 @@ int do_expand(mh_engine* e, const int* init_dev, long long* energy, int* cycles)
     ExpandStats st{};
     {
         ScopedTimer t(e, MH_K_EXPAND);
-        hipError_t he = hipSuccess;
+        ExpandResult res;
         e->last_expand_retries = 0;
         for (int attempt = 0; attempt < 5; ++attempt) {
-            w.solve_grid = solve_grid;
+            tu.solve_grid = solve_grid;
             // How long a barrier may wait before the launch gives up and the expansion restarts: a healthy barrier takes
             // about 8 us, so max(20 ms, 50 x the longest steady-state wait this engine has seen) tells "a workgroup is not
             // resident" from "slow" within tens of milliseconds.  The FIRST barrier of a launch is the one that waits for
@@ -159,37 +128,37 @@ int do_expand(mh_engine* e, const int* init_dev, long long* energy, int* cycles)
             // a launch already down to one workgroup) waits the full 3 s before the call fails.
             const bool last_attempt = attempt == 4 || solve_grid == 1;
             const double steady_ms = std::max(20.0, 50.0 * e->longest_barrier_wait_ms);
-            w.barrier_timeout_ticks = last_attempt ? 300000000ll : (long long)(steady_ms * 1e5);
-            w.barrier_first_timeout_ticks = last_attempt ? 300000000ll : (long long)(std::max(250.0, 10.0 * steady_ms) * 1e5);
+            tu.barrier_timeout_ticks = last_attempt ? 300000000ll : (long long)(steady_ms * 1e5);
+            tu.barrier_first_timeout_ticks = last_attempt ? 300000000ll : (long long)(std::max(250.0, 10.0 * steady_ms) * 1e5);
             if (w.saved_flow) HIPCHK(hipMemsetAsync(e->ew_saved.p, 0, sizeof(int) * recycle_words, e->stream));
             HIPCHK(launch_init_labeling(e->cost.p, e->cost_L, e->n, init_dev, w.label, w.cur_cost, e->stream));
-            w.inject_group = e->inject_solve_failure >> 4;                     // test hook (mh_set_tuning key 40): first attempt only
-            w.inject_ctx = e->inject_solve_failure & 15;
+            w.hooks.inject_group = e->inject_solve_failure >> 4;                    // test hook (mh_set_tuning key 40): first attempt only
+            w.hooks.inject_ctx = e->inject_solve_failure & 15;
             e->inject_solve_failure = 0;
-            he = run_expansion(g, e->cost.p, e->cost_L, potts, w, 1000, &st, e->stream);
-            bool timed_out = he == hipErrorLaunchTimeOut && st.energy == -2;
-            if (he == hipSuccess && e->inject_barrier_timeouts > 0) {           // test hook (mh_set_tuning key 14)
+            res = run_expansion(g, e->cost.p, e->cost_L, potts, w, 1000, &st, e->stream);
+            if (res.status == ExpandStatus::ok && e->inject_barrier_timeouts > 0) {           // test hook (mh_set_tuning key 14)
                 --e->inject_barrier_timeouts;
-                timed_out = true;
-                he = hipErrorLaunchTimeOut;
-                st.energy = -2;
+                res.status = ExpandStatus::barrier_timeout;
             }
             e->last_solve_grid = solve_grid;
-            if (!timed_out || solve_grid == 1 || attempt == 4) break;
+            if (res.status != ExpandStatus::barrier_timeout || solve_grid == 1 || attempt == 4) break;
             if (attempt >= 1) solve_grid = std::max(1, solve_grid / 2);      // (the first retry keeps the grid)
             ++e->last_expand_retries;
             ++e->expand_retries_total;
         }
-        if (he == hipErrorOutOfMemory)
+        switch (res.status) {
+        case ExpandStatus::ok: break;
+        case ExpandStatus::too_many_sites:
             return fail(MH_ERR_INVALID, "alpha-expansion: more sites than the solver's per-row state holds (about 1.3 million at 256 workgroups)");
-        if (he == hipErrorInvalidValue && st.energy == -1)
+        case ExpandStatus::overflow:
             return fail(MH_ERR_OVERFLOW, "int32 energy term overflow in alpha-expansion");
-        if (he == hipErrorLaunchTimeOut && st.energy == -2)
+        case ExpandStatus::barrier_timeout:
             return fail(MH_ERR_HIP, "alpha-expansion: the solver's grid barrier timed out even with the launch cut down to a few workgroups "
                                     "(its workgroups were not all resident; is the GPU shared with other persistent launches?)");
-        if (he == hipErrorLaunchTimeOut && st.energy == -3)
+        case ExpandStatus::no_convergence:
             return fail(MH_ERR_HIP, "alpha-expansion: push-relabel did not converge within its iteration bound");
-        HIPCHK(he);
+        case ExpandStatus::hip_error: { const hipError_t he = res.hip; HIPCHK(he); }
+        }
     }
     e->last_expand = st;
     if (st.max_barrier_wait_ms > e->longest_barrier_wait_ms) e->longest_barrier_wait_ms = std::min(st.max_barrier_wait_ms, 50.0);

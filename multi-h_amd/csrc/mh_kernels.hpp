@@ -212,7 +212,7 @@ hipError_t launch_ms_pack(const MeanShiftWork& w, int climbs, int longest, const
 // compacts and clears the votes of all `climbs` climbs, ended or not
 hipError_t launch_ms_collect(const MeanShiftWork& w, int climbs, hipStream_t s);
 
-// --- expand.hip -------------------------------------------------------------
+// --- expand.hip, expand_solve.hip ---------------------------------------------
 struct Graph {              // symmetric weighted CSR in HBM
     const int* rowptr;      // n+1
     const int* col;         // nnz
@@ -224,68 +224,75 @@ struct Graph {              // symmetric weighted CSR in HBM
     const int* wsum;        // n    sum of w over the site's row: bounds every n-link total of the site (expand.hip, k_move_setup)
 };
 
-struct ExpandWork {         // scratch owned by the engine
-    int* label;             // n   current labeling (GCO numbering)
-    int* cur_cost;          // n   cost[i][label[i]]
-    int* cap;               // nnz capacities of the move's s-t graph
-    int* sent;              // nnz cumulative flow per arc, written by the arc's tail only (expand.hip, k_solve)
-    int* excess;            // n
-    int* sink_cap;          // n
-    int* height;            // n
-    int* decided;           // n   0 undecided, 1 source side (takes alpha), 2 sink side (keeps its label), 3 not in the graph
-    unsigned char* took;    // n   1 where the last solved move moves the site to alpha (applied lazily, see expand.hip)
-    int* core;              // 8 x n  compacted list of the sites the dominance reduction left undecided, in 8 shards
-    int* flags;             // device control words (EXPAND_FLAG_WORDS ints, see expand.hip)
-    long long* acc;         // device 64-bit accumulators (EXPAND_ACC_WORDS)
-    int* h_flags;           // pinned, device-mapped host mirror of flags (host address)
-    long long* h_acc;       // pinned, device-mapped host mirror of acc (host address)
-    int* h_flags_dev;       // device addresses of the two mirrors
-    long long* h_acc_dev;
-    // schedule knobs of the per-move solver (see expand.hip): relaxation rounds per barrier interval, push cycles per
-    // push phase, push phases per global relabel, workgroups of the solver launch
-    int relax_rounds, push_cycles, push_phases, solve_grid, push_mult;
-    int reduce_rounds;      // dominance-reduction rounds per launch; 0 switches the reduction off (A/B)
-    int reduce_launches;    // reduction launches per move in front of the solver: 2, or 1 (the compacting one alone)
-    int cascade_iters;      // barrier-separated passes of the dominance cascade inside the solver launch (0 = to its fixed point)
-    int* trace;             // optional: 8 ints per move {core sites, workgroups, relabels, relax intervals, push phases,
-    int trace_moves;        //   barriers, ticks (100 MHz), ticks inside barriers}; moves beyond trace_moves are not traced
-    int detail_move;        // move whose global relabels are logged behind the trace (4 ints each, at most 2048): {active sites,
-                            //   largest finite height, relabel intervals so far, ticks so far}; -1 none
-    // flow recycling (expand.hip, k_solve): per label the net arc flows (L x nnz) and sink flows (L x n) its last
-    // expansion ended with; null = every move starts from the zero flow
-    int* saved_flow;
-    int* saved_sink;
+constexpr int EXPAND_MAX_CTX = 16;
+constexpr int EXPAND_FLAG_WORDS = 896;     // device control block (expand_ctl.hpp)
+constexpr int EXPAND_HOST_WORDS = 32;      // its head, mirrored to the host
+constexpr int EXPAND_ACC_WORDS = 64 + 3 * 64 * 16;   // 16 scalars (mirrored to the host) + three striped sums
+constexpr int EXPAND_CORE_SHARDS = 8;
+
+// The schedule knobs of an expansion (see expand.hip and expand_solve.hip); do_expand sets every one.
+struct ExpandTuning {
+    // per-move solver: relaxation rounds per barrier interval, push cycles per push phase, push phases per global relabel,
+    // workgroups of the solver launch
+    int relax_rounds = 0, push_cycles = 0, push_phases = 0, solve_grid = 0, push_mult = 0;
+    int reduce_rounds = 0;      // dominance-reduction rounds per launch; 0 switches the reduction off (A/B)
+    int reduce_launches = 1;    // reduction launches per move in front of the solver: 2, or 1 (the compacting one alone)
+    int cascade_iters = 0;      // barrier-separated passes of the dominance cascade inside the solver launch (0 = to its fixed point)
     // 100 MHz ticks a poll at a grid barrier may last before the launch gives up (a workgroup of it is not resident: a GPU
     // shared with other persistent launches); 0 = 3 s
     long long barrier_timeout_ticks = 0;
     long long barrier_first_timeout_ticks = 0;     // the launch's first barrier (residency of all its workgroups)
+    int batch_min_labels = 0;   // batches from the first cycle on only when the label set has at least this many labels
+    int batch_spw = 0;          // sites per wave in a batch's setup and reduction launches: 16 / 32 / 64, 0 = by the size of the launch (a move alone: 16)
+};
+
+// Test hook (mh_set_tuning key 40): the solve of context inject_ctx in the inject_group-th group of moves this expansion
+// enqueues (a batch or a move alone, counted from 1) is marked failed (ERR_NO_CONVERGENCE) behind its k_solve; 0 = off
+struct ExpandHooks { int inject_group = 0, inject_ctx = 0; };
+
+// What the caller lends an expansion.  Everything optional is off (null) unless set.
+struct ExpandWork {
+    int* label = nullptr;       // n   current labeling (GCO numbering)
+    int* cur_cost = nullptr;    // n   cost[i][label[i]]
+    // The per-move state of one move in flight.  n_ctx >= 2: that many consecutive moves are solved together on the SAME
+    // labeling, each in a context of its own, and committed in order by k_batch_commit (expand.hip, "batches").
+    struct Ctx {
+        int* cap;               // nnz capacities of the move's s-t graph
+        int* sent;              // nnz cumulative flow per arc, written by the arc's tail only (expand_solve.hip)
+        int* excess;            // n
+        int* sink_cap;          // n
+        int* height;            // n
+        int* decided;           // n   0 undecided, 1 source side (takes alpha), 2 sink side (keeps its label), 3 not in the graph
+        unsigned char* took;    // n   1 where the last solved move moves the site to alpha (applied lazily, see expand.hip)
+        int* core;              // 8 x n  compacted list of the sites the dominance reduction left undecided, in 8 shards
+        int* flags;             // device control words (EXPAND_FLAG_WORDS ints, expand_ctl.hpp)
+        long long* acc;         // device 64-bit accumulators (EXPAND_ACC_WORDS)
+        int* took_list;         // n   the sites the context's move takes (null: not kept; only batches walk it)
+    };
+    int n_ctx = 1;
+    Ctx ctx[EXPAND_MAX_CTX] = {};
+    int* h_flags = nullptr;         // pinned, device-mapped host mirror of context 0's flags (host address)
+    long long* h_acc = nullptr;     // ... and of its accumulators
+    int* h_flags_dev = nullptr;     // device addresses of the two mirrors
+    long long* h_acc_dev = nullptr;
+    int* bctl = nullptr;            // 8 + EXPAND_MAX_CTX   batch control words (device)
+    int* h_batch = nullptr;         // 8   k_batch_commit's publication, pinned + device-mapped (host address) ...
+    int* h_batch_dev = nullptr;     //     ... and its device address
+    // flow recycling (expand_solve.hip): per label the net arc flows (L x nnz) and sink flows (L x n) its last
+    // expansion ended with; null = every move starts from the zero flow
+    int* saved_flow = nullptr;
+    int* saved_sink = nullptr;
+    int* trace = nullptr;           // 8 ints per move {core sites, workgroups, relabels, relax intervals, push phases,
+    int trace_moves = 0;            //   barriers, ticks (100 MHz), ticks inside barriers}; moves beyond trace_moves are not traced
+    int detail_move = -1;           // move whose global relabels are logged behind the trace (4 ints each, at most 2048): {active sites,
+                                    //   largest finite height, relabel intervals so far, ticks so far}; -1 none
     // diagnostic (expand.hip, k_core_components): 16 ints per move for the first comp_moves moves; scratch 2 n ints
     int* comp_out = nullptr;
     int* comp_scratch = nullptr;
     int comp_moves = 0;
-    // r06: concurrent alpha-moves (expand.hip, "batches").  n_ctx >= 2: that many consecutive moves are solved together on
-    // the SAME labeling, each in a context of its own (the fields above are context 0; ctx[k - 1] holds context k), and
-    // committed in order by k_batch_commit, which keeps a move only if it passes a test against what its predecessors in the batch changed.
-    int n_ctx = 1;
-    struct Ctx { int* cap; int* sent; int* excess; int* sink_cap; int* height; int* decided; unsigned char* took; int* core; int* flags; long long* acc; int* took_list; };
-    int* took_list0 = nullptr;    // n   context 0's list of the sites its move takes (the other contexts': Ctx::took_list)
-    Ctx ctx[15] = {};     // EXPAND_MAX_CTX - 1
-    int* bctl = nullptr;          // 8 + EXPAND_MAX_CTX   batch control words (device)
-    int* h_batch = nullptr;       // 8   k_batch_commit's publication, pinned + device-mapped (host address) ...
-    int* h_batch_dev = nullptr;   //     ... and its device address
-    int batch_min_labels = 0;     // batches only when the label set has at least this many labels
-    int batch_spw = 0;            // sites per wave in a batch's setup and reduction launches: 16 / 32 / 64, 0 = by the size of the launch (a move alone: 16)
-    // test hook (mh_set_tuning key 40): the solve of context inject_ctx in the inject_group-th group of moves this expansion
-    // enqueues (a batch or a move alone, counted from 1) is marked failed (ERR_NO_CONVERGENCE) behind its k_solve; 0 = off
-    int inject_group = 0;
-    int inject_ctx = 0;
+    ExpandTuning tune;
+    ExpandHooks hooks;
 };
-constexpr int EXPAND_MAX_CTX = 16;
-static_assert(sizeof(ExpandWork::ctx) / sizeof(ExpandWork::Ctx) == EXPAND_MAX_CTX - 1, "one context is the work area itself");
-constexpr int EXPAND_FLAG_WORDS = 896;     // device control block (expand.hip)
-constexpr int EXPAND_HOST_WORDS = 32;      // its head, mirrored to the host
-constexpr int EXPAND_ACC_WORDS = 64 + 3 * 64 * 16;   // 16 scalars (mirrored to the host) + three striped sums
-constexpr int EXPAND_CORE_SHARDS = 8;
 
 struct ExpandStats {
     int cycles;
@@ -311,10 +318,14 @@ struct ExpandStats {
     long long injected_discarded;             // test hook (key 40): injected failures whose move the commit threw away
 };
 
+// How an expansion ended.  `hip` means something for hip_error alone; the statistics' energy is an energy and nothing else.
+enum class ExpandStatus { ok, hip_error, overflow, barrier_timeout, no_convergence, too_many_sites };
+struct ExpandResult { ExpandStatus status = ExpandStatus::ok; hipError_t hip = hipSuccess; };
+
 // resident workgroups of the solver launch per CU, as the occupancy query sees k_solve
 hipError_t solver_blocks_per_cu(int* blocks);
-hipError_t run_expansion(const Graph& g, const int* cost /* n x L */, int L, int potts,
-                         ExpandWork& w, int max_cycles, ExpandStats* st, hipStream_t s);
+ExpandResult run_expansion(const Graph& g, const int* cost /* n x L */, int L, int potts,
+                           ExpandWork& w, int max_cycles, ExpandStats* st, hipStream_t s);
 hipError_t launch_init_labeling(const int* cost, int L, int n, const int* init_or_null_dev,
                                 int* label, int* cur_cost, hipStream_t s);
 hipError_t launch_argmin_labels(const int* cost, int L, int n, int* label, long long* acc,

@@ -113,6 +113,24 @@ def test_only_the_engine_header_allocates_and_frees():
     assert any(u.startswith("hipEventCreate") for u in used) and any(u.startswith("hipStreamCreate") for u in used)
 
 
+def test_the_expansion_has_one_context_record_one_status_and_a_host_only_planner():
+    """The alpha-expansion's sixteen contexts are one record (ExpandCtxBufs / ExpandWork::Ctx): no source names a list of
+    context 0's own or the packed buffers of 'the others'.  How an expansion ended travels as ExpandStatus: neither the C ABI
+    nor the schedule compares an energy with a negated ERR_ code.  The planner's header is host arithmetic alone."""
+    csrc = os.path.join(ROOT, "multi-h_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, f), errors="ignore").read()
+        assert "took_list0" not in text and "ewx_" not in text, f
+    for f in ("capi_label.hip", "expand.hip"):
+        text = open(os.path.join(csrc, f)).read()
+        assert not re.search(r"energy\s*(==|!=|<=?|>=?|=)\s*-\s*(\(long long\)|ERR_|w\.h_flags|[123]\b)", text), f
+        assert not re.search(r"-\s*ERR_\w+", text), f
+    plan = open(os.path.join(csrc, "expand_plan.hpp")).read()
+    includes = re.findall(r"#\s*include\s*[<\"]([^>\"]+)[>\"]", plan)
+    assert includes and not any("hip" in i.lower() or i.endswith(".hpp") for i in includes), includes
+    assert not re.search(r"\bhip[A-Z]\w*|__global__|__device__", plan)
+
+
 def test_product_library_kernels_are_the_product_instantiations_only(mh, engine_lib):
     """the kernel templates carry measurement switches (the residual sweep's configuration: CALIB =
     store-only calibration, CONTRACT = fused multiply-adds — not bit-exact —, TILED = tile-major R, SF = asm store flavours,

@@ -88,6 +88,35 @@ def test_every_batch_size_gives_the_sequential_result_and_the_oracles(engine, sy
         assert failed > 0, "near-duplicate models: some move must fail its test against its predecessor's changes"
 
 
+def test_one_engines_contexts_grow_and_shrink_with_the_scenes_and_the_batch_size(engine, synth, oracle, restore):
+    """The sixteen contexts' buffers (csrc/capi_engine.hpp, ExpandCtxBufs) on ONE engine, through every way they are reserved
+    and viewed: sixteen fresh contexts; a smaller scene in buffers larger than it needs; more sites and arcs with two contexts;
+    the other fourteen behind buffers that already exist; fewer again.  Batches from the first cycle on (key 38 = 0), cold and
+    from a seeded random labeling: labels, energy and cycle count are the oracle's every time."""
+    rng = np.random.default_rng(77)
+    scenes = {}
+    for key, (n, planes) in {"a": (600, 3), "b": (64, 2), "c": (900, 3)}.items():
+        sc = synth.make_scene(n, planes, seed=10 + n)
+        H = _label_set(sc, rng, 4, 2e-4)
+        init = rng.integers(0, H.shape[0] + 1, size=sc.n).astype(np.int32)
+        scenes[key] = [sc, H, init, None]
+    kept = 0
+    for key, ctx in (("a", 16), ("b", 16), ("c", 2), ("c", 16), ("c", 3)):
+        sc, H, init, want = scenes[key]
+        _load(engine, sc)
+        engine.set_models(H)
+        cost = engine.data_cost()
+        if want is None:                                   # the reference, once per scene
+            want = scenes[key][3] = tuple(oracle.expand(cost, sc.hit_rowptr, sc.hit_col, oracle.potts(LAM), init_labels=i) for i in (None, init))
+        for start, ref in zip((None, init), want):
+            lab, en, cyc, b, st = _expand(engine, ctx, 0, start)
+            assert st["barrier_timeout_retries"] == 0, "an expansion restarted after a barrier timeout: the run does not count"
+            assert np.array_equal(lab, ref[0]) and en == ref[1] and cyc == ref[2], (key, ctx, start is not None, b)
+            assert b["moves_per_batch"] == ctx and b["batch_committed"] + b["solo_moves"] + b["host_skipped"] == st["moves"] == cyc * (H.shape[0] + 1), b
+            kept += b["batch_committed"]
+    assert kept > 0, "no move was ever kept out of a batch: the path under test did not run"
+
+
 def test_hundreds_of_labels_batches_pay_off_and_change_nothing(engine, synth, restore):
     """The reference's own route hands the loop several hundred stable-set models (M/MultiH.cpp:604-694).  540 labels on 20 000
     sites: the batched form keeps nearly every move out of a batch (r06: 1 203 of 1 620, 417 never launched, 49-66 batches cut
