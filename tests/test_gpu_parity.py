@@ -214,7 +214,7 @@ def test_moments_and_collinearity(engine, synth, oracle):
     mo, me = engine.inlier_moments(THR2)
     mo_ref, me_ref = oracle.inlier_moments(sc.src, sc.dst, H, THR2)
     assert np.array_equal(mo.view(np.uint64), mo_ref.view(np.uint64))
-    assert np.allclose(me, me_ref, rtol=1e-9, atol=1e-9)
+    assert np.array_equal(me.view(np.uint64), me_ref.view(np.uint64))     # same matrix bits, the same cyclic Jacobi
 
 
 @pytest.mark.parametrize("n,k,seed", [(300, 3, 1), (5000, 3, 1234), (2000, 10, 8)])
