@@ -334,6 +334,46 @@ MH_API int mh_inliers_of_model(mh_engine* e, int idx, double thr2, int label_val
  * model set is left untouched.  Used by the sharded propose stage, where the winning hypothesis
  * of a round may live on another rank. */
 MH_API int mh_inliers_of_homography(mh_engine* e, const double* H, double thr2, int label_value, int* labels /* in/out n */);
+/* One homography refitted to ALL its inliers over the resident correspondences: the step cv::findHomography(CV_RANSAC) runs
+ * behind its winning minimal sample (M/MultiH.cpp:719-741), without OpenCV's Levenberg-Marquardt polish.  Like
+ * mh_inliers_of_homography it touches neither the resident model set nor the counts, weights, data cost or graph.  One
+ * launch of one workgroup whatever `iterations` is (csrc/refit_h.hip, k_refit_h).
+ *   Inlier set  S(H) = { i : d2(H, i) < thr2 }, strictly; d2 the forward transfer error in the reference's operation order
+ *               (M/MultiH.cpp:434-441); a NaN is not an inlier; always the forward error, whatever mh_set_residual_mode says.
+ *   Sums        every FP64 sum below in the engine's order: thread t of 256 starts at 0.0 and adds the terms of the members of
+ *               S with index = t (mod 256) in ascending index, each as acc = acc + term; then the binary tree s = 128 .. 1,
+ *               v[t] = v[t] + v[t + s].  No fused multiply-add anywhere.
+ *   fit(S)      with c = |S|; fails when c < 4.
+ *     1. the centroids of both images, sum * (1.0 / c);
+ *     2. the mean distances d = sum of sqrt(ax * ax + ay * ay), (ax, ay) = point - centroid, and the scales
+ *        s = sqrt(2.0) / (d / c); fails when a scale is not finite;
+ *     3. x, y, u, v = (coordinate - centroid) * scale, (x, y) from the first image, (u, v) from the second; p = (x, y, 1.0);
+ *     4. for the six pairs a <= b in the order 00 01 02 11 12 22, t = p_a * p_b and the 24 sums
+ *          G0 += t    G1 += u * t    G2 += v * t    G3 += (u * u + v * v) * t
+ *        the normal matrix of the two DLT rows [-p, 0, u p] and [0, -p, v p] (symmetric 9 x 9):
+ *          M[a][b] = M[3+a][3+b] = G0    M[a][6+b] = M[6+b][a] = -G1    M[3+a][6+b] = M[6+b][3+a] = -G2    M[6+a][6+b] = G3
+ *        every other entry 0;
+ *     5. the cyclic Jacobi solve (csrc/mh_device.hpp, jacobi_sym_dev(9)); the column of the smallest eigenvalue, the first index
+ *        on ties, as the row-major Hn;
+ *     6. T2^-1 Hn T1 by the 4-point DLT proposer's steps (csrc/dlt4.hip): per row (a, b, c) of Hn
+ *          (a * s1, b * s1, (c - (a * s1) * cx1) - (b * s1) * cy1),
+ *        then rows 1 and 2 times 1.0 / s2 plus cx2 resp. cy2 times row 3; the sum of the nine squares in index order from 0.0,
+ *        every entry times 1.0 / sqrt(sum), negated when h33 < 0;
+ *     7. fails when an entry of the result is not finite.
+ *   Rounds      cur = H_in, n_cur = |S(cur)|, accepted = 0; for r = 1 .. iterations:
+ *     1. cand = fit(S(cur)); stop when it fails;
+ *     2. stop when cand equals cur bit for bit;
+ *     3. n_cand = |S(cand)|; stop when n_cand < n_cur (a refit must explain at least as many points: the rule of mh_set_tuning key 30);
+ *     4. cur = cand, n_cur = n_cand, ++accepted.
+ *   Outputs     H_out = cur; inlier_mask (n bytes, 1 = inlier) and inliers are those of H_out; fits_accepted = accepted.  With
+ *               nothing accepted H_out is H_in's nine doubles unchanged (not renormalised), so iterations = 0 gives the mask
+ *               and count of H_in.
+ * MH_ERR_INVALID for a null engine, H_in or H_out, iterations outside [0, 16], a NaN thr2; MH_ERR_NOT_SET without
+ * correspondences.  Affinities and the epipolar geometry are not read: the point-only route can call it.  Deterministic, so
+ * every rank of a sharded run (all hold all points) gets the same result without an exchange. */
+MH_API int mh_refit_homography(mh_engine* e, const double H_in[9], double thr2, int iterations, double H_out[9],
+                               unsigned char* inlier_mask /* n, nullable */, int* inliers /* nullable */,
+                               int* fits_accepted /* nullable */);
 /* Trial statistics of HomographyCompatibilityCheck (M/MultiH.cpp:128-196; host/merge_step.cpp ClusterMedian) for
  * `clusters` clusters of at least 19 points each.  pts_xyxy: the clusters' points back to back in cluster order, 4 doubles
  * each (x1 y1 x2 y2); cluster_begin[c] .. cluster_begin[c+1] (cluster_begin[0] = 0); per (cluster, trial): tri = the

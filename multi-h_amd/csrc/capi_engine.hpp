@@ -213,6 +213,9 @@ struct mh_engine : ResidentBatch {                    // (e->m, e->origin, e->ha
     DevBuf<int> C;                            // mh_cost_matrix
     long long ldc = 0;
     DevBuf<unsigned char> mask;
+    DevBuf<double> rh_H;                      // mh_refit_homography: H_in and H_out (18 doubles),
+    DevBuf<unsigned char> rh_mask;            // the inlier flags of H_out (n bytes),
+    DevBuf<int> rh_out;                       // its inlier count and the fits accepted
     DevBuf<double> moments, min_eig;
     DevBuf<double> cp_pts, cp_H, cp_out;     // mh_compat_trial_stats staging
     DevBuf<int> cp_begin, cp_tri;

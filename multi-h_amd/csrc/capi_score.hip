@@ -459,6 +459,33 @@ int mh_inliers_of_homography(mh_engine* e, const double* H, double thr2, int lab
     });
 }
 
+int mh_refit_homography(mh_engine* e, const double H_in[9], double thr2, int iterations, double H_out[9],
+                        unsigned char* inlier_mask, int* inliers, int* fits_accepted)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (!H_in || !H_out) return fail(MH_ERR_INVALID, "null homography");
+    if (iterations < 0 || iterations > REFIT_H_MAX_ITERATIONS) return fail(MH_ERR_INVALID, "iterations outside [0, 16]");
+    if (thr2 != thr2) return fail(MH_ERR_INVALID, "thr2 is NaN");
+    int rc = require_points(e);
+    if (rc) return rc;
+    HIPCHK(e->rh_H.reserve(18));
+    HIPCHK(e->rh_mask.reserve(e->n));
+    HIPCHK(e->rh_out.reserve(2));
+    HIPCHK(hipMemcpyAsync(e->rh_H.p, H_in, sizeof(double) * 9, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(launch_refit_h(e->pts(), e->rh_H.p, thr2, iterations, e->rh_H.p + 9, e->rh_mask.p, e->rh_out.p, e->stream));
+    // one read-back: H_out, then (count, accepted), then the flags if they are wanted
+    int out_i[2] = { 0, 0 };
+    HIPCHK(hipMemcpyAsync(H_out, e->rh_H.p + 9, sizeof(double) * 9, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(out_i, e->rh_out.p, sizeof(int) * 2, hipMemcpyDeviceToHost, e->stream));
+    if (inlier_mask) HIPCHK(hipMemcpyAsync(inlier_mask, e->rh_mask.p, e->n, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (inliers) *inliers = out_i[0];
+    if (fits_accepted) *fits_accepted = out_i[1];
+    return MH_OK;
+    });
+}
+
 int mh_inlier_moments(mh_engine* e, double thr2, double* moments, double* min_eig)
 {
     return guarded([&]() -> int {

@@ -112,6 +112,12 @@ hipError_t launch_sampson_score(const Points& p, const double* F, int M, double 
 hipError_t launch_fund_refit(const Points& p, const double* F_in, double thr2, double* F_out,
                              unsigned char* mask_out, int* count_out, hipStream_t s, int metric);
 
+// --- refit_h.hip: one homography refitted to its inliers, every round inside one launch (mh_refit_homography) ---
+// H_in, H_out: 9 doubles each on the device; mask_out: p.n bytes; out_i[2]: inliers of H_out, fits accepted
+constexpr int REFIT_H_MAX_ITERATIONS = 16;
+hipError_t launch_refit_h(const Points& p, const double* H_in, double thr2, int iterations, double* H_out,
+                          unsigned char* mask_out, int* out_i, hipStream_t s);
+
 // --- datacost.hip -----------------------------------------------------------
 // the data cost of every model against every point, int32, model-major with pitch ldc (datacost.hip)
 inline long long cost_ld(int n) { return ((long long)n + 31) & ~31ll; }

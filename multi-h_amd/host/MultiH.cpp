@@ -33,6 +33,8 @@
 #pragma weak mh_score_msac
 #pragma weak mh_select_best_msac
 #pragma weak mh_get_model
+// ... and for the refit of the tail's winner (SetTailRefit): without its entry point that mode fails with a message.
+#pragma weak mh_refit_homography
 // ... and for the selection ranked by weight (SetSelectionScore): without its entry point that mode fails with a message.
 #pragma weak mh_select_greedy_msac
 // ... and for the HAF proposals (SetProposalSource): without its entry point that source fails with a message.
@@ -351,6 +353,15 @@ bool MultiH::Run(bool points_only)
     }
     if (tail_score == TAIL_SCORE_MSAC && (!mh_score_msac || !mh_select_best_msac || !mh_get_model)) {
         std::cerr << "Error: the engine library has no MSAC scores (mh_score_msac, mh_select_best_msac, mh_get_model)\n";
+        return false;
+    }
+    // whether the degenerate tail refits its winner
+    if (tail_refit < 0 || tail_refit > 16) {
+        std::cerr << "Error: tail refit iterations " << tail_refit << " outside [0, 16]\n";
+        return false;
+    }
+    if (tail_refit > 0 && (!mh_refit_homography || !mh_get_model)) {
+        std::cerr << "Error: the engine library has no homography refit (mh_refit_homography, mh_get_model)\n";
         return false;
     }
     // how ProposeModels ranks a batch (INIT_STABLE_SETS proposes nothing: the mode is not looked at)
@@ -1048,11 +1059,30 @@ void MultiH::HandleDegenerateCase()
     const int M = std::max(proposal_hypotheses, 1000);
     if (!ApplyProposalSampler(false)) return;          // this batch is uniform whatever SetProposalSampler says (the oracle's mho_handle_degenerate defines it)
     if (!Check(mh_propose_dlt4(engine, proposal_seed ^ 0xdeadull, 0, M), "mh_propose_dlt4")) return;
+    // the winner: by weight (the scores stay on the device, the engine's arg-max picks) or by count (the first maximum)
+    long long best = 0;
     if (tail_score == TAIL_SCORE_MSAC) {
-        // by weight: the scores stay on the device, the engine's arg-max picks, one H comes back
-        long long best = 0;
         if (!Check(mh_score_msac(engine, sqr_threshold_homography, nullptr, nullptr, nullptr), "mh_score_msac")) return;
         if (!Check(mh_select_best_msac(engine, &best, nullptr, nullptr), "mh_select_best_msac")) return;
+    } else {
+        std::vector<int> counts(M);
+        if (!Check(mh_score(engine, sqr_threshold_homography, nullptr, counts.data()), "mh_score")) return;
+        best = std::max_element(counts.begin(), counts.end()) - counts.begin();
+    }
+    if (tail_refit > 0) {
+        // that ONE model comes back, is refitted to all its inliers on the original points, and the refit's inliers are labelled
+        double Hb[9], Hr[9];
+        if (!Check(mh_get_model(engine, (int)best, Hb), "mh_get_model")) return;
+        std::vector<unsigned char> inl(N);
+        if (!Check(mh_refit_homography(engine, Hb, sqr_threshold_homography, tail_refit, Hr, inl.data(), nullptr, nullptr),
+                   "mh_refit_homography"))
+            return;
+        for (int i = 0; i < N; ++i) labeling[i] = inl[i] ? 0 : -1;
+        cluster_homographies.push_back(MatFrom9(Hr));
+        return;
+    }
+    if (tail_score == TAIL_SCORE_MSAC) {
+        // one H comes back
         if (!Check(mh_inliers_of_model(engine, (int)best, sqr_threshold_homography, 0, labeling.data()), "mh_inliers_of_model"))
             return;
         double Hb[9];
@@ -1060,12 +1090,9 @@ void MultiH::HandleDegenerateCase()
         cluster_homographies.push_back(MatFrom9(Hb));
         return;
     }
-    std::vector<int> counts(M);
-    if (!Check(mh_score(engine, sqr_threshold_homography, nullptr, counts.data()), "mh_score")) return;
-    const int best = static_cast<int>(std::max_element(counts.begin(), counts.end()) - counts.begin());
     std::vector<double> H(9 * (size_t)M);
     if (!Check(mh_get_models(engine, H.data()), "mh_get_models")) return;
-    if (!Check(mh_inliers_of_model(engine, best, sqr_threshold_homography, 0, labeling.data()), "mh_inliers_of_model"))
+    if (!Check(mh_inliers_of_model(engine, (int)best, sqr_threshold_homography, 0, labeling.data()), "mh_inliers_of_model"))
         return;
     cluster_homographies.push_back(MatFrom9(&H[9 * (size_t)best]));
 }
@@ -1169,6 +1196,10 @@ void mhh_set_data_term(int term) { g_data_term = term; }
 static int g_tail_score = -1;
 extern "C" __attribute__((visibility("default")))
 void mhh_set_tail_score(int score) { g_tail_score = score; }
+// MultiH::SetTailRefit for the next mhh_run_process calls (< 0: the class default)
+static int g_tail_refit = -1;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_tail_refit(int iterations) { g_tail_refit = iterations; }
 // MultiH::SetSelectionScore for the next mhh_run_process calls (< 0: the class default)
 static int g_selection_score = -1;
 extern "C" __attribute__((visibility("default")))
@@ -1250,6 +1281,7 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     if (g_fund_metric >= 0) mh.SetFundamentalMetric(g_fund_metric);
     if (g_data_term >= 0) mh.SetDataTerm(g_data_term);
     if (g_tail_score >= 0) mh.SetTailScore(g_tail_score);
+    if (g_tail_refit >= 0) mh.SetTailRefit(g_tail_refit);
     if (g_selection_score >= 0) mh.SetSelectionScore(g_selection_score);
     if (g_fund_estimator >= 0) mh.SetFundamentalEstimator(g_fund_estimator, g_fund_max_samples, g_fund_confidence);
     for (const auto& kv : g_tuning) mh.SetEngineTuning(kv.first, kv.second);

@@ -145,6 +145,13 @@ public:
     // Any other value makes Process() fail with a message.
     enum { TAIL_SCORE_COUNT = 0, TAIL_SCORE_MSAC = 1 };
     void SetTailScore(int t) { tail_score = t; }
+    // Refit of the degenerate tail's winner: 0 (default) returns the 4-point hypothesis as it was proposed; n in [1, 16] hands
+    // the winner — picked exactly as above, by count or by weight — to mh_refit_homography (include/multih_hip.h: the normalised
+    // N-point DLT on all its inliers, at most n rounds, a refit kept only while it explains at least as many points), labels the
+    // refit's inliers 0 and returns the refit.  What cv::findHomography(CV_RANSAC) does behind its winning sample, without its
+    // LM polish.  Works on the point-only route and on every rank of a sharded run alike.  Any other value makes Process() fail
+    // with a message.
+    void SetTailRefit(int iterations) { tail_refit = iterations; }
     // How ProposeModels ranks the hypotheses of a batch — the initial batch, the iterative ones and the sharded route alike:
     // SELECTION_SCORE_COUNT (default) by inlier count (mh_select_greedy), SELECTION_SCORE_MSAC by the MSAC weight among the
     // hypotheses with at least min_inliers-or-8 inliers (mh_select_greedy_msac, include/multih_hip.h: the count makes a hypothesis
@@ -270,6 +277,7 @@ protected:
     int estimator = ESTIMATOR_HAF;
     int data_term = DATA_TERM_REFERENCE;
     int tail_score = TAIL_SCORE_COUNT;
+    int tail_refit = 0;
     int selection_score = SELECTION_SCORE_COUNT;
     int proposal_sampler = PROPOSAL_UNIFORM, proposal_sampler_k = 32, proposal_uniform_per_16 = 4;
     bool proposal_local_run = false;      // this Process() call proposes with the local sampler (its table is on the engine)
