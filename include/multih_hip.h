@@ -374,6 +374,59 @@ MH_API int mh_inliers_of_homography(mh_engine* e, const double* H, double thr2, 
 MH_API int mh_refit_homography(mh_engine* e, const double H_in[9], double thr2, int iterations, double H_out[9],
                                unsigned char* inlier_mask /* n, nullable */, int* inliers /* nullable */,
                                int* fits_accepted /* nullable */);
+/* Levenberg-Marquardt polish of m homographies, each over the resident correspondences that carry its label: the minimiser of
+ * the forward transfer error itself — what the route scores, thresholds and labels by (M/MultiH.cpp:434-441) — where every
+ * other estimate of the engine is a linear fit to an algebraic error.  It is the step cv::findHomography runs behind its
+ * re-estimated winner (ten rounds there; M/MultiH.cpp:725 calls it).  The loop is LMSolverImpl::run (M/Utilities.hpp:762-869;
+ * host/merge_step.cpp restates it for three parameters, lm_run3); compute() is OpenCV 3.1.0's HomographyRefineCallback, which
+ * is not in the reference tree, so this comment is the definition (tests/polish_h_numpy.py restates it).  One launch of one
+ * 256-thread workgroup per model whatever max_iterations is (csrc/polish_h.hip, k_polish_h).  It reads the points only —
+ * not the affinities, F, the resident model set, counts, weights, data cost or graph — and leaves all of them untouched.
+ *   Members     S_k = { i : labels[i] == k }, k = 0 .. m - 1; every other value (-1, >= m) belongs to nobody.
+ *   Parameters  x_j = H_in[k][j] / H_in[k][8], j = 0 .. 7.
+ *   compute(x)  per member (X, Y) -> (u, v):
+ *                 ww = (x6 * X + x7 * Y) + 1.0;  ww = |ww| > DBL_EPSILON ? 1.0 / ww : 0.0
+ *                 xi = ((x0 * X + x1 * Y) + x2) * ww      yi = ((x3 * X + x4 * Y) + x5) * ww      r = (rx, ry) = (xi - u, yi - v)
+ *               and, with a = (X * ww, Y * ww, ww), bx = (-(a0 * xi), -(a1 * xi)), by = (-(a0 * yi), -(a1 * yi)), the Jacobian rows
+ *                 [a0 a1 a2 0 0 0 bx0 bx1]      [0 0 0 a0 a1 a2 by0 by1]
+ *   Sums        every FP64 sum below in the engine's order (that of mh_refit_homography): thread t of 256 starts at 0.0 and adds
+ *               the terms of the members with index = t (mod 256) in ascending index, each as acc = acc + term; then the binary
+ *               tree s = 128 .. 1, v[t] = v[t] + v[t + s].  No fused multiply-add anywhere.  The 30 terms of a member:
+ *                 S         rx * rx + ry * ry
+ *                 v = J^T r a_i * rx (i = 0 1 2), a_i * ry (i = 0 1 2), bx0 * rx + by0 * ry, bx1 * rx + by1 * ry
+ *                 A = J^T J a_i * a_j for the pairs 00 01 02 11 12 22 (both 3 x 3 diagonal blocks; the block between them is 0),
+ *                           a_i * bx_j (A[i][6+j]) and a_i * by_j (A[3+i][6+j]), i = 0 1 2, j = 0 1,
+ *                           bx0 * bx0 + by0 * by0, bx0 * bx1 + by0 * by1, bx1 * bx1 + by1 * by1 (the last 2 x 2 block)
+ *               max |r| is the largest |rx| or |ry| of a member (a NaN is never the largest).  A candidate's Sd is the sum S alone.
+ *   pinv        of a symmetric 8 x 8 M: the cyclic Jacobi (csrc/mh_device.hpp, jacobi_sym_dev(8)) gives w and the columns V;
+ *               cut = (sum of |w_k| in index order from 0.0) * (2.0 * DBL_EPSILON); eigenvalues with |w_k| <= cut are dropped
+ *               (sym_eig_solve3's cut).  pinv(M) b: from 0.0, for the kept k in index order, proj = (sum_i V[i][k] * b[i] from
+ *               0.0) / w_k, out[i] = out[i] + proj * V[i][k].  Its diagonal: out[i] = out[i] + V[i][k] * V[i][k] / w_k.
+ *   The loop    S, A, v, max |r| = compute(x); D = diag(A), once; lambda = 1, lc = 0.75, iter = 0, accepted = 0.  Repeat:
+ *     1. Ap = A with Ap[i][i] = A[i][i] + lambda * D[i];  d = pinv(Ap) v;  xd[i] = x[i] - d[i];  Sd from compute(xd);
+ *     2. temp[i] = -(sum_j A[i][j] * d[j] from 0.0) + 2.0 * v[i];  dS = sum_i d[i] * temp[i] from 0.0;
+ *        R = (S - Sd) / (|dS| > DBL_EPSILON ? dS : 1.0);
+ *     3. R > 0.75: lambda = lambda * 0.5, then lambda = 0 when lambda < lc.
+ *        R < 0.25: t = sum_i d[i] * v[i] from 0.0;  nu = (Sd - S) / (|t| > DBL_EPSILON ? t : 1.0) + 2.0, raised to 2.0 when
+ *        nu < 2.0, lowered to 10.0 when nu > 10.0; when lambda == 0: p = the diagonal of pinv(A), maxval = the largest of
+ *        DBL_EPSILON and |p_i|, lambda = lc = 1.0 / maxval, nu = nu * 0.5; then lambda = lambda * nu;
+ *     4. Sd < S: the step is accepted — S = Sd, x = xd, ++accepted;
+ *     5. ++iter; stop when iter >= max_iterations, or max_i |d_i| < FLT_EPSILON, or an entry of d is not finite (this stop is
+ *        not in LMSolverImpl::run: there the loop would go on with x standing still);
+ *     6. after an accepted step A, v and max |r| are those of compute(x) (D stays); stop when max |r| < FLT_EPSILON.
+ *     max_iterations = 0 runs compute(x) once and reports S.
+ *   Outputs     H_out[k] = (x0 .. x7, 1.0) — the form cv::findHomography returns — when a step was accepted, otherwise H_in[k]'s
+ *               nine doubles unchanged; cost[k] = (S of H_in, S of H_out); info[k] = (|S_k|, iter, accepted, status).
+ *               status 1: |S_k| < 4; status 2 (looked at after status 1): an x_j is not finite (H_in[k][8] == 0, a NaN).  With
+ *               status 1 or 2 H_out[k] is H_in[k]'s nine doubles, cost[k] = (0, 0) and iter = accepted = 0.
+ * MH_ERR_INVALID for a null engine, labels, H_in or H_out, m outside [1, 65536], max_iterations outside
+ * [0, MH_POLISH_MAX_ITERATIONS]; MH_ERR_NOT_SET without correspondences.  H_out may be H_in.  The point-only route can call
+ * it.  Deterministic, so every rank of a sharded run (all hold all points) gets the same result without an exchange. */
+#define MH_POLISH_MAX_ITERATIONS 32
+MH_API int mh_polish_homographies(mh_engine* e, const int* labels /* n */, const double* H_in /* m x 9 */, int m,
+                                  int max_iterations, double* H_out /* m x 9 */,
+                                  double* cost /* m x 2: S before, S after; nullable */,
+                                  int* info /* m x 4: members, iterations run, steps accepted, status; nullable */);
 /* Trial statistics of HomographyCompatibilityCheck (M/MultiH.cpp:128-196; host/merge_step.cpp ClusterMedian) for
  * `clusters` clusters of at least 19 points each.  pts_xyxy: the clusters' points back to back in cluster order, 4 doubles
  * each (x1 y1 x2 y2); cluster_begin[c] .. cluster_begin[c+1] (cluster_begin[0] = 0); per (cluster, trial): tri = the

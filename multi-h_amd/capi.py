@@ -31,7 +31,7 @@ SYMBOLS = [
     "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_propose_fund7", "mh_get_fund7_samples", "mh_estimate_fundamental_minimal", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons", "mh_refine_points",
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
     "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_propose_haf", "mh_get_haf_support", "mh_propose_3pt", "mh_set_residual_mode", "mh_score", "mh_score_msac", "mh_select_best_msac",
-    "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_select_greedy_msac", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_refit_homography", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
+    "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_select_greedy_msac", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_refit_homography", "mh_polish_homographies", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
     "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
     "mh_profile_get", "mh_set_tuning",
 ]
@@ -487,6 +487,22 @@ class Engine:
         self._check(self.lib.mh_refit_homography(self._h, _p(H, C.c_double), C.c_double(thr2), int(iterations),
                                                  _p(out, C.c_double), _p(mask, C.c_ubyte), C.byref(inl), C.byref(acc)))
         return out, mask, inl.value, acc.value
+
+    def polish_homographies(self, labels, H, max_iterations: int):
+        """mh_polish_homographies: every row of H (m x 9) polished by Levenberg-Marquardt over the correspondences that carry its
+        label, all iterations in one launch; the model set is left untouched.  Returns (H_out [m, 9], cost [m, 2] = S before and
+        after, info int32 [m, 4] = members, iterations run, steps accepted, status)."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        if labels.size != self.n:
+            raise ValueError(f"labels: {labels.size} values for {self.n} correspondences")
+        H = np.ascontiguousarray(H, dtype=np.float64).reshape(-1, 9)
+        m = H.shape[0]
+        out = np.empty((m, 9), dtype=np.float64)
+        cost = np.empty((m, 2), dtype=np.float64)
+        info = np.empty((m, 4), dtype=np.int32)
+        self._check(self.lib.mh_polish_homographies(self._h, _p(labels, C.c_int), _p(H, C.c_double), m, int(max_iterations),
+                                                    _p(out, C.c_double), _p(cost, C.c_double), _p(info, C.c_int)))
+        return out, cost, info
 
     def inlier_moments(self, thr2: float):
         m = self.model_count

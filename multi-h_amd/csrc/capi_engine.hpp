@@ -216,6 +216,8 @@ struct mh_engine : ResidentBatch {                    // (e->m, e->origin, e->ha
     DevBuf<double> rh_H;                      // mh_refit_homography: H_in and H_out (18 doubles),
     DevBuf<unsigned char> rh_mask;            // the inlier flags of H_out (n bytes),
     DevBuf<int> rh_out;                       // its inlier count and the fits accepted
+    DevBuf<int> ph_labels, ph_info;           // mh_polish_homographies: the labels (n) and per model members, iterations, steps, status,
+    DevBuf<double> ph_H, ph_cost;             // H_in and H_out (2 x m x 9), S before and after (m x 2)
     DevBuf<double> moments, min_eig;
     DevBuf<double> cp_pts, cp_H, cp_out;     // mh_compat_trial_stats staging
     DevBuf<int> cp_begin, cp_tri;

@@ -486,6 +486,34 @@ int mh_refit_homography(mh_engine* e, const double H_in[9], double thr2, int ite
     });
 }
 
+int mh_polish_homographies(mh_engine* e, const int* labels, const double* H_in, int m, int max_iterations, double* H_out,
+                           double* cost, int* info)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (!labels) return fail(MH_ERR_INVALID, "null labels");
+    if (!H_in || !H_out) return fail(MH_ERR_INVALID, "null homographies");
+    if (m < 1 || m > POLISH_H_MAX_MODELS) return fail(MH_ERR_INVALID, "m outside [1, 65536]");
+    if (max_iterations < 0 || max_iterations > POLISH_H_MAX_ITERATIONS) return fail(MH_ERR_INVALID, "max_iterations outside [0, 32]");
+    int rc = require_points(e);
+    if (rc) return rc;
+    const size_t mm = (size_t)m;
+    HIPCHK(e->ph_labels.reserve(e->n));
+    HIPCHK(e->ph_H.reserve(18 * mm));
+    HIPCHK(e->ph_cost.reserve(2 * mm));
+    HIPCHK(e->ph_info.reserve(4 * mm));
+    HIPCHK(hipMemcpyAsync(e->ph_labels.p, labels, sizeof(int) * (size_t)e->n, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->ph_H.p, H_in, sizeof(double) * 9 * mm, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(launch_polish_h(e->pts(), e->ph_labels.p, e->ph_H.p, m, max_iterations, e->ph_H.p + 9 * mm, e->ph_cost.p, e->ph_info.p,
+                           e->stream));
+    HIPCHK(hipMemcpyAsync(H_out, e->ph_H.p + 9 * mm, sizeof(double) * 9 * mm, hipMemcpyDeviceToHost, e->stream));
+    if (cost) HIPCHK(hipMemcpyAsync(cost, e->ph_cost.p, sizeof(double) * 2 * mm, hipMemcpyDeviceToHost, e->stream));
+    if (info) HIPCHK(hipMemcpyAsync(info, e->ph_info.p, sizeof(int) * 4 * mm, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MH_OK;
+    });
+}
+
 int mh_inlier_moments(mh_engine* e, double thr2, double* moments, double* min_eig)
 {
     return guarded([&]() -> int {

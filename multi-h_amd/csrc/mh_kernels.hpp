@@ -118,6 +118,15 @@ constexpr int REFIT_H_MAX_ITERATIONS = 16;
 hipError_t launch_refit_h(const Points& p, const double* H_in, double thr2, int iterations, double* H_out,
                           unsigned char* mask_out, int* out_i, hipStream_t s);
 
+// --- polish_h.hip: Levenberg-Marquardt polish of one homography per label, every iteration inside one launch of one workgroup
+// per model (mh_polish_homographies) ---
+// labels: p.n ints on the device; H_in, H_out: m x 9 doubles; cost: m x 2 doubles (S before, S after); info: m x 4 ints
+// (members, iterations run, steps accepted, status), all on the device
+constexpr int POLISH_H_MAX_ITERATIONS = 32;
+constexpr int POLISH_H_MAX_MODELS = 65536;
+hipError_t launch_polish_h(const Points& p, const int* labels, const double* H_in, int m, int max_iterations, double* H_out,
+                           double* cost, int* info, hipStream_t s);
+
 // --- datacost.hip -----------------------------------------------------------
 // the data cost of every model against every point, int32, model-major with pitch ldc (datacost.hip)
 inline long long cost_ld(int n) { return ((long long)n + 31) & ~31ll; }

@@ -35,6 +35,8 @@
 #pragma weak mh_get_model
 // ... and for the refit of the tail's winner (SetTailRefit): without its entry point that mode fails with a message.
 #pragma weak mh_refit_homography
+// ... and for the LM polish of the results (SetTailPolish, SetModelPolish): without its entry point those modes fail with a message.
+#pragma weak mh_polish_homographies
 // ... and for the selection ranked by weight (SetSelectionScore): without its entry point that mode fails with a message.
 #pragma weak mh_select_greedy_msac
 // ... and for the HAF proposals (SetProposalSource): without its entry point that source fails with a message.
@@ -364,6 +366,23 @@ bool MultiH::Run(bool points_only)
         std::cerr << "Error: the engine library has no homography refit (mh_refit_homography, mh_get_model)\n";
         return false;
     }
+    // whether the tail's result and the final models are polished
+    if (tail_polish < 0 || tail_polish > 32) {
+        std::cerr << "Error: tail polish iterations " << tail_polish << " outside [0, 32]\n";
+        return false;
+    }
+    if (model_polish < 0 || model_polish > 32) {
+        std::cerr << "Error: model polish iterations " << model_polish << " outside [0, 32]\n";
+        return false;
+    }
+    if ((tail_polish > 0 || model_polish > 0) && !mh_polish_homographies) {
+        std::cerr << "Error: the engine library has no homography polish (mh_polish_homographies)\n";
+        return false;
+    }
+    if (tail_polish > 0 && !mh_get_model) {
+        std::cerr << "Error: the engine library has no single-model read-back for the tail's polish (mh_get_model)\n";
+        return false;
+    }
     // how ProposeModels ranks a batch (INIT_STABLE_SETS proposes nothing: the mode is not looked at)
     if (init_mode != INIT_STABLE_SETS) {
         if (selection_score != SELECTION_SCORE_COUNT && selection_score != SELECTION_SCORE_MSAC) {
@@ -576,8 +595,31 @@ bool MultiH::Run(bool points_only)
         labeling.resize(src_points.size(), -1);
         cluster_homographies.resize(0);
         HandleDegenerateCase();
+    } else if (model_polish > 0) {
+        // every cluster's homography polished over its labelled (refined) correspondences: the engine still holds them
+        const int nh = static_cast<int>(cluster_homographies.size());
+        if (labeling.size() != src_points.size()) {
+            std::cerr << "Error: model polish: " << labeling.size() << " labels for " << src_points.size() << " correspondences\n";
+            return false;
+        }
+        std::vector<double> H(9 * (size_t)nh);
+        for (int i = 0; i < nh; ++i) {
+            const double* p = reinterpret_cast<const double*>(cluster_homographies[i].data);
+            for (int k = 0; k < 9; ++k) H[9 * (size_t)i + k] = p[k];
+        }
+        if (!Check(mh_polish_homographies(engine, labeling.data(), H.data(), nh, model_polish, H.data(), nullptr, nullptr),
+                   "mh_polish_homographies"))
+            return false;
+        for (int i = 0; i < nh; ++i) cluster_homographies[i] = MatFrom9(&H[9 * (size_t)i]);
     }
     return true;
+}
+
+// The tail's model polished over its inliers (labeling: 0 = inlier) on the original points, which the engine holds here
+bool MultiH::PolishTailModel(double H[9])
+{
+    if (tail_polish <= 0) return true;
+    return Check(mh_polish_homographies(engine, labeling.data(), H, 1, tail_polish, H, nullptr, nullptr), "mh_polish_homographies");
 }
 
 void MultiH::HomographyCompatibilityCheck()
@@ -1078,15 +1120,17 @@ void MultiH::HandleDegenerateCase()
                    "mh_refit_homography"))
             return;
         for (int i = 0; i < N; ++i) labeling[i] = inl[i] ? 0 : -1;
+        if (!PolishTailModel(Hr)) return;
         cluster_homographies.push_back(MatFrom9(Hr));
         return;
     }
-    if (tail_score == TAIL_SCORE_MSAC) {
-        // one H comes back
+    if (tail_score == TAIL_SCORE_MSAC || tail_polish > 0) {
+        // one H comes back; its inliers are labelled, and with SetTailPolish it is polished over them
         if (!Check(mh_inliers_of_model(engine, (int)best, sqr_threshold_homography, 0, labeling.data()), "mh_inliers_of_model"))
             return;
         double Hb[9];
         if (!Check(mh_get_model(engine, (int)best, Hb), "mh_get_model")) return;
+        if (!PolishTailModel(Hb)) return;
         cluster_homographies.push_back(MatFrom9(Hb));
         return;
     }
@@ -1200,6 +1244,12 @@ void mhh_set_tail_score(int score) { g_tail_score = score; }
 static int g_tail_refit = -1;
 extern "C" __attribute__((visibility("default")))
 void mhh_set_tail_refit(int iterations) { g_tail_refit = iterations; }
+// MultiH::SetTailPolish and MultiH::SetModelPolish for the next mhh_run_process calls (< 0: the class default)
+static int g_tail_polish = -1, g_model_polish = -1;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_tail_polish(int iterations) { g_tail_polish = iterations; }
+extern "C" __attribute__((visibility("default")))
+void mhh_set_model_polish(int iterations) { g_model_polish = iterations; }
 // MultiH::SetSelectionScore for the next mhh_run_process calls (< 0: the class default)
 static int g_selection_score = -1;
 extern "C" __attribute__((visibility("default")))
@@ -1260,11 +1310,13 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     // r06: the affinities as NON-owning 2 x 2 headers over one copy of the caller's array (cv::Mat(rows, cols, type, data): the
     // same with the real library) — 50 000 matrices that each own a 32-byte allocation cost 5 ms to build and to copy, a third
     // of what this hook reported as "Process()" at configs[4].  The copy outlives the call below.
-    std::vector<double> aff_copy(aff, aff + 4 * (size_t)n);
+    // aff == NULL: the point-only route, Process(src, dst)
+    std::vector<double> aff_copy;
+    if (aff) aff_copy.assign(aff, aff + 4 * (size_t)n);
     for (int i = 0; i < n; ++i) {
         s[i] = cv::Point2d(src_xy[2 * i], src_xy[2 * i + 1]);
         d[i] = cv::Point2d(dst_xy[2 * i], dst_xy[2 * i + 1]);
-        a[i] = cv::Mat(2, 2, CV_64F, aff_copy.data() + 4 * (size_t)i);
+        if (aff) a[i] = cv::Mat(2, 2, CV_64F, aff_copy.data() + 4 * (size_t)i);
     }
     MultiH mh(thr_F, thr_H, locality, lambda, min_inliers);
     if (F && e2) mh.SetEpipolarGeometry(F, e2);
@@ -1282,6 +1334,8 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     if (g_data_term >= 0) mh.SetDataTerm(g_data_term);
     if (g_tail_score >= 0) mh.SetTailScore(g_tail_score);
     if (g_tail_refit >= 0) mh.SetTailRefit(g_tail_refit);
+    if (g_tail_polish >= 0) mh.SetTailPolish(g_tail_polish);
+    if (g_model_polish >= 0) mh.SetModelPolish(g_model_polish);
     if (g_selection_score >= 0) mh.SetSelectionScore(g_selection_score);
     if (g_fund_estimator >= 0) mh.SetFundamentalEstimator(g_fund_estimator, g_fund_max_samples, g_fund_confidence);
     for (const auto& kv : g_tuning) mh.SetEngineTuning(kv.first, kv.second);
@@ -1296,7 +1350,7 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
         for (int i = 0; i < n_init; ++i) hs.push_back(MatFrom9(init_H + 9 * (size_t)i));
         mh.SetInitialHomographies(hs);
     }
-    if (!mh.Process(s, d, a)) return -1;
+    if (aff ? !mh.Process(s, d, a) : !mh.Process(s, d)) return -1;
     {
         const MultiH::FrontStages st = mh.GetFrontStages();
         g_front_stages[0] = st.input; g_front_stages[1] = st.in_ransac_mask; g_front_stages[2] = st.triangulated; g_front_stages[3] = st.affine_consistent;

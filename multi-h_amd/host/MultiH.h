@@ -152,6 +152,18 @@ public:
     // LM polish.  Works on the point-only route and on every rank of a sharded run alike.  Any other value makes Process() fail
     // with a message.
     void SetTailRefit(int iterations) { tail_refit = iterations; }
+    // Levenberg-Marquardt polish of the degenerate tail's result: 0 (default) off; n in [1, 32] hands the tail's model — the
+    // winner, refitted when SetTailRefit says so — with its inliers on the original points as label 0 to
+    // mh_polish_homographies (include/multih_hip.h: at most n iterations of OpenCV's LM schedule on the forward transfer error)
+    // and returns the polished model.  The labels stay those of the model in front of the polish, as OpenCV's mask does.
+    // SetTailRefit(1) with SetTailPolish(10) is cv::findHomography's sequence.  Any other value makes Process() fail with a
+    // message.
+    void SetTailPolish(int iterations) { tail_polish = iterations; }
+    // The same polish at the very end of Process() on the normal path (more than one cluster left, after the compatibility
+    // check): every cluster's homography over the correspondences that carry its label, in one call.  Labels, energy and
+    // iteration count are unchanged.  0 (default) off; n in [1, 32]; works on the point-only route and on every rank of a
+    // sharded run alike.  Any other value makes Process() fail with a message.
+    void SetModelPolish(int iterations) { model_polish = iterations; }
     // How ProposeModels ranks the hypotheses of a batch — the initial batch, the iterative ones and the sharded route alike:
     // SELECTION_SCORE_COUNT (default) by inlier count (mh_select_greedy), SELECTION_SCORE_MSAC by the MSAC weight among the
     // hypotheses with at least min_inliers-or-8 inliers (mh_select_greedy_msac, include/multih_hip.h: the count makes a hypothesis
@@ -278,6 +290,7 @@ protected:
     int data_term = DATA_TERM_REFERENCE;
     int tail_score = TAIL_SCORE_COUNT;
     int tail_refit = 0;
+    int tail_polish = 0, model_polish = 0;
     int selection_score = SELECTION_SCORE_COUNT;
     int proposal_sampler = PROPOSAL_UNIFORM, proposal_sampler_k = 32, proposal_uniform_per_16 = 4;
     bool proposal_local_run = false;      // this Process() call proposes with the local sampler (its table is on the engine)
@@ -319,6 +332,7 @@ protected:
     bool LabelingStep(double& energy, bool changed);   // :513-602
     void ComputeInliersOfHomography(int idx);          // :743-768
     void HandleDegenerateCase();                       // :719-741 (single best DLT model)
+    bool PolishTailModel(double H[9]);                 // SetTailPolish: the tail's model over its labelled inliers
 };
 
 namespace multih {

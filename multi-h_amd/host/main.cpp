@@ -29,6 +29,11 @@
 //                                default, by inlier count; msac by the fit-weighted score of mh_score_msac
 //                  [--tail-refit N]   the degenerate tail refits its winner to all its inliers, at most N rounds (MultiH::SetTailRefit;
 //                                0, the default, returns the 4-point hypothesis; N <= 16)
+//                  [--tail-polish N]  the degenerate tail polishes its result — the winner, refitted when --tail-refit says so — by at
+//                                most N Levenberg-Marquardt iterations on the transfer error of its inliers (MultiH::SetTailPolish;
+//                                0, the default, off; N <= 32); --tail-refit 1 --tail-polish 10 is cv::findHomography's sequence
+//                  [--polish N]       every final cluster's homography polished the same way over its labelled correspondences
+//                                (MultiH::SetModelPolish; 0, the default, off; N <= 32)
 //                  [--select-score count|msac]   how the proposal batches are ranked (MultiH::SetSelectionScore): count, the default,
 //                                by inlier count (mh_select_greedy); msac by the MSAC weight among the hypotheses with enough
 //                                inliers (mh_select_greedy_msac)
@@ -119,7 +124,7 @@ int main(int argc, char** argv)
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
                      "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] [--f-estimator ls8|minimal] "
-                     "[--stages file] [--points] [--estimator haf|3pt] [--data-term reference|rising] [--tail-score count|msac] [--tail-refit N] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
+                     "[--stages file] [--points] [--estimator haf|3pt] [--data-term reference|rising] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
         return 2;
     }
     double thrF = 2.6, thrH = 2.2, locality = 0.005, lambda = 0.5;     // M/main.cpp:55-59
@@ -134,7 +139,7 @@ int main(int argc, char** argv)
     int estimator = MultiH::ESTIMATOR_HAF;
     int data_term = MultiH::DATA_TERM_REFERENCE;
     int tail_score = MultiH::TAIL_SCORE_COUNT;
-    int tail_refit = 0;
+    int tail_refit = 0, tail_polish = 0, model_polish = 0;
     int select_score = MultiH::SELECTION_SCORE_COUNT;
     int sampler = MultiH::PROPOSAL_UNIFORM, sampler_k = 32, sampler_u = 4;
     int proposals = MultiH::PROPOSAL_SOURCE_DLT, haf_members = 16, haf_stride = 1;
@@ -166,6 +171,14 @@ int main(int argc, char** argv)
                 return 2;
             }
             tail_refit = atoi(v);
+        }
+        else if (k == "--tail-polish" || k == "--polish") {
+            const std::string tv = v;
+            if (tv.empty() || tv.size() > 2 || tv.find_first_not_of("0123456789") != std::string::npos || atoi(v) > 32) {
+                std::cerr << k << ": a whole number in [0, 32]\n";
+                return 2;
+            }
+            (k == "--polish" ? model_polish : tail_polish) = atoi(v);
         }
         else if (k == "--select-score") {
             if (std::string(v) == "count") select_score = MultiH::SELECTION_SCORE_COUNT;
@@ -369,6 +382,8 @@ int main(int argc, char** argv)
     multiH->SetDataTerm(data_term);
     multiH->SetTailScore(tail_score);
     multiH->SetTailRefit(tail_refit);
+    multiH->SetTailPolish(tail_polish);
+    multiH->SetModelPolish(model_polish);
     multiH->SetSelectionScore(select_score);
     multiH->SetProposalSampler(sampler, sampler_k, sampler_u);
     multiH->SetProposalSource(proposals, haf_members, haf_stride);
