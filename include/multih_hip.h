@@ -474,7 +474,7 @@ MH_API int mh_set_transport(mh_engine* e, int rank, int world, mh_allgather_stre
  * nothing, sets the record's error word, and after the exchange every rank leaves the loop — the failing one with its
  * own error, the others with MH_ERR_HIP "a rank reported an error".  Arguments (thr2, need, max_models, total_m) must be
  * the same on every rank, and so must the settings the records' mode word carries: the residual mode, refitted winners and their
- * estimator, the sampler, (bit 15) whether the rank ranks by count — this entry point — or by weight
+ * estimator (bits 2 and 24), the sampler, (bit 15) whether the rank ranks by count — this entry point — or by weight
  * (mh_select_greedy_msac), (bit 16, bits 17-22) whether the resident batch is mh_propose_haf's and with how many members, and
  * (bit 23) whether it is mh_propose_3pt's;
  * ranks that disagree all return MH_ERR_INVALID after the first exchange. */
@@ -494,7 +494,7 @@ MH_API int mh_select_greedy(mh_engine* e, double thr2, int need, int max_models,
  *                    take the hypothesis' H, batch position, count and weight at the moment it was selected.
  *   5. Compaction.   Candidates with count_c >= need move on to the next round, the winner does not (counts and weights only
  *                    fall as S shrinks).
- *   6. Refit (mh_set_tuning key 30; HAF or MH_ESTIMATOR_3PT as for mh_select_greedy).  The winner is refitted to its inliers on S;
+ *   6. Refit (mh_set_tuning key 30; HAF, MH_ESTIMATOR_3PT or MH_ESTIMATOR_DLT as for mh_select_greedy).  The winner is refitted to its inliers on S;
  *                    the refit takes its place in the claim and in H_out when it is finite and its WEIGHT on S is at least the
  *                    hypothesis' weight (mh_select_greedy: "explains at least as many points").  counts_out and weights_out
  *                    stay the hypothesis' own.
@@ -616,16 +616,34 @@ MH_API int mh_get_core_components(mh_engine* e, int* out /* moves x 16 */, int m
  *   MH_ESTIMATOR_3PT  GetHomography3PT without LM refinement (M/MultiH.cpp:995-1050) over each label's members: H = [e']x F + e' v^T
  *                     by least squares from the points alone; needs the epipolar geometry, not the affinities.  A label with
  *                     fewer than 3 members keeps its H (as does one whose fit is not finite).
- * Sticky per engine; mh_set_correspondences does not reset it.  The ranks of a sharded mh_select_greedy must agree on it. */
+ *   MH_ESTIMATOR_DLT  the normalised N-point DLT over each label's members, from the points alone: needs neither the epipolar
+ *                     geometry nor the affinities (csrc/reestimate_dlt.hip, k_dlt_reestimate).  For label k = 0 .. Nh-1,
+ *                     S_k = { i : labels[i] == k } (labels of -1 or >= Nh belong to nobody) and H[k] = fit(S_k), with fit(S)
+ *                     exactly as defined under mh_refit_homography: its steps 1-7, every FP64 sum in the engine's order (thread
+ *                     t of 256 adds the members with index = t (mod 256) in ascending index from 0.0, then the binary tree
+ *                     128 .. 1), no fused multiply-add, jacobi_sym_dev(9) and the column of the smallest eigenvalue (the first
+ *                     index on ties), k_dlt4's de-normalisation, unit Frobenius norm, h33 >= 0.  When the fit fails (|S_k| < 4,
+ *                     a scale that is not finite, an entry of the result that is not finite) the label keeps its H's nine
+ *                     doubles unchanged.  (Members that are all one point fail through the scale only where the centroid comes
+ *                     out as that point exactly; where it rounds away from it the scales are finite and the fit is what the
+ *                     steps give.)  There is no acceptance test against inlier counts: the loop's re-estimators replace
+ *                     unconditionally, and under key 30 the selection's own rule decides.  MH_BUF_LABEL_COUNTS receives |S_k|.
+ * Sticky per engine; mh_set_correspondences does not reset it.  The ranks of a sharded mh_select_greedy must agree on it.
+ * Another value: MH_ERR_INVALID. */
 #define MH_ESTIMATOR_HAF 0
 #define MH_ESTIMATOR_3PT 1
+#define MH_ESTIMATOR_DLT 2
 MH_API int mh_set_estimator(mh_engine* e, int estimator);
 /* GetHomographyHAFNonminimal for every label (M/MultiH.cpp:913-989 + the 1/lambda rescale of
- * Homography_RefineHAFCallback.h:33-34), or the 3-point fit under MH_ESTIMATOR_3PT.  labels: -1..Nh-1 per point.  Updates the
- * current model set in place; H_out (nullable) receives a host copy. */
+ * Homography_RefineHAFCallback.h:33-34), or the 3-point fit under MH_ESTIMATOR_3PT, or the N-point DLT under MH_ESTIMATOR_DLT.
+ * labels: -1..Nh-1 per point.  Updates the current model set in place (the data cost goes stale); H_out (nullable) receives a
+ * host copy.  Needs: HAF the affinities and mh_set_epipolar, 3PT mh_set_epipolar, DLT correspondences and models only (a
+ * missing mh_set_epipolar or missing affinities is no error there). */
 MH_API int mh_reestimate(mh_engine* e, const int* labels, double* H_out);
 /* LabelingStep (M/MultiH.cpp:513-602): data cost -> expansion (warm start iff warm != 0, from
- * `labeling` + 1) -> labels - 1 -> re-estimation (the engine's estimator).  labeling: in/out n ints (-1..Nh-1). */
+ * `labeling` + 1) -> labels - 1 -> re-estimation (the engine's estimator).  labeling: in/out n ints (-1..Nh-1).
+ * Needs the neighbour graph and what the estimator needs (see mh_reestimate): under MH_ESTIMATOR_DLT neither affinities nor
+ * mh_set_epipolar. */
 MH_API int mh_labeling_step(mh_engine* e, int warm, int* labeling, double* energy, int* cycles);
 
 /* ---- device-side access (bench / multi-GPU plumbing) --------------------- */
@@ -688,7 +706,8 @@ MH_API int mh_profile_get(mh_engine* e, int kernel, int* launches, double* total
  *  29   S     12      mean shift: at most this many running climbs of a batch finish in one persistent launch (0 = a launch per iteration)
  *  30   R     0       mh_select_greedy refits every round's winner to the correspondences of the support set it explains (the loop's
  *                     per-label HAF least squares, M/MultiH.cpp:913-989, one label; needs affinities and the epipolar geometry; under
- *                     MH_ESTIMATOR_3PT the 3-point least squares, which needs the epipolar geometry alone) before it
+ *                     MH_ESTIMATOR_3PT the 3-point least squares, which needs the epipolar geometry alone; under MH_ESTIMATOR_DLT
+ *                     the N-point DLT fit over the winner's inliers on the support set, which needs the points alone) before it
  *                     claims them; the refit takes the hypothesis' place when it is finite and explains at least as many.  Sticky per engine;
  *                     class MultiH sets it on every call (SetProposalRefit, default on).  The ranks of a sharded batch must agree on it
  *                     (their records carry it; r06).

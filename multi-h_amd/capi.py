@@ -18,7 +18,7 @@ ERR_NAMES = {-1: "MH_ERR_NO_DEVICE", -2: "MH_ERR_INVALID", -3: "MH_ERR_HIP", -4:
              -5: "MH_ERR_OVERFLOW"}
 BUF_COUNTS, BUF_MODELS, BUF_RESIDUALS, BUF_LABELS, BUF_COST, BUF_LABEL_COUNTS, BUF_WEIGHTS = 0, 1, 2, 3, 4, 6, 7
 MSAC_SCALE = 256                       # MH_MSAC_SCALE
-ESTIMATORS = {"haf": 0, "3pt": 1}      # MH_ESTIMATOR_HAF, MH_ESTIMATOR_3PT
+ESTIMATORS = {"haf": 0, "3pt": 1, "dlt": 2}      # MH_ESTIMATOR_HAF, MH_ESTIMATOR_3PT, MH_ESTIMATOR_DLT
 SAMPLER_UNIFORM, SAMPLER_LOCAL = 0, 1  # MH_SAMPLER_UNIFORM, MH_SAMPLER_LOCAL
 DATA_TERMS = {"reference": 0, "rising": 1}      # MH_DATA_TERM_REFERENCE, MH_DATA_TERM_RISING
 K_DLT4, K_RESIDUAL, K_SCORE, K_DATACOST, K_EXPAND, K_REESTIMATE, K_COSTMATRIX = 0, 1, 2, 3, 4, 5, 6
@@ -582,9 +582,9 @@ class Engine:
         return out
 
     def set_estimator(self, name: str):
-        """mh_set_estimator: "haf" (default) or "3pt" (point-only least squares)."""
+        """mh_set_estimator: "haf" (default), "3pt" (point-only least squares with F) or "dlt" (N-point DLT, no F)."""
         if name not in ESTIMATORS:
-            raise ValueError(f"unknown estimator {name!r} (haf | 3pt)")
+            raise ValueError(f"unknown estimator {name!r} (haf | 3pt | dlt)")
         self._check(self.lib.mh_set_estimator(self._h, ESTIMATORS[name]))
 
     def set_data_term(self, name: str):
@@ -611,6 +611,24 @@ class Engine:
         ptr, nbytes = C.c_void_p(), C.c_ulonglong(0)
         self._check(self.lib.mh_device_buffer(self._h, int(which), C.byref(ptr), C.byref(nbytes)))
         return ptr.value, nbytes.value
+
+    def label_counts(self):
+        """MH_BUF_LABEL_COUNTS on the host: per label its member count in the last re-estimation (mh_reestimate /
+        mh_labeling_step), one int32 per model.  Copied by the HIP runtime the engine itself has loaded (a second runtime
+        client in the process, such as torch, is not needed and not started)."""
+        ptr, nbytes = self.device_buffer(6)
+        m = self.model_count
+        if not ptr or nbytes < 4 * m:
+            raise MultiHError(-4, "no label counts: no re-estimation has run on this model set")
+        hip = C.CDLL("libamdhip64.so", mode=C.RTLD_GLOBAL)
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        hip.hipMemcpy.restype = C.c_int
+        out = np.empty(m, dtype=np.int32)
+        self.synchronize()
+        rc = hip.hipMemcpy(out.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), 4 * m, 2)      # hipMemcpyDeviceToHost
+        if rc != 0:
+            raise MultiHError(-3, f"hipMemcpy of the label counts failed ({rc})")
+        return out
 
     def profile_enable(self, on: bool = True):
         self._check(self.lib.mh_profile_enable(self._h, int(bool(on))))

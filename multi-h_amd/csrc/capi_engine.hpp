@@ -477,7 +477,7 @@ int score_models(mh_engine* e, const Points& p, const double* Hs, int m, double 
 // follows score_models' preconditions to the letter; false for mh_score_msac (pretest_usable, capi_score.hip).
 int msac_models(mh_engine* e, const Points& p, const double* Hs, int m, double thr2, const unsigned char* dmask, int* counts_dev,
                 int* weights_dev, bool plain_variant_only);
-// the engine's re-estimator over labels_dev (n ints) for models H_dev (Nh x 9, in place) — HAF or 3-point (capi_label.hip)
+// the engine's re-estimator over labels_dev (n ints) for models H_dev (Nh x 9, in place) — HAF, 3-point or N-point DLT (capi_label.hip)
 int launch_estimator(mh_engine* e, const int* labels_dev, int Nh, double* H_dev, int* counts_dev);
 // the exchange's stream and events (capi_select.hip); the second stream of the prefetch queue and its events (capi_score.hip)
 int ensure_xchg_stream(mh_engine* e);

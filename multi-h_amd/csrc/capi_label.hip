@@ -365,6 +365,10 @@ namespace mhe {
 int launch_estimator(mh_engine* e, const int* labels_dev, int Nh, double* H_dev, int* counts_dev)
 {
     ScopedTimer t(e, MH_K_REESTIMATE);
+    if (e->estimator == MH_ESTIMATOR_DLT) {
+        HIPCHK(launch_reestimate_dlt(e->pts(), labels_dev, Nh, H_dev, counts_dev, e->stream));
+        return MH_OK;
+    }
     if (e->estimator == MH_ESTIMATOR_3PT) {
         HIPCHK(e->r3_scratch.reserve(reestimate_3pt_scratch_ints(e->n, Nh)));
         HIPCHK(launch_reestimate_3pt(e->pts(), labels_dev, Nh, e->epi, H_dev, counts_dev, e->r3_scratch.p, e->stream,
@@ -385,7 +389,8 @@ int mh_set_estimator(mh_engine* e, int estimator)
     return guarded([&]() -> int {
     int rc = enter(e);
     if (rc) return rc;
-    if (estimator != MH_ESTIMATOR_HAF && estimator != MH_ESTIMATOR_3PT) return fail(MH_ERR_INVALID, "unknown estimator");
+    if (estimator != MH_ESTIMATOR_HAF && estimator != MH_ESTIMATOR_3PT && estimator != MH_ESTIMATOR_DLT)
+        return fail(MH_ERR_INVALID, "unknown estimator");
     e->estimator = estimator;
     return MH_OK;
     });
@@ -409,7 +414,7 @@ int mh_reestimate(mh_engine* e, const int* labels, double* H_out)
     if (rc) return rc;
     if (!labels) return fail(MH_ERR_INVALID, "labels is null");
     if (e->estimator == MH_ESTIMATOR_HAF && !e->have_aff) return fail(MH_ERR_NOT_SET, "affinities are not set");
-    if (!e->have_epi) return fail(MH_ERR_NOT_SET, "fundamental matrix / epipole are not set");
+    if (e->estimator != MH_ESTIMATOR_DLT && !e->have_epi) return fail(MH_ERR_NOT_SET, "fundamental matrix / epipole are not set");
     HIPCHK(e->labels_pts.reserve(e->n));
     HIPCHK(e->label_counts.reserve(e->m));
     HIPCHK(hipMemcpyAsync(e->labels_pts.p, labels, sizeof(int) * e->n, hipMemcpyHostToDevice, e->stream));
@@ -432,7 +437,7 @@ int mh_labeling_step(mh_engine* e, int warm, int* labeling, double* energy, int*
     if (!labeling) return fail(MH_ERR_INVALID, "labeling is null");
     if (e->estimator == MH_ESTIMATOR_HAF && (!e->have_aff || !e->have_epi))
         return fail(MH_ERR_NOT_SET, "affinities / epipolar geometry are not set");
-    if (!e->have_epi) return fail(MH_ERR_NOT_SET, "epipolar geometry is not set");
+    if (e->estimator != MH_ESTIMATOR_DLT && !e->have_epi) return fail(MH_ERR_NOT_SET, "epipolar geometry is not set");
     rc = do_data_cost(e);
     if (rc) return rc;
     const int* init_dev = nullptr;

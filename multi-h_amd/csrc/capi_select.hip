@@ -42,7 +42,8 @@ int selection_mode_word(const mh_engine* e, bool by_weight)
 {
     int w = 0;
     if (e->residual_mode == MH_RESIDUAL_SYMMETRIC) w |= SEL_MODE_SYMMETRIC;
-    if (e->tune_select_refine != 0) w |= SEL_MODE_REFIT | (e->estimator == MH_ESTIMATOR_3PT ? SEL_MODE_REFIT_3PT : 0);
+    if (e->tune_select_refine != 0)
+        w |= SEL_MODE_REFIT | (e->estimator == MH_ESTIMATOR_3PT ? SEL_MODE_REFIT_3PT : 0) | (e->estimator == MH_ESTIMATOR_DLT ? SEL_MODE_REFIT_DLT : 0);
     if (e->sampler == MH_SAMPLER_LOCAL)
         w |= SEL_MODE_SAMPLER_LOCAL | (e->smp_k << SEL_MODE_SAMPLER_K_SHIFT) | (e->sampler_uniform_per_16 << SEL_MODE_SAMPLER_UNIFORM_SHIFT);
     if (by_weight) w |= SEL_MODE_BY_WEIGHT;
@@ -90,10 +91,11 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
     // r06 (advisor): affinities / epipolar geometry missing is the state of THIS rank's engine — it goes through local_failure like
     // every other rank-local error (returning here would leave the peers waiting in the all-gather); the setting itself travels in
     // the records' mode word.  Under the 3-point estimator (mh_set_estimator) the refit is the point-only fit and needs the
-    // epipolar geometry alone.
+    // epipolar geometry alone; under the DLT estimator it is the N-point DLT over the winner's inliers and needs the points alone.
     const bool refine = e->tune_select_refine != 0;
     const bool refit3 = e->estimator == MH_ESTIMATOR_3PT;
-    const bool refine_usable = refine && e->have_epi && (refit3 || e->have_aff);
+    const bool refit_dlt = e->estimator == MH_ESTIMATOR_DLT;
+    const bool refine_usable = refine && (refit_dlt || (e->have_epi && (refit3 || e->have_aff)));
     const int mode_word = selection_mode_word(e, by_weight);
     if (refine && !refine_usable)
         local_failure(MH_ERR_NOT_SET, std::string(by_weight ? "mh_select_greedy_msac" : "mh_select_greedy") +
@@ -236,7 +238,8 @@ int select_greedy(mh_engine* e, double thr2, int need, int max_models, unsigned 
             // every rank holds all the points and the same records: the refit is computed redundantly, identically
             Affines aff{ e->a11.p, e->a12.p, e->a21.p, e->a22.p };
             HIPCHK(launch_sel_refit(e->pts(), aff, e->epi, records, world, thr2, e->mask.p, e->labels_pts.p, e->sel_refit.p,
-                                    e->sel_refit_ctr.p, e->sel_refit_ctr.p + 1, s, by_weight, symmetric, refit3 ? e->r3_scratch.p : nullptr));
+                                    e->sel_refit_ctr.p, e->sel_refit_ctr.p + 1, s, by_weight, symmetric, refit3 ? e->r3_scratch.p : nullptr,
+                                    refit_dlt));
             refit = e->sel_refit.p;
         }
         const unsigned long long* check = gather_scores && !local_err ? key_check : nullptr;

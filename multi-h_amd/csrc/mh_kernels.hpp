@@ -148,6 +148,11 @@ size_t reestimate_3pt_scratch_ints(int n, int Nh);
 hipError_t launch_reestimate_3pt(const Points& p, const int* labels, int Nh, const Epipolar& ep, double* H, int* counts,
                                  int* scratch, hipStream_t s, int form = 0);
 
+// --- reestimate_dlt.hip: the re-estimator without epipolar geometry (the normalised N-point DLT over every label's members) ---
+// H[k] = fit(S_k) of mh_refit_homography's rule, the members found by the match loop (part of the definition of the sums'
+// order); a label with < 4 members or a fit that is not finite keeps its H; counts (nullable): member count per label
+hipError_t launch_reestimate_dlt(const Points& p, const int* labels, int Nh, double* H, int* counts, hipStream_t s);
+
 hipError_t launch_haf_point(const Points& p, const Affines& a, const Epipolar& ep, double locality,
                             double* H_out /* n x 9, nullable */, double* feat_out /* n x 10, nullable */,
                             hipStream_t s);
@@ -368,6 +373,7 @@ constexpr int SEL_MODE_BY_WEIGHT = 1 << 15;            // ranked by MSAC weight:
 constexpr int SEL_MODE_HAF = 1 << 16;                  // the resident batch is mh_propose_haf's, and then:
 constexpr int SEL_MODE_HAF_MEMBERS_SHIFT = 17;         //   bits 17-22 its `members` (0 .. 32)
 constexpr int SEL_MODE_P3 = 1 << 23;                   // the resident batch is mh_propose_3pt's
+constexpr int SEL_MODE_REFIT_DLT = 1 << 24;            // winners are refitted by the N-point DLT estimator (mh_set_estimator); only beside SEL_MODE_REFIT
 static_assert(sizeof(SelRecord) == 88, "the exchanged record is 88 bytes");
 // scores_full (nullable): the first round's vector for the all-gather — the rank value of an eligible candidate, -1 otherwise
 hipError_t launch_sel_argmax(const int* counts, const int* weights, const int* orig, int Mc, int need, unsigned int my_off,
@@ -392,9 +398,10 @@ hipError_t launch_sel_claim(const Points& p, const SelRecord* records, int world
 // (one label); refit = 9 doubles + the refit's rank value on the support set; launch_sel_claim takes it in the winner's place when
 // it is finite and that value is at least the hypothesis'.  labels: n ints, sum / label_count: one int each (scratch).
 // scratch3 non-null: the point-only 3-point fit instead (launch_reestimate_3pt, reestimate_3pt_scratch_ints(n, 1) ints; a unused)
+// dlt: the N-point DLT fit instead (launch_reestimate_dlt; a, ep and scratch3 unused)
 hipError_t launch_sel_refit(const Points& p, const Affines& a, const Epipolar& ep, const SelRecord* records, int world, double thr2,
                             const unsigned char* mask, int* labels, double* refit, int* sum, int* label_count, hipStream_t s,
-                            bool by_weight, int symmetric, int* scratch3);
+                            bool by_weight, int symmetric, int* scratch3, bool dlt = false);
 hipError_t launch_sel_publish(int* rec, unsigned long long* keys, SelRecord* my_record, int* h_rec_dev, hipStream_t s);
 hipError_t launch_best_fused(int* scores, int world, int longest, int base, int rem, int* h_best_dev, int* clear,
                              int clear_count, hipStream_t s);

@@ -464,13 +464,14 @@ hipError_t launch_sel_claim(const Points& p, const SelRecord* records, int world
 // the round's winner refitted to its inliers: labels (n ints), refit (10 doubles), sum (1 int) are scratch of the caller
 hipError_t launch_sel_refit(const Points& p, const Affines& a, const Epipolar& ep, const SelRecord* records, int world, double thr2,
                             const unsigned char* mask, int* labels, double* refit, int* sum, int* label_count, hipStream_t s,
-                            bool by_weight, int symmetric, int* scratch3)
+                            bool by_weight, int symmetric, int* scratch3, bool dlt)
 {
     const dim3 grid((p.n + 255) / 256);
     hipLaunchKernelGGL(k_sel_winner_labels, grid, dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, records, world, thr2, mask, labels,
                        refit, symmetric);
-    hipError_t he = scratch3 ? launch_reestimate_3pt(p, labels, 1, ep, refit, label_count, scratch3, s)
-                             : launch_reestimate(p, a, labels, 1, ep, refit, label_count, s);
+    hipError_t he = dlt        ? launch_reestimate_dlt(p, labels, 1, refit, label_count, s)
+                    : scratch3 ? launch_reestimate_3pt(p, labels, 1, ep, refit, label_count, scratch3, s)
+                               : launch_reestimate(p, a, labels, 1, ep, refit, label_count, s);
     if (he != hipSuccess) return he;
     he = hipMemsetAsync(sum, 0, sizeof(int), s);
     if (he != hipSuccess) return he;

@@ -284,6 +284,21 @@ bool MultiH::Run(bool points_only)
         std::cerr << "Error: the stable point sets (INIT_STABLE_SETS) need affinities; the point-only Process() cannot use them\n";
         return false;
     }
+    if (estimator != ESTIMATOR_HAF && estimator != ESTIMATOR_3PT && estimator != ESTIMATOR_DLT) {
+        std::cerr << "Error: unknown estimator " << estimator << " (ESTIMATOR_HAF, ESTIMATOR_3PT or ESTIMATOR_DLT)\n";
+        return false;
+    }
+    if (epipolar_free) {      // what needs F cannot run without one
+        if (init_mode == INIT_STABLE_SETS) {
+            std::cerr << "Error: the stable point sets (INIT_STABLE_SETS) need the fundamental matrix; the epipolar-free route (SetEpipolarFree) cannot use them\n";
+            return false;
+        }
+        if (proposal_source == PROPOSAL_SOURCE_HAF || proposal_source == PROPOSAL_SOURCE_3PT) {
+            std::cerr << "Error: " << (proposal_source == PROPOSAL_SOURCE_HAF ? "HAF proposals (PROPOSAL_SOURCE_HAF)" : "3-point proposals (PROPOSAL_SOURCE_3PT)")
+                      << " need the fundamental matrix; the epipolar-free route (SetEpipolarFree) cannot use them\n";
+            return false;
+        }
+    }
     // where the initial batch comes from (looked at only where a batch is proposed)
     proposal_haf_run = false;
     proposal_3pt_run = false;
@@ -330,7 +345,8 @@ bool MultiH::Run(bool points_only)
     };
     if (!EnsureEngine()) return false;
     // the re-estimator of the loop and of the proposal refit (sticky on the engine, and engines are reused)
-    const int est = points_only ? MH_ESTIMATOR_3PT : estimator;
+    // (the epipolar-free route: the N-point DLT, which reads no F; the point-only route: the 3-point fit unless the DLT is asked for)
+    const int est = epipolar_free || estimator == ESTIMATOR_DLT ? MH_ESTIMATOR_DLT : points_only ? MH_ESTIMATOR_3PT : estimator;
     if (!mh_set_estimator || !mh_refine_points) {
         if (est != MH_ESTIMATOR_HAF) {
             std::cerr << "Error: the engine library has no point-only entry points (mh_set_estimator, mh_refine_points)\n";
@@ -422,7 +438,10 @@ bool MultiH::Run(bool points_only)
         return false;
     stage("correspondences on the device");
 
-    if (!have_epipolar) {
+    if (epipolar_free) {
+        // no F is estimated, no correspondence refined or dropped: the stage table keeps the input count four times
+        if (have_epipolar) printf("[Multi-H] Epipolar-free route: the epipolar geometry given by SetEpipolarGeometry is ignored.\n");
+    } else if (!have_epipolar) {
         // GetFundamentalMatrixAndRefineData (M/MultiH.cpp:770-848) on the GPU: RANSAC over normalised
         // 8-point hypotheses with Sampson scoring, LS refit, epipoles from F^T F / F F^T, then the
         // per-correspondence refinement of :807-838.
@@ -512,7 +531,7 @@ bool MultiH::Run(bool points_only)
         HandleDegenerateCase();
         return true;
     }
-    if (!Check(mh_set_epipolar(engine, fundamental_matrix, epipole_2), "mh_set_epipolar")) return false;
+    if (!epipolar_free && !Check(mh_set_epipolar(engine, fundamental_matrix, epipole_2), "mh_set_epipolar")) return false;
 
     // The proposal sampler: its three arguments are checked here, once; then the local sampler's table, once, on the
     // correspondences the proposer samples (the refined ones).
@@ -579,7 +598,9 @@ bool MultiH::Run(bool points_only)
     ClusterMergingAndLabeling();
     stage("neighbourhood + alternation");
 
-    if (cluster_homographies.size() > 1 && run_compatibility_check) {        // :78-86
+    if (cluster_homographies.size() > 1 && run_compatibility_check && epipolar_free) {
+        printf("[Multi-H] Epipolar-free route: the compatibility check is skipped (its trials are 3-point fits with F).\n");
+    } else if (cluster_homographies.size() > 1 && run_compatibility_check) {        // :78-86
         const int before = static_cast<int>(cluster_homographies.size());
         auto t0 = std::chrono::system_clock::now();
         post_filter_failed = false;
@@ -1004,12 +1025,14 @@ void MultiH::ClusterMergingAndLabeling()
 // candidates scoring and the collinearity filter on the GPU (mh_inlier_moments; :430-463).  kept: the surviving
 // candidates, 9 doubles each.  Returns an MH_* status.  The correspondences must be resident in the engine; its model
 // set is replaced by the candidates.
+// F == nullptr: the epipolar-free route, whose candidate of a mode is its medoid (merge_step.cpp MergeCandidatesMedoid).
 static int MergingStepOnEngine(mh_engine* engine, const double* H, int nh, const double F[9], double thr_h, double straightness,
                                uint64_t seed, std::vector<double>& kept, uint64_t* draws)
 {
     kept.clear();
     std::vector<double> cand;
-    const int nc = multih::MergeCandidates(H, nh, F, thr_h, seed, nullptr, nullptr, cand, nullptr, draws);
+    const int nc = F ? multih::MergeCandidates(H, nh, F, thr_h, seed, nullptr, nullptr, cand, nullptr, draws)
+                     : multih::MergeCandidatesMedoid(H, nh, thr_h, seed, nullptr, nullptr, cand, nullptr, draws);
     if (nc == 0) return MH_OK;
     int rc = mh_set_models(engine, cand.data(), nc);
     if (rc != MH_OK) return rc;
@@ -1051,7 +1074,7 @@ bool MultiH::MergingStep(bool& changed)
         for (int k = 0; k < 9; ++k) H[9 * (size_t)i + k] = p[k];
     }
     std::vector<double> kept9;
-    const int rc = MergingStepOnEngine(engine, H.data(), nh, fundamental_matrix, threshold_homography, straightness_threshold,
+    const int rc = MergingStepOnEngine(engine, H.data(), nh, epipolar_free ? nullptr : fundamental_matrix, threshold_homography, straightness_threshold,
                                        proposal_seed ^ 0x4d53u ^ (merge_rng_counter << 20), kept9, nullptr);
     ++merge_rng_counter;
     if (!Check(rc, "MergingStep (mh_set_models / mh_inlier_moments)")) return false;
@@ -1250,6 +1273,12 @@ extern "C" __attribute__((visibility("default")))
 void mhh_set_tail_polish(int iterations) { g_tail_polish = iterations; }
 extern "C" __attribute__((visibility("default")))
 void mhh_set_model_polish(int iterations) { g_model_polish = iterations; }
+// MultiH::SetEstimator (-1: leave as is, the class default) and MultiH::SetEpipolarFree for the next mhh_run_process calls
+static int g_estimator = -1, g_epipolar_free = 0;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_estimator(int estimator) { g_estimator = estimator; }
+extern "C" __attribute__((visibility("default")))
+void mhh_set_epipolar_free(int on) { g_epipolar_free = on; }
 // MultiH::SetSelectionScore for the next mhh_run_process calls (< 0: the class default)
 static int g_selection_score = -1;
 extern "C" __attribute__((visibility("default")))
@@ -1337,6 +1366,8 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     if (g_tail_polish >= 0) mh.SetTailPolish(g_tail_polish);
     if (g_model_polish >= 0) mh.SetModelPolish(g_model_polish);
     if (g_selection_score >= 0) mh.SetSelectionScore(g_selection_score);
+    if (g_estimator >= 0) mh.SetEstimator(g_estimator);
+    mh.SetEpipolarFree(g_epipolar_free != 0);
     if (g_fund_estimator >= 0) mh.SetFundamentalEstimator(g_fund_estimator, g_fund_max_samples, g_fund_confidence);
     for (const auto& kv : g_tuning) mh.SetEngineTuning(kv.first, kv.second);
     if (g_radius > 0.0 && g_max_hits > 0) { mh.SetNeighbourRadius(g_radius, g_max_hits); if (g_knn > 0) mh.SetFallbackK(g_knn); }

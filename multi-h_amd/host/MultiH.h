@@ -129,8 +129,18 @@ public:
     void SetProposalRefit(bool on) { proposal_refit = on; }
     // The re-estimator of Process() with affinities (the point-only Process() always takes ESTIMATOR_3PT): the HAF
     // non-minimal fit (M/MultiH.cpp:913-989, the reference's; default) or the 3-point least squares from the points alone.
-    enum { ESTIMATOR_HAF = 0, ESTIMATOR_3PT = 1 };
+    // ESTIMATOR_DLT: the normalised N-point DLT over each label's members (MH_ESTIMATOR_DLT), which reads neither F nor the
+    // affinities; the point-only Process() honours it (the two other values give ESTIMATOR_3PT there).
+    enum { ESTIMATOR_HAF = 0, ESTIMATOR_3PT = 1, ESTIMATOR_DLT = 2 };
     void SetEstimator(int e) { estimator = e; }
+    // The route without epipolar geometry (default off), for pairs no single F describes: independently moving planes, a
+    // rotating camera in front of moving planes, a plane-dominated pair whose F is unstable.  With it on, both Process()
+    // forms estimate no F and refine or drop no correspondence (GetFrontStages() reports the input count four times; a
+    // caller's SetEpipolarGeometry is ignored with one log line), run the engine under ESTIMATOR_DLT without mh_set_epipolar
+    // (affinities are uploaded if given and never read), take the medoid of each mean-shift mode as MergingStep's candidate
+    // (multih::MergeCandidatesMedoid) and skip HomographyCompatibilityCheck, whose trials are 3-point fits with F (one log
+    // line).  INIT_STABLE_SETS, PROPOSAL_SOURCE_HAF and PROPOSAL_SOURCE_3PT need F: Process() refuses them with a message.
+    void SetEpipolarFree(bool on) { epipolar_free = on; }
     // The data term of the labeling (mh_set_data_term, include/multih_hip.h): DATA_TERM_REFERENCE is dataEnergy
     // (M/MultiH.cpp:473-504), whose cost inside the truncation threshold FALLS as the fit gets worse (default);
     // DATA_TERM_RISING drops its `1.0 -`, so the cost rises with the error.  Process() applies it to its engine on every
@@ -287,6 +297,7 @@ protected:
     int proposal_max_models = 32;
     bool proposal_refit = true;
     int estimator = ESTIMATOR_HAF;
+    bool epipolar_free = false;
     int data_term = DATA_TERM_REFERENCE;
     int tail_score = TAIL_SCORE_COUNT;
     int tail_refit = 0;

@@ -21,8 +21,10 @@
 //                                Process()'s RANSAC mask, after OptimalTriangulation, after distanceError <= 1 (M/MultiH.cpp:807-838)
 //                  [--points]   point-only correspondences: 4 numbers per input row (x1 y1 x2 y2, no affinity) and 5 per output
 //                                row (x1 y1 x2 y2 label); runs MultiH::Process(src, dst), the point-only route (3-point refits)
-//                  [--estimator haf|3pt]   the re-estimator of the route with affinities (MultiH::SetEstimator; haf, the default,
-//                                is the reference's); --points always takes 3pt
+//                  [--estimator haf|3pt|dlt]   the re-estimator of the route with affinities (MultiH::SetEstimator; haf, the default,
+//                                is the reference's); --points takes 3pt unless dlt (the N-point DLT, which reads no F) is asked for
+//                  [--no-epipolar]   the route without epipolar geometry (MultiH::SetEpipolarFree): no F is estimated, no row is
+//                                filtered (the load filter included), DLT refits, medoid merge candidates, no compatibility check
 //                  [--data-term reference|rising]   the data term of the labeling (MultiH::SetDataTerm): reference, the default, is
 //                                the reference's dataEnergy (the cost falls as the fit gets worse); rising drops its `1.0 -`
 //                  [--tail-score count|msac]   how the degenerate tail ranks its DLT hypotheses (MultiH::SetTailScore): count, the
@@ -124,7 +126,7 @@ int main(int argc, char** argv)
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
                      "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] [--f-estimator ls8|minimal] "
-                     "[--stages file] [--points] [--estimator haf|3pt] [--data-term reference|rising] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
+                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--data-term reference|rising] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
         return 2;
     }
     double thrF = 2.6, thrH = 2.2, locality = 0.005, lambda = 0.5;     // M/main.cpp:55-59
@@ -135,7 +137,7 @@ int main(int argc, char** argv)
     int f_metric = MultiH::FUND_EPIPOLAR_MAX;
     MultiH::FundEstimator f_estimator;
     std::string epi, neighbourhood = "knn", stages_path;
-    bool points_only = false;
+    bool points_only = false, no_epipolar = false;
     int estimator = MultiH::ESTIMATOR_HAF;
     int data_term = MultiH::DATA_TERM_REFERENCE;
     int tail_score = MultiH::TAIL_SCORE_COUNT;
@@ -145,14 +147,16 @@ int main(int argc, char** argv)
     int proposals = MultiH::PROPOSAL_SOURCE_DLT, haf_members = 16, haf_stride = 1;
     for (int i = 3; i < argc; ++i) {
         const std::string k = argv[i];
-        if (k == "--points") { points_only = true; continue; }      // the one option without a value
+        if (k == "--points") { points_only = true; continue; }      // the two options without a value
+        if (k == "--no-epipolar") { no_epipolar = true; continue; }
         if (i + 1 >= argc) break;
         const char* v = argv[++i];
         if (k == "--epipolar") epi = v;
         else if (k == "--estimator") {
             if (std::string(v) == "haf") estimator = MultiH::ESTIMATOR_HAF;
             else if (std::string(v) == "3pt") estimator = MultiH::ESTIMATOR_3PT;
-            else { std::cerr << "--estimator: haf or 3pt\n"; return 2; }
+            else if (std::string(v) == "dlt") estimator = MultiH::ESTIMATOR_DLT;
+            else { std::cerr << "--estimator: haf, 3pt or dlt\n"; return 2; }
         }
         else if (k == "--data-term") {
             if (std::string(v) == "reference") data_term = MultiH::DATA_TERM_REFERENCE;
@@ -350,7 +354,7 @@ int main(int argc, char** argv)
     std::vector<cv::Point2d> srcPointsOrig, dstPointsOrig;
     std::vector<cv::Mat> origAffines;
     int rows_loaded = 0;
-    if (!LoadPointsFromFile(srcPointsOrig, dstPointsOrig, origAffines, argv[1], epi.empty() ? load_filter : 0.0, seed, f_metric,
+    if (!LoadPointsFromFile(srcPointsOrig, dstPointsOrig, origAffines, argv[1], epi.empty() && !no_epipolar ? load_filter : 0.0, seed, f_metric,
                             comm ? rank : 0, &rows_loaded, points_only, f_estimator)) {
         std::cerr << "cannot read " << argv[1] << " (or the load filter failed)\n";
         return finish(1);
@@ -379,6 +383,7 @@ int main(int argc, char** argv)
     if (neighbourhood == "radius") multiH->SetNeighbourRadius(1.0 / locality);        // the complete list of M/MultiH.cpp:252-253 (see MultiH.h)
     else if (neighbourhood == "approx") multiH->SetNeighbourApprox(4, 32, 0x464c414e4eull + seed);   // ... as FLANN's default search answers it
     multiH->SetEstimator(estimator);
+    multiH->SetEpipolarFree(no_epipolar);
     multiH->SetDataTerm(data_term);
     multiH->SetTailScore(tail_score);
     multiH->SetTailRefit(tail_refit);
@@ -396,12 +401,12 @@ int main(int argc, char** argv)
         const MultiH::FrontStages st = multiH->GetFrontStages();
         printf("[Multi-H] stages: %d loaded, %d after the load filter (%.2f px), %d in Process()'s RANSAC mask (%.2f px), "
                "%d after OptimalTriangulation, %d after distanceError <= 1\n",
-               rows_loaded, rows_after_load_filter, epi.empty() ? load_filter : 0.0, st.in_ransac_mask, thrF, st.triangulated,
+               rows_loaded, rows_after_load_filter, epi.empty() && !no_epipolar ? load_filter : 0.0, st.in_ransac_mask, thrF, st.triangulated,
                st.affine_consistent);
         if (!stages_path.empty() && rank == 0) {
             std::ofstream sf(stages_path);
             sf << "{\"loaded\": " << rows_loaded << ", \"after_load_filter\": " << rows_after_load_filter
-               << ", \"load_filter_px\": " << (epi.empty() ? load_filter : 0.0) << ", \"in_ransac_mask\": " << st.in_ransac_mask
+               << ", \"load_filter_px\": " << (epi.empty() && !no_epipolar ? load_filter : 0.0) << ", \"in_ransac_mask\": " << st.in_ransac_mask
                << ", \"ransac_px\": " << thrF << ", \"after_optimal_triangulation\": " << st.triangulated
                << ", \"after_distance_error\": " << st.affine_consistent << ", \"f_metric\": \""
                << (f_metric == MultiH::FUND_SAMPSON ? "sampson" : "opencv") << "\", \"f_estimator\": \""

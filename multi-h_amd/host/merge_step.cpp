@@ -801,10 +801,59 @@ int MergeCandidates(const double* H, int nh, const double F[9], double thr_h, ui
     return static_cast<int>(cand.size() / 9);
 }
 
+int MergeCandidatesMedoid(const double* H, int nh, double thr_h, uint64_t seed, std::vector<double>* feat_out,
+                          std::vector<double>* modes_out, std::vector<double>& cand, std::vector<int>* cand_mode, uint64_t* draws)
+{
+    std::vector<double> feat(6 * (size_t)nh);
+    HomographyFeatures(H, nh, feat.data());
+    MeanShiftResult ms;
+    MeanShiftCluster(feat.data(), nh, 6, thr_h, seed, ms, draws);
+    const int k = static_cast<int>(ms.members.size());
+    cand.clear();
+    if (cand_mode) cand_mode->clear();
+    for (int c = 0; c < k; ++c) {
+        // the member nearest the mode in L1 (k = 0..5 summed from 0.0), the lowest index on ties; a distance that is not
+        // a number never wins against one that is
+        int best = -1;
+        double best_d = 0.0;
+        std::vector<int> mem(ms.members[c].begin(), ms.members[c].end());
+        std::sort(mem.begin(), mem.end());              // ascending, whatever the order of the member list
+        for (const int j : mem) {
+            double d = 0.0;
+            for (int q = 0; q < 6; ++q) d = d + std::fabs(feat[6 * (size_t)j + q] - ms.modes[6 * (size_t)c + q]);
+            if (best < 0 || d < best_d || (best_d != best_d && d == d)) { best = j; best_d = d; }
+        }
+        if (best < 0) continue;                         // a mode without members gives no candidate
+        cand.insert(cand.end(), H + 9 * (size_t)best, H + 9 * (size_t)best + 9);
+        if (cand_mode) cand_mode->push_back(c);
+    }
+    if (feat_out) *feat_out = std::move(feat);
+    if (modes_out) *modes_out = std::move(ms.modes);
+    return static_cast<int>(cand.size() / 9);
+}
+
 } // namespace multih
 
 // ---- C hooks for the CPU-side tests (no GPU needed) ----------------------------
 extern "C" {
+
+// MergeCandidatesMedoid for tests: mhh_merge_candidates' arguments without F
+__attribute__((visibility("default")))
+int mhh_merge_candidates_medoid(const double* H, int nh, double thr_h, unsigned long long seed, double* feat,
+                                double* modes, int* n_modes, double* cand, int* cand_mode, unsigned long long* draws)
+{
+    std::vector<double> f, m, c;
+    std::vector<int> cm;
+    uint64_t d = 0;
+    const int nc = multih::MergeCandidatesMedoid(H, nh, thr_h, seed, &f, &m, c, &cm, &d);
+    std::copy(f.begin(), f.end(), feat);
+    std::copy(m.begin(), m.end(), modes);
+    *n_modes = (int)(m.size() / 6);
+    std::copy(c.begin(), c.end(), cand);
+    std::copy(cm.begin(), cm.end(), cand_mode);
+    if (draws) *draws = d;
+    return nc;
+}
 
 // MergeCandidates for tests: feat nh x 6, modes up to nh x 6 (*n_modes of them), cand up to nh x 9, cand_mode up to nh.
 __attribute__((visibility("default")))

@@ -54,6 +54,14 @@ int MergeCandidates(const double* H /* nh x 9 */, int nh, const double F[9], dou
                     std::vector<double>* feat, std::vector<double>* modes, std::vector<double>& cand,
                     std::vector<int>* cand_mode = nullptr, uint64_t* draws = nullptr);
 
+// MergeCandidates for the route without epipolar geometry (MultiH::SetEpipolarFree): the same features, the same mean shift and
+// the same draws, but the candidate of a mode cannot be a 3-point fit with F.  The candidate of mode c is the MEDOID: the member j
+// of ms.members[c] with the smallest sum over k = 0..5 (from 0.0) of |feat[j][k] - mode[c][k]|, the lowest j on ties (a sum that is
+// not a number loses to one that is); the candidate is H[j]'s nine doubles unchanged.  A mode without members gives no candidate.
+int MergeCandidatesMedoid(const double* H /* nh x 9 */, int nh, double thr_h, uint64_t seed, std::vector<double>* feat,
+                          std::vector<double>* modes, std::vector<double>& cand, std::vector<int>* cand_mode = nullptr,
+                          uint64_t* draws = nullptr);
+
 // HomographyCompatibilityCheck (M/MultiH.cpp:100-222): per cluster 501 trials of {3 random cluster
 // points -> GetHomography3PT without refinement -> median squared transfer error of the remaining
 // points}; a cluster whose median-of-medians exceeds thr^2*81/16, or that has fewer than
