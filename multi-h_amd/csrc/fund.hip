@@ -19,7 +19,7 @@
 // M/MultiH.cpp:775: threshold_fundamental_matrix).
 
 #include "mh_kernels.hpp"
-#include "mh_device.hpp"
+#include "wg_fit.hpp"
 
 namespace mh {
 
@@ -245,27 +245,14 @@ hipError_t launch_fund_mask(const Points& p, const double* F_in, double thr2, un
 
 // ---------------------------------------------------------------------------
 // Refit: normalised least-squares 8-point on the inliers of F_in.  One workgroup, three strided
-// passes over the points, every FP64 sum in the engine's deterministic order (thread t of 256 adds
-// its points t, t+256, ... then a binary tree), so the oracle reproduces it bit for bit:
+// passes over the points, every FP64 sum in the engine's deterministic order (wg_fit.hpp), so the
+// oracle reproduces it bit for bit:
 //   pass 1  inlier mask, count, centroid sums of both images
 //   pass 2  mean distance to the centroid in both images  -> scales s = sqrt(2)/mean
 //   pass 3  the 45 unique entries of A^T A of the normalised design rows
 // thread 0: 9x9 cyclic Jacobi, eigenvector of the smallest eigenvalue, rank-2 projection,
 // de-normalisation, unit Frobenius norm, F[8] >= 0.
 // ---------------------------------------------------------------------------
-template <int K>
-__device__ __forceinline__ void tree_reduce(double (*sv)[K], int t)
-{
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (t < s) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) sv[t][k] = sv[t][k] + sv[t + s][k];
-        }
-        __syncthreads();
-    }
-}
-
 template <int METRIC>
 __global__ void __launch_bounds__(256)
 k_fund_refit(const double* __restrict__ x1, const double* __restrict__ y1,
@@ -292,19 +279,11 @@ k_fund_refit(const double* __restrict__ x1, const double* __restrict__ y1,
         }
         sv[t][0] = a0; sv[t][1] = a1; sv[t][2] = a2; sv[t][3] = a3;
         sc[t] = cnt;
-        __syncthreads();
-        for (int s = 128; s >= 1; s >>= 1) {
-            if (t < s) {
-                for (int k = 0; k < 4; ++k) sv[t][k] = sv[t][k] + sv[t + s][k];
-                sc[t] += sc[t + s];
-            }
-            __syncthreads();
-        }
+        wg_tree<4>(sv, sc, t);
         if (t == 0) {
             const int c = sc[0];
             if (count_out) *count_out = c;
-            const double inv = 1.0 / (double)c;
-            s_par[0] = sv[0][0] * inv; s_par[1] = sv[0][1] * inv; s_par[2] = sv[0][2] * inv; s_par[3] = sv[0][3] * inv;
+            hartley_put_centroids(sv[0], c, s_par);
         }
         __syncthreads();
     }
@@ -313,32 +292,21 @@ k_fund_refit(const double* __restrict__ x1, const double* __restrict__ y1,
         if (t < 9) F_out[t] = f[t];
         return;
     }
-    const double cx1 = s_par[0], cy1 = s_par[1], cx2 = s_par[2], cy2 = s_par[3];
+    Hartley hn;
+    hartley_get_centroids(s_par, hn);
     __syncthreads();
     // pass 2
     {
         double d1 = 0.0, d2 = 0.0;
         for (int n = t; n < N; n += 256) {
             const double x = x1[n], y = y1[n], u = x2[n], v = y2[n];
-            if (epipolar_d<METRIC>(f, x, y, u, v) < thr2) {
-                const double ax = x - cx1, ay = y - cy1, bx = u - cx2, by = v - cy2;
-                d1 = d1 + sqrt(ax * ax + ay * ay);
-                d2 = d2 + sqrt(bx * bx + by * by);
-            }
+            if (epipolar_d<METRIC>(f, x, y, u, v) < thr2) hartley_distances(hn, x, y, u, v, d1, d2);
         }
         sv[t][0] = d1; sv[t][1] = d2;
-        __syncthreads();
-        for (int s = 128; s >= 1; s >>= 1) {
-            if (t < s) { sv[t][0] = sv[t][0] + sv[t + s][0]; sv[t][1] = sv[t][1] + sv[t + s][1]; }
-            __syncthreads();
-        }
-        if (t == 0) {
-            s_par[4] = sqrt(2.0) / (sv[0][0] / (double)count);
-            s_par[5] = sqrt(2.0) / (sv[0][1] / (double)count);
-        }
-        __syncthreads();
+        wg_tree<2>(sv, t);
     }
-    const double s1 = s_par[4], s2 = s_par[5];
+    hartley_scales(sv[0], count, s_par, t, hn);
+    const double cx1 = hn.cx1, cy1 = hn.cy1, cx2 = hn.cx2, cy2 = hn.cy2, s1 = hn.s1, s2 = hn.s2;
     __syncthreads();
     // pass 3
     {
@@ -359,7 +327,7 @@ k_fund_refit(const double* __restrict__ x1, const double* __restrict__ y1,
         }
 #pragma unroll
         for (int k = 0; k < 45; ++k) sv[t][k] = acc[k];
-        tree_reduce<45>(sv, t);
+        wg_tree<45>(sv, t);
     }
     if (t != 0) return;
     double A[81], V[81], D[9];

@@ -11,8 +11,7 @@
 //                          candidate pass (xd): Sd alone
 //                          thread 0: R, lambda (LMSolverImpl::run's two branches), accept iff Sd < S
 //                          accepted: Jacobian pass (xd)
-// so a call of r iterations is at most 2 r + 1 passes.  Every FP64 sum in the engine's order (thread t adds its members t,
-// t + 256, ... in ascending index from 0.0, then the binary tree 128 .. 1), -ffp-contract=off.  The loop is bounded by
+// so a call of r iterations is at most 2 r + 1 passes.  Every FP64 sum in the engine's order (wg_fit.hpp).  The loop is bounded by
 // max_iterations (at most POLISH_H_MAX_ITERATIONS), Jacobi by its 30 sweeps; nothing waits for anything but the workgroup's own
 // barriers, and every exit is taken by the whole workgroup.
 //
@@ -20,7 +19,7 @@
 // between two passes; A, v, D, x, xd and d are small LDS arrays: no private array with a run-time index, no scratch.
 
 #include "mh_kernels.hpp"
-#include "mh_device.hpp"
+#include "wg_fit.hpp"
 
 namespace mh {
 
@@ -29,21 +28,6 @@ namespace {
 constexpr int PH_SUMS = 30;                      // S | J^T r (8) | a a (6) | a bx (6) | a by (6) | the 2 x 2 block (3)
 constexpr double PH_DEPS = 2.220446049250313e-16;
 constexpr double PH_FEPS = 1.1920928955078125e-07;
-
-__device__ __forceinline__ bool polish_h_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }     // false for NaN
-
-template <int K>
-__device__ __forceinline__ void polish_h_tree(double (*sv)[PH_SUMS], int t)
-{
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (t < s) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) sv[t][k] = sv[t][k] + sv[t + s][k];
-        }
-        __syncthreads();
-    }
-}
 
 // compute(x) of one member: the inverse denominator, the transferred point and the residual
 struct PolishPoint { double ww, xi, yi, rx, ry; };
@@ -130,7 +114,7 @@ __device__ __forceinline__ int polish_h_jacobian_pass(const double* __restrict__
         if (ax > mr) mr = ax;
         if (ay > mr) mr = ay;
     }
-    // max |r| and the count first, in two columns of the buffer (a count is exact as a double), then the 30 sums
+    // max |r| and the count first, in two columns of the buffer (a count is exact as a double; a max, so not wg_tree), then the 30 sums
     sv[t][0] = mr;
     sv[t][1] = (double)cnt;
     __syncthreads();
@@ -146,7 +130,7 @@ __device__ __forceinline__ int polish_h_jacobian_pass(const double* __restrict__
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < PH_SUMS; ++q) sv[t][q] = acc[q];
-    polish_h_tree<PH_SUMS>(sv, t);
+    wg_tree<PH_SUMS>(sv, t);
     if (t < PH_SUMS) G[t] = sv[0][t];
     __syncthreads();
     return members;
@@ -197,7 +181,7 @@ k_polish_h(const double* __restrict__ x1, const double* __restrict__ y1,
     __syncthreads();
     bool finite = true;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) finite = finite && polish_h_finite(s_x[j]);
+    for (int j = 0; j < 8; ++j) finite = finite && finite_dev(s_x[j]);
 
     const int members = polish_h_jacobian_pass(x1, y1, x2, y2, N, labels, k, s_x, sv, s_G, &s_maxr, t);
     const int status = members < 4 ? 1 : (!finite ? 2 : 0);
@@ -235,7 +219,7 @@ k_polish_h(const double* __restrict__ x1, const double* __restrict__ y1,
                     a0 = a0 + (p.rx * p.rx + p.ry * p.ry);
                 }
                 sv[t][0] = a0;
-                polish_h_tree<1>(sv, t);
+                wg_tree<1>(sv, t);
                 if (t == 0) s_Sd = sv[0][0];
                 __syncthreads();                 // the reduction buffer is idle again
             }
@@ -282,7 +266,7 @@ k_polish_h(const double* __restrict__ x1, const double* __restrict__ y1,
                 for (int i = 0; i < 8; ++i) {
                     const double a = fabs(s_d[i]);
                     if (a > maxd) maxd = a;
-                    dfin = dfin && polish_h_finite(s_d[i]);
+                    dfin = dfin && finite_dev(s_d[i]);
                 }
                 s_accept = accept ? 1 : 0;
                 s_stop = (iter >= max_iterations || maxd < PH_FEPS || !dfin) ? 1 : 0;

@@ -9,16 +9,15 @@
 // (a11 a12 a21 a22), the correspondence, F and the epipole e2 (:938-966); the
 // reference forms the 6n x 4 matrix and multiplies A^T A with OpenCV gemm.
 // Here one workgroup per label accumulates the 10 unique A^T A entries
-// directly: thread t of 256 adds its sites t, t+256, ... in increasing order,
-// then a binary tree v[t] += v[t+s], s = 128..1 (the engine's deterministic
-// FP64 summation order, identical to oracle/mh_oracle.cpp TreeAcc).  Thread 0
+// directly, in the engine's deterministic FP64 summation order (wg_fit.hpp;
+// identical to oracle/mh_oracle.cpp TreeAcc).  Thread 0
 // solves the 4x4 symmetric eigen-problem (cyclic Jacobi, stands for cv::eigen
 // :973), takes the eigenvector of the smallest eigenvalue (:975-982), builds
 // rows 1-2 of H (:984-989) and rescales.  A label with no points keeps its H
 // (:592-593).  Nh is small (10..100): the kernel is latency-bound by design.
 
 #include "mh_kernels.hpp"
-#include "mh_device.hpp"
+#include "wg_fit.hpp"
 
 namespace mh {
 
@@ -39,11 +38,10 @@ k_haf_reestimate(const double* __restrict__ x1, const double* __restrict__ y1,
 #pragma unroll
     for (int k = 0; k < 10; ++k) acc[k] = 0.0;
     int cnt = 0;
-    // A lane's members are added up in index order (the oracle's order).  The loop is latency bound, and most points
-    // carry another label: the labels of 32 of the lane's points are fetched together (one trip to memory), the
-    // correspondences and affinities only of those that match, four at a time (r05; before: all eight doubles of EVERY
-    // point, four points per trip — 85 of the launch's 110 us at 50 000 points, whatever the label's size).  The additions
-    // keep their order.
+    // A lane's members are added up in index order (the oracle's order).  The rule is wg_fit.hpp's for_label_members; this
+    // loop is written out because the prefetch of the matching points' eight doubles, four points at a time, is woven into
+    // the visit (r05; before: all eight doubles of EVERY point, four points per trip — 85 of the launch's 110 us at 50 000
+    // points, whatever the label's size).  The additions keep their order.
     auto add_point = [&](const double (&in)[8]) {
         const double a11 = in[0], a12 = in[1], a21 = in[2], a22 = in[3];
         const double px = in[4], py = in[5], qx = in[6], qy = in[7];
@@ -106,15 +104,7 @@ k_haf_reestimate(const double* __restrict__ x1, const double* __restrict__ y1,
 #pragma unroll
     for (int k = 0; k < 10; ++k) sv[t][k] = acc[k];
     sc[t] = cnt;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (t < s) {
-#pragma unroll
-            for (int k = 0; k < 10; ++k) sv[t][k] = sv[t][k] + sv[t + s][k];
-            sc[t] += sc[t + s];
-        }
-        __syncthreads();
-    }
+    wg_tree<10>(sv, sc, t);
     if (t != 0) return;
     if (counts) counts[l] = sc[0];
     if (sc[0] == 0) return;

@@ -13,11 +13,11 @@
 //   k_3pt_scan         one workgroup: exclusive prefix sum of cnt in place (label-major, blocks ascending), total behind it
 //   k_3pt_scatter      members[cnt[label * blocks + block] + rank] = point
 // so label l's members lie in members[cnt[l * blocks] .. cnt[(l + 1) * blocks]) in ascending point index.  Many labels: the
-// single scan of labels x blocks counts costs more than it saves, and each workgroup finds its members by the match loop of
-// k_haf_reestimate instead (32 labels per trip, three passes).
+// single scan of labels x blocks counts costs more than it saves, and each workgroup finds its members by the match loop
+// instead (wg_fit.hpp's for_label_members: 32 labels per trip, three passes).
 //
-// Then k_3pt_reestimate, one workgroup of 256 per label, three sums in the engine's deterministic FP64 order (thread t adds
-// the label's members t, t + 256, ... in ascending order, then the LDS binary tree v[t] += v[t + s], s = 128..1):
+// Then k_3pt_reestimate, one workgroup of 256 per label, three sums in the engine's deterministic FP64 order (wg_fit.hpp: thread t adds
+// the label's members t, t + 256, ... in ascending order, then the LDS binary tree):
 //   1. the centroids of both images (with the member count, for the match loop) (NormalizePoints, Homography_Refine3PTCallback.h:161-196),
 //   2. the mean distances to them -> ratio = sqrt(2) / mean,
 //   3. the normal equations of the 2n x 3 system (:1019-1037): A^T A (6 unique entries) and A^T b (3), two rows per point.
@@ -29,7 +29,7 @@
 // The host's sums run from 0.0 in index order, so the two agree to rounding, not bit for bit; so do the two forms.
 
 #include "mh_kernels.hpp"
-#include "mh_device.hpp"
+#include "wg_fit.hpp"
 
 #include <algorithm>
 
@@ -54,7 +54,8 @@ __device__ __forceinline__ void block_rank(const int* sl, int t, int l, int& ran
     last = lst;
 }
 
-// v[k][t] summed over t by the fixed binary tree; every thread returns with the sums in v[k][0]
+// v[k][t] summed over t by the fixed binary tree; every thread returns with the sums in v[k][0].  The transposed twin of
+// wg_fit.hpp's wg_tree: this kernel keeps its sums as [K][256].
 template <int K>
 __device__ __forceinline__ void tree_sum(double (*v)[R3_BLOCK], int t)
 {
@@ -127,31 +128,15 @@ k_3pt_scatter(const int* __restrict__ labels, int N, int Nh, const int* __restri
 }
 
 // The members of label l in ascending point index, lane t taking every 256th: from the compacted list (COMPACT), or by
-// the match loop of k_haf_reestimate — the labels of 32 of the lane's points fetched per trip, the matching ones visited in
-// order (lane t then takes the members among the points t, t + 256, ...).  The two forms order the sums differently.
+// the match loop (for_label_members: lane t then takes the members among the points t, t + 256, ...).  The two forms order
+// the sums differently.
 template <bool COMPACT, class Fn>
 __device__ __forceinline__ void for_members(const int* mem, int n, const int* labels, int N, int l, int t, Fn&& f)
 {
-    if (COMPACT) {
+    if constexpr (COMPACT) {
         for (int k = t; k < n; k += R3_BLOCK) f(mem[k]);
-        return;
-    }
-    constexpr int BATCH = 32;
-    for (int n0 = t; n0 < N; n0 += R3_BLOCK * BATCH) {
-        int lb[BATCH];
-#pragma unroll
-        for (int j = 0; j < BATCH; ++j) {
-            const int i = n0 + R3_BLOCK * j;
-            lb[j] = labels[i < N ? i : 0];
-        }
-        unsigned match = 0;
-#pragma unroll
-        for (int j = 0; j < BATCH; ++j) match |= (n0 + R3_BLOCK * j < N && lb[j] == l) ? 1u << j : 0u;
-        while (match) {
-            const int j = __builtin_ctz(match);
-            match &= match - 1u;
-            f(n0 + R3_BLOCK * j);
-        }
+    } else {
+        for_label_members<32, int>(labels, N, l, t, f);
     }
 }
 

@@ -28,7 +28,7 @@
 #include <type_traits>
 
 #include "mh_kernels.hpp"
-#include "mh_device.hpp"
+#include "wg_fit.hpp"
 
 namespace mh {
 
@@ -520,9 +520,8 @@ hipError_t launch_inliers_of_model(const Points& p, const double* H, int idx, do
 
 // ---------------------------------------------------------------------------
 // Collinearity moments (M/MultiH.cpp:446-463).  One workgroup per model.  The
-// FP64 sums use the engine's deterministic order: lane t of 256 adds its points
-// t, t+256, ... in increasing order, then a binary tree v[t] += v[t+s],
-// s = 128..1.  Thread 0 finishes with a cyclic-Jacobi 3x3 eigen solve.
+// FP64 sums use the engine's deterministic order (wg_fit.hpp).  Thread 0
+// finishes with a cyclic-Jacobi 3x3 eigen solve.
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 k_moments(const double* __restrict__ x1, const double* __restrict__ y1,
@@ -567,15 +566,7 @@ k_moments(const double* __restrict__ x1, const double* __restrict__ y1,
 #pragma unroll
     for (int k = 0; k < 5; ++k) sv[t][k] = acc[k];
     sc[t] = cnt;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (t < s) {
-#pragma unroll
-            for (int k = 0; k < 5; ++k) sv[t][k] = sv[t][k] + sv[t + s][k];
-            sc[t] += sc[t + s];
-        }
-        __syncthreads();
-    }
+    wg_tree<5>(sv, sc, t);
     if (t == 0) {
         double* mo = moments + 6 * (size_t)m;
         const double c = (double)sc[0];

@@ -131,6 +131,23 @@ def test_the_expansion_has_one_context_record_one_status_and_a_host_only_planner
     assert not re.search(r"\bhip[A-Z]\w*|__global__|__device__", plan)
 
 
+def test_the_per_model_fits_state_their_shared_parts_once():
+    """csrc/wg_fit.hpp holds the finite test, the workgroup's summation tree and the N-point fit of the per-model fit kernels;
+    no kernel source restates them.  The tree's loop head is left in polish_h.hip (its max-and-count tree, not a sum), in
+    meanshift.hip (another scheme) and once in reestimate_dlt.hip (pass 1's counted tree: as a call it changes the
+    instructions of k_dlt_reestimate's label fetch, and the house rule backs such a sharing out); the 9 x 9 Jacobi call in
+    fund.hip (k_fund_refit's 45-sum design is its own)."""
+    csrc = os.path.join(ROOT, "multi-h_amd", "csrc")
+    hips = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert len(hips) >= 20
+    text = {f: open(os.path.join(csrc, f)).read() for f in hips}
+    assert [f for f in hips if "1.7976931348623157e308" in text[f]] == []
+    assert [f for f in hips if "s = 128; s >= 1" in text[f]] == ["meanshift.hip", "polish_h.hip", "reestimate_dlt.hip"]
+    assert text["polish_h.hip"].count("s = 128; s >= 1") == 1 and "if (sv[t + s][0] > sv[t][0])" in text["polish_h.hip"]
+    assert text["reestimate_dlt.hip"].count("s = 128; s >= 1") == 1 and "sc[t] += sc[t + s];" in text["reestimate_dlt.hip"]
+    assert [f for f in hips if "jacobi_sym_dev(9," in text[f]] == ["fund.hip"]
+
+
 def test_product_library_kernels_are_the_product_instantiations_only(mh, engine_lib):
     """the kernel templates carry measurement switches (the residual sweep's configuration: CALIB =
     store-only calibration, CONTRACT = fused multiply-adds — not bit-exact —, TILED = tile-major R, SF = asm store flavours,

@@ -159,6 +159,38 @@ def test_failed_fits_keep_their_models_and_leave_the_others_alone(engine):
         assert np.array_equal(_bits(want[k]), _bits(clean[k])) and not np.array_equal(_bits(want[k]), _bits(H_in[k])), k
 
 
+# ---- 2a. one fit, two kernels -------------------------------------------------------------------------------------------------
+def _accepted_refit_scene(n):
+    """A scene and a start whose first refit is accepted (checked with the twin, no GPU needed): n = 4 is the plane's own four
+    points without noise, n = 257 has 30 % outliers and starts from a fit to eight of the plane's points."""
+    rng = np.random.default_rng(7000 + n)
+    outliers = int(0.3 * n) if n > 4 else 0
+    src, dst, H_true, good = R.plane_scene(rng, n - outliers, 0.7 if n > 4 else 0.0, outliers=outliers)
+    H_in = R.fit(src, dst, np.sort(rng.choice(np.flatnonzero(good), 8, replace=False))) if n > 4 else H_true
+    return src, dst, H_in
+
+
+@pytest.mark.parametrize("n", [4, 257])
+def test_the_label_fit_is_the_refit_of_the_same_set(engine, n):
+    """k_dlt_reestimate and k_refit_h run one fit (csrc/wg_fit.hpp): on labels = the inlier mask of H_in, the per-label
+    estimator returns the nine doubles of mh_refit_homography's first, accepted, round, bit for bit."""
+    src, dst, H_in = _accepted_refit_scene(n)
+    why = []
+    H_twin, _, _, acc_twin = R.refit(src, dst, H_in, THR2, 1, why)
+    assert acc_twin == 1 and why == ["iterations"], (acc_twin, why)          # (a property of the scene, not of the engine)
+    engine.set_correspondences(src, dst)
+    _, mask, inliers, _ = engine.refit_homography(H_in, THR2, 0)
+    H_refit, _, _, accepted = engine.refit_homography(H_in, THR2, 1)
+    assert accepted == 1 and inliers >= 4
+    labels = np.where(mask != 0, 0, -1).astype(np.int32)
+    engine.set_estimator("dlt")
+    engine.set_models(_models(np.random.default_rng(n), 1))
+    got = engine.reestimate(labels)
+    assert _label_counts(engine, 1).tolist() == [inliers]
+    assert np.array_equal(_bits(got[0]), _bits(H_refit)), (got[0], H_refit)
+    assert np.array_equal(_bits(got[0]), _bits(H_twin))
+
+
 # ---- 3. no epipolar geometry needed -------------------------------------------------------------------------------------------
 def _motions(n):
     if n not in _cache:

@@ -5,8 +5,11 @@ file: the function index inside local labels (.LBB12_3 -> .LBB_3) and the compil
 
     python tools/asm_kernel_diff.py --old old/expand.hip --new multi-h_amd/csrc/expand.hip multi-h_amd/csrc/expand_solve.hip
 
-Prints one line per kernel; exit status 1 when a body differs or a kernel exists on one side only."""
+Prints one line per kernel; exit status 1 when a body differs or a kernel exists on one side only.  --detail adds, for a
+kernel that differs, what differs: descriptor lines, mnemonic counts and a diff with register and block numbers masked."""
 import argparse
+import collections
+import difflib
 import hashlib
 import importlib
 import os
@@ -36,11 +39,33 @@ def kernels(src, include, tmp):
     return found
 
 
+def detail(old, new):
+    """What differs between two kernels that are not the same text: descriptor lines, the multiset of mnemonics, and the
+    body as a unified diff with register and block numbers masked (v12, s[4:5], .LBB_7 -> v#, s#, .LBB_#), so that a
+    renumbering alone shows nothing."""
+    desc = lambda k: [l for l in k if l.startswith(".amdhsa_")]
+    ops = lambda k: collections.Counter(l.split()[0] for l in k if not l.startswith(".") and not l.endswith(":"))
+    for o, n in zip(desc(old), desc(new)):
+        if o != n:
+            print(f"    descriptor: {o}  ->  {n}")
+    if desc(old) == desc(new):
+        print("    descriptor: equal")
+    a, b = ops(old), ops(new)
+    diff = {m: (a[m], b[m]) for m in sorted(set(a) | set(b)) if a[m] != b[m]}
+    print("    mnemonics: " + (", ".join(f"{m} {x} -> {y}" for m, (x, y) in diff.items()) if diff else "equal multiset"))
+    raw = [l for l in difflib.unified_diff(old, new, n=0, lineterm="") if l[0] in "+-" and l[:3] not in ("+++", "---")]
+    print(f"    text: {sum(l[0] == '-' for l in raw)} lines removed, {sum(l[0] == '+' for l in raw)} added; with register numbers masked:")
+    regs = lambda k: [re.sub(r"\b([vsa])(\d+|\[\d+:\d+\])|(\.LBB_)\d+", r"\1\3#", l) for l in k if not l.startswith(".amdhsa_")]
+    for l in difflib.unified_diff(regs(old), regs(new), "old", "new", n=0, lineterm=""):
+        print("      " + l)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--old", nargs="+", required=True)
     ap.add_argument("--new", nargs="+", required=True)
     ap.add_argument("--include", default=b.CSRC, help="where the old sources find the headers they include")
+    ap.add_argument("--detail", action="store_true", help="for a kernel that differs: descriptor, mnemonic counts, unified diff")
     a = ap.parse_args()
     old, new = {}, {}
     with tempfile.TemporaryDirectory() as tmp:
@@ -59,6 +84,8 @@ def main():
             same = old[name] == new[name]
             bad += not same
             print(f"{pretty:48s} {len(old[name]):6d} / {len(new[name]):6d} lines  {'identical' if same else 'DIFFERENT'}")
+            if a.detail and not same:
+                detail(old[name], new[name])
     return 1 if bad else 0
 
 
