@@ -159,8 +159,8 @@ MH_API int mh_refine_correspondences(mh_engine* e, const double F[9], const doub
  * the stage table of the harness (rows after the RANSAC mask, after OptimalTriangulation, after distanceError > 1). */
 #define MH_REFINE_KEPT 0
 #define MH_REFINE_NOT_IN_MASK 1          /* :809  mask[i] == 0 */
-#define MH_REFINE_TRIANGULATION 2        /* :815-817  OptimalTriangulation failed (optimum at infinity, :1170-1175) */
-#define MH_REFINE_AFFINE_TEST 3          /* :826  distanceError > 1 (a NaN is dropped here too, DESIGN 7) */
+#define MH_REFINE_TRIANGULATION 2        /* :815-817  OptimalTriangulation failed (optimum at infinity, :1170-1175) or its pair is not finite */
+#define MH_REFINE_AFFINE_TEST 3          /* :826  distanceError > 1 (a NaN is dropped here too, DESIGN 7.25) */
 MH_API int mh_get_refine_reasons(mh_engine* e, unsigned char* reason /* n */, int n);
 /* The point-only form of mh_refine_correspondences: the Hartley-Sturm correction (step 1) alone, the same kernel and the same
  * bits as there; no affinity is read (they need not be set).  Every row that is triangulated is kept.  refined (n x 4):

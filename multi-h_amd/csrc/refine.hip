@@ -151,6 +151,9 @@ k_refine_points(const double* __restrict__ x1, const double* __restrict__ y1,
     // R2^-1 = (1/s2) [-e2x e2y; -e2y -e2x]
     const double vx = (-g.e2x * p2x + g.e2y * p2y) / s2 + qx;
     const double vy = (-g.e2y * p2x - g.e2x * p2y) / s2 + qy;
+    // A NaN or infinite coordinate makes every comparison above false (t[deg] == 0, |im| <= 1e-10, valInf < bestS): the
+    // row would arrive here "triangulated" with a non-finite pair, and mh_refine_points would keep it.  It leaves at step 1.
+    if (!(isfinite(ux) && isfinite(uy) && isfinite(vx) && isfinite(vy))) return;
     if (points_only) {                                         // mh_refine_points: no affinity, no steps 2-3
         double* o = out + 4 * (size_t)n;
         o[0] = ux; o[1] = uy; o[2] = vx; o[3] = vy;

@@ -1292,16 +1292,20 @@ MHO_API void mho_poly_roots(const double* c, int n, double* re, double* im)
     for (int i = 0; i < n; ++i) { re[i] = z[i].re; im[i] = z[i].im; }
 }
 
-// reason (nullable, N): the stage a row left at — 0 kept, 1 not in the mask (:809), 2 OptimalTriangulation failed (:815-817),
-// 3 distanceError > 1 (:826) — the product's mh_get_refine_reasons.
-MHO_API void mho_refine_points_ex(const double* x1, const double* y1, const double* x2, const double* y2,
-                                  const double* aff, int N, const double* F, const double* e1, const double* e2,
-                                  const unsigned char* in_mask, unsigned char* keep, double* out /* N*8 */, unsigned char* reason)
+// reason (nullable, N): the stage a row left at — 0 kept, 1 not in the mask (:809), 2 OptimalTriangulation failed (:815-817)
+// or returned a non-finite pair (a NaN or infinite coordinate makes every comparison of :1156-1170 false), 3 distanceError > 1
+// (:826) — the product's mh_get_refine_reasons.
+// points_only: step 1 alone (the product's mh_refine_points) — out is N*4, aff is not read, every triangulated row is kept.
+static void refine_points_impl(const double* x1, const double* y1, const double* x2, const double* y2,
+                               const double* aff, int N, const double* F, const double* e1, const double* e2,
+                               const unsigned char* in_mask, unsigned char* keep, double* out /* N*8, points_only: N*4 */,
+                               unsigned char* reason, int points_only)
 {
     const double e1x = e1[0], e1y = e1[1], e2x = e2[0], e2y = e2[1];
+    const int width = points_only ? 4 : 8;
     for (int n = 0; n < N; ++n) {
         keep[n] = 0;
-        for (int q = 0; q < 8; ++q) out[8 * (size_t)n + q] = 0.0;
+        for (int q = 0; q < width; ++q) out[width * (size_t)n + q] = 0.0;
         if (reason) reason[n] = 1;
         if (in_mask && !in_mask[n]) continue;
         if (reason) reason[n] = 2;
@@ -1351,7 +1355,6 @@ MHO_API void mho_refine_points_ex(const double* x1, const double* y1, const doub
         }
         const double valInf = 1 / f12 + (c * c) / (a * a + f22 * c * c);
         if (valInf < bestS) continue;
-        if (reason) reason[n] = 3;
         const double l0 = F3[1] * bestT + F3[2], l1 = F3[4] * bestT + F3[5], l2 = F3[7] * bestT + F3[8];
         const double w2 = l0 * l0 + l1 * l1;
         const double iw = 1.0 / w2;
@@ -1361,6 +1364,15 @@ MHO_API void mho_refine_points_ex(const double* x1, const double* y1, const doub
         const double uy = (e1y * 0.0 + e1x * bestT) / s1 + py;
         const double vx = (-e2x * p2x + e2y * p2y) / s2 + qx;
         const double vy = (-e2y * p2x - e2x * p2y) / s2 + qy;
+        if (!(std::isfinite(ux) && std::isfinite(uy) && std::isfinite(vx) && std::isfinite(vy))) continue;   // no corrected pair
+        if (points_only) {
+            double* o = out + 4 * (size_t)n;
+            o[0] = ux; o[1] = uy; o[2] = vx; o[3] = vy;
+            keep[n] = 1;
+            if (reason) reason[n] = 0;
+            continue;
+        }
+        if (reason) reason[n] = 3;
         const double A11 = aff[4 * n], A12 = aff[4 * n + 1], A21 = aff[4 * n + 2], A22 = aff[4 * n + 3];
         const double L1[3] = { (F[0] * vx + F[3] * vy) + F[6], (F[1] * vx + F[4] * vy) + F[7], (F[2] * vx + F[5] * vy) + F[8] };
         const double L2[3] = { (F[0] * ux + F[1] * uy) + F[2], (F[3] * ux + F[4] * uy) + F[5], (F[6] * ux + F[7] * uy) + F[8] };
@@ -1389,6 +1401,21 @@ MHO_API void mho_refine_points_ex(const double* x1, const double* y1, const doub
         keep[n] = 1;
         if (reason) reason[n] = 0;
     }
+}
+
+MHO_API void mho_refine_points_ex(const double* x1, const double* y1, const double* x2, const double* y2,
+                                  const double* aff, int N, const double* F, const double* e1, const double* e2,
+                                  const unsigned char* in_mask, unsigned char* keep, double* out /* N*8 */, unsigned char* reason)
+{
+    refine_points_impl(x1, y1, x2, y2, aff, N, F, e1, e2, in_mask, keep, out, reason, 0);
+}
+
+// Step 1 alone: keep, out (N*4: x1 y1 x2 y2) and reason (0, 1, 2) of the product's mh_refine_points.
+MHO_API void mho_refine_points_only(const double* x1, const double* y1, const double* x2, const double* y2, int N,
+                                    const double* F, const double* e1, const double* e2, const unsigned char* in_mask,
+                                    unsigned char* keep, double* out /* N*4 */, unsigned char* reason)
+{
+    refine_points_impl(x1, y1, x2, y2, nullptr, N, F, e1, e2, in_mask, keep, out, reason, 1);
 }
 
 MHO_API void mho_refine_points(const double* x1, const double* y1, const double* x2, const double* y2,

@@ -234,6 +234,22 @@ def refine_points(src, dst, aff, F, e1, e2, in_mask=None, with_reasons=False):
     return (keep, out, reason) if with_reasons else (keep, out)
 
 
+def refine_points_only(src, dst, F, e1, e2, in_mask=None):
+    """mho_refine_points_only: step 1 alone, no affinities.  Returns (keep [n], refined [n, 4], reason [n])."""
+    x1, y1, x2, y2 = soa(src, dst)
+    F, e1, e2 = f64(F), f64(e1), f64(e2)
+    keep = np.empty(x1.size, dtype=np.uint8)
+    out = np.empty((x1.size, 4))
+    reason = np.empty(x1.size, dtype=np.uint8)
+    mp = None
+    if in_mask is not None:
+        in_mask = np.ascontiguousarray(in_mask, dtype=np.uint8)
+        mp = in_mask.ctypes.data_as(C.POINTER(C.c_ubyte))
+    lib().mho_refine_points_only(_d(x1), _d(y1), _d(x2), _d(y2), x1.size, _d(F), _d(e1), _d(e2), mp,
+                                 keep.ctypes.data_as(C.POINTER(C.c_ubyte)), _d(out), reason.ctypes.data_as(C.POINTER(C.c_ubyte)))
+    return keep, out, reason
+
+
 def haf_point(src, dst, aff, F, e2, locality):
     x1, y1, x2, y2 = soa(src, dst)
     aff, F, e2 = f64(aff), f64(F), f64(e2)
