@@ -427,6 +427,52 @@ MH_API int mh_polish_homographies(mh_engine* e, const int* labels /* n */, const
                                   int max_iterations, double* H_out /* m x 9 */,
                                   double* cost /* m x 2: S before, S after; nullable */,
                                   int* info /* m x 4: members, iterations run, steps accepted, status; nullable */);
+/* Iteratively reweighted N-point DLT refits of m homographies, each over the resident correspondences that carry its label.
+ * Every other per-label estimate of the engine (the HAF fit, the 3-point fit, MH_ESTIMATOR_DLT, mh_polish_homographies) is a
+ * plain least-squares fit over whatever the labeling handed it, contaminated or not; this one weighs each member by its MSAC
+ * gain under the model that stands, so members that model explains badly pull less and members beyond c2 not at all.  There
+ * is no counterpart in the reference, so this comment is the definition (tests/reweight_h_numpy.py restates it).  One launch
+ * of one 256-thread workgroup per model whatever `rounds` is (csrc/reweight_h.hip, k_reweight_h).  It reads the points only —
+ * not the affinities, F, the resident model set, counts, weights, data cost or graph — and leaves all of them untouched.
+ *   Members     S_k = { i : labels[i] == k }, k = 0 .. m - 1; every other value (-1, >= m) belongs to nobody.
+ *   Weight      of member i under H: d2 the forward transfer error in the reference's operation order (M/MultiH.cpp:434-441),
+ *               always the forward error, whatever mh_set_residual_mode says;
+ *                 w = d2 < c2 ? 1.0 - (d2 / c2) : 0.0
+ *               strictly; a NaN gives 0.  One IEEE division and one subtraction: mh_score_msac's expression in front of its
+ *               256.0 *.  The support of H is the set of members with d2 < c2; each of them has w > 0.
+ *   Sums        every FP64 sum below in the engine's order (that of mh_refit_homography): thread t of 256 starts at 0.0 and adds
+ *               the terms of the members with index = t (mod 256) in ascending index, each as acc = acc + term; then the binary
+ *               tree s = 128 .. 1, v[t] = v[t] + v[t + s].  No fused multiply-add anywhere.  Members with w == 0 contribute no
+ *               term: they are skipped, not added as zeros.
+ *   wfit(H)     fit(S) of mh_refit_homography with every member's terms weighted by its w under H:
+ *     1. W = sum of w and c = |support|; fails when c < 4;
+ *     2. the centroids of both images, (sum of w * coordinate) * (1.0 / W);
+ *     3. d = sum of w * sqrt(ax * ax + ay * ay), (ax, ay) = point - centroid, and the scales s = sqrt(2.0) / (d / W); fails when
+ *        a scale is not finite;
+ *     4. x, y, u, v and p = (x, y, 1.0) exactly as in fit(S) step 3;
+ *     5. for the six pairs a <= b in the order 00 01 02 11 12 22, t = p_a * p_b, wt = w * t and the 24 sums
+ *          G0 += wt    G1 += u * wt    G2 += v * wt    G3 += (u * u + v * v) * wt
+ *     6. the normal matrix, the Jacobi solve, the de-normalisation and the finiteness test of fit(S) steps 4 (layout) to 7.
+ *               With every weight 1.0 wfit is fit(S) bit for bit.
+ *   Rounds      cur = H_in[k], done = 0; for r = 1 .. rounds:
+ *     1. cand = wfit(cur); stop when it fails;
+ *     2. stop when cand equals cur bit for bit;
+ *     3. cur = cand, ++done.
+ *               There is no acceptance test: the caller gets the gains and judges.
+ *   Outputs     H_out[k] = cur — with done == 0 H_in[k]'s nine doubles unchanged (not renormalised); gain[k] = (W under H_in[k],
+ *               W under H_out[k]) over the members; info[k] = (|S_k|, support of H_out[k], done, status).  status 1: |S_k| < 4;
+ *               status 2 (looked at after status 1): an entry of H_in[k] is not finite.  With status 1 or 2 H_out[k] is H_in[k]'s
+ *               nine doubles, gain[k] = (0, 0), the support 0 and done 0.  rounds = 0 reports W and the support of H_in.
+ * MH_ERR_INVALID for a null engine, labels, H_in or H_out, m outside [1, 65536], rounds outside [0, MH_REWEIGHT_MAX_ROUNDS], a
+ * c2 that is not finite or <= 0; MH_ERR_NOT_SET without correspondences.  H_out may be H_in.  The scale is the caller's: at c2
+ * near the noise floor the weights cut into the noise and cost accuracy on clean sets.  The point-only and
+ * epipolar-free routes can call it.  Deterministic, so every rank of a sharded run (all hold all points) gets the same result
+ * without an exchange. */
+#define MH_REWEIGHT_MAX_ROUNDS 16
+MH_API int mh_reweight_homographies(mh_engine* e, const int* labels /* n */, const double* H_in /* m x 9 */, int m,
+                                    double c2, int rounds, double* H_out /* m x 9 */,
+                                    double* gain /* m x 2: W of H_in, W of H_out; nullable */,
+                                    int* info /* m x 4: members, support of H_out, rounds done, status; nullable */);
 /* Trial statistics of HomographyCompatibilityCheck (M/MultiH.cpp:128-196; host/merge_step.cpp ClusterMedian) for
  * `clusters` clusters of at least 19 points each.  pts_xyxy: the clusters' points back to back in cluster order, 4 doubles
  * each (x1 y1 x2 y2); cluster_begin[c] .. cluster_begin[c+1] (cluster_begin[0] = 0); per (cluster, trial): tri = the
@@ -634,6 +680,15 @@ MH_API int mh_get_core_components(mh_engine* e, int* out /* moves x 16 */, int m
 #define MH_ESTIMATOR_3PT 1
 #define MH_ESTIMATOR_DLT 2
 MH_API int mh_set_estimator(mh_engine* e, int estimator);
+/* Reweighted rounds for the MH_ESTIMATOR_DLT re-estimator of mh_reestimate and mh_labeling_step.  rounds = 0 (default): nothing
+ * anywhere changes, k_dlt_reestimate runs.  rounds in [1, MH_REWEIGHT_MAX_ROUNDS]: the re-estimator is
+ * mh_reweight_homographies(labels, H, Nh, c2, rounds) in place on the resident models — each label starts from its standing
+ * model, the one the labeling was made with; a label whose first round fails (or with fewer than 4 members, or a standing model
+ * that is not finite) keeps its H; MH_BUF_LABEL_COUNTS receives |S_k| as before.  The other estimators ignore the setting, and
+ * so does the refit of the greedy selections (mh_set_tuning key 30): the selections and their mode word stay as they are.
+ * Sticky per engine; mh_set_correspondences does not reset it.  MH_ERR_INVALID for a null engine, rounds outside
+ * [0, MH_REWEIGHT_MAX_ROUNDS], or with rounds > 0 a c2 that is not finite or <= 0 (with rounds = 0 c2 is not looked at). */
+MH_API int mh_set_estimator_reweighting(mh_engine* e, int rounds, double c2);
 /* GetHomographyHAFNonminimal for every label (M/MultiH.cpp:913-989 + the 1/lambda rescale of
  * Homography_RefineHAFCallback.h:33-34), or the 3-point fit under MH_ESTIMATOR_3PT, or the N-point DLT under MH_ESTIMATOR_DLT.
  * labels: -1..Nh-1 per point.  Updates the current model set in place (the data cost goes stale); H_out (nullable) receives a

@@ -31,8 +31,8 @@ SYMBOLS = [
     "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_propose_fund7", "mh_get_fund7_samples", "mh_estimate_fundamental_minimal", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons", "mh_refine_points",
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
     "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_propose_haf", "mh_get_haf_support", "mh_propose_3pt", "mh_set_residual_mode", "mh_score", "mh_score_msac", "mh_select_best_msac",
-    "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_select_greedy_msac", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_refit_homography", "mh_polish_homographies", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
-    "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
+    "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_select_greedy_msac", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_refit_homography", "mh_polish_homographies", "mh_reweight_homographies", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
+    "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_set_estimator_reweighting", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
     "mh_profile_get", "mh_set_tuning",
 ]
 
@@ -504,6 +504,23 @@ class Engine:
                                                     _p(out, C.c_double), _p(cost, C.c_double), _p(info, C.c_int)))
         return out, cost, info
 
+    def reweight_homographies(self, labels, H, c2: float, rounds: int):
+        """mh_reweight_homographies: every row of H (m x 9) refitted by `rounds` reweighted N-point DLT rounds over the
+        correspondences that carry its label, weights 1 - d2 / c2, all rounds in one launch; the model set is left untouched.
+        Returns (H_out [m, 9], gain [m, 2] = W under H_in and under H_out, info int32 [m, 4] = members, support of H_out,
+        rounds done, status)."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        if labels.size != self.n:
+            raise ValueError(f"labels: {labels.size} values for {self.n} correspondences")
+        H = np.ascontiguousarray(H, dtype=np.float64).reshape(-1, 9)
+        m = H.shape[0]
+        out = np.empty((m, 9), dtype=np.float64)
+        gain = np.empty((m, 2), dtype=np.float64)
+        info = np.empty((m, 4), dtype=np.int32)
+        self._check(self.lib.mh_reweight_homographies(self._h, _p(labels, C.c_int), _p(H, C.c_double), m, C.c_double(c2), int(rounds),
+                                                      _p(out, C.c_double), _p(gain, C.c_double), _p(info, C.c_int)))
+        return out, gain, info
+
     def inlier_moments(self, thr2: float):
         m = self.model_count
         mo = np.empty((m, 6), dtype=np.float64)
@@ -586,6 +603,11 @@ class Engine:
         if name not in ESTIMATORS:
             raise ValueError(f"unknown estimator {name!r} (haf | 3pt | dlt)")
         self._check(self.lib.mh_set_estimator(self._h, ESTIMATORS[name]))
+
+    def set_estimator_reweighting(self, rounds: int, c2: float = 0.0):
+        """mh_set_estimator_reweighting: under the "dlt" estimator, mh_reestimate and mh_labeling_step run `rounds` reweighted
+        rounds at scale c2 from each label's standing model instead of the plain fit; 0 (default) off.  Sticky."""
+        self._check(self.lib.mh_set_estimator_reweighting(self._h, int(rounds), C.c_double(c2)))
 
     def set_data_term(self, name: str):
         """mh_set_data_term: "reference" (default) or "rising" (the cost grows with the error); sticky, marks the data cost stale."""

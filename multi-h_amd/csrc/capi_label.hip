@@ -365,6 +365,11 @@ namespace mhe {
 int launch_estimator(mh_engine* e, const int* labels_dev, int Nh, double* H_dev, int* counts_dev)
 {
     ScopedTimer t(e, MH_K_REESTIMATE);
+    if (e->estimator == MH_ESTIMATOR_DLT && e->est_rw_rounds > 0) {      // mh_set_estimator_reweighting: from each label's standing model, in place
+        HIPCHK(launch_reweight_h(e->pts(), labels_dev, H_dev, Nh, e->est_rw_c2, e->est_rw_rounds, H_dev, nullptr, nullptr, counts_dev,
+                                 e->stream));
+        return MH_OK;
+    }
     if (e->estimator == MH_ESTIMATOR_DLT) {
         HIPCHK(launch_reestimate_dlt(e->pts(), labels_dev, Nh, H_dev, counts_dev, e->stream));
         return MH_OK;
@@ -392,6 +397,19 @@ int mh_set_estimator(mh_engine* e, int estimator)
     if (estimator != MH_ESTIMATOR_HAF && estimator != MH_ESTIMATOR_3PT && estimator != MH_ESTIMATOR_DLT)
         return fail(MH_ERR_INVALID, "unknown estimator");
     e->estimator = estimator;
+    return MH_OK;
+    });
+}
+
+int mh_set_estimator_reweighting(mh_engine* e, int rounds, double c2)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (rounds < 0 || rounds > REWEIGHT_H_MAX_ROUNDS) return fail(MH_ERR_INVALID, "rounds outside [0, 16]");
+    if (rounds > 0 && (!(c2 > 0.0) || !std::isfinite(c2)))
+        return fail(MH_ERR_INVALID, "c2 is not a finite positive number");
+    e->est_rw_rounds = rounds;
+    e->est_rw_c2 = rounds > 0 ? c2 : 0.0;
     return MH_OK;
     });
 }

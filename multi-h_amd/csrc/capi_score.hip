@@ -514,6 +514,35 @@ int mh_polish_homographies(mh_engine* e, const int* labels, const double* H_in, 
     });
 }
 
+int mh_reweight_homographies(mh_engine* e, const int* labels, const double* H_in, int m, double c2, int rounds, double* H_out,
+                             double* gain, int* info)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (!labels) return fail(MH_ERR_INVALID, "null labels");
+    if (!H_in || !H_out) return fail(MH_ERR_INVALID, "null homographies");
+    if (m < 1 || m > REWEIGHT_H_MAX_MODELS) return fail(MH_ERR_INVALID, "m outside [1, 65536]");
+    if (rounds < 0 || rounds > REWEIGHT_H_MAX_ROUNDS) return fail(MH_ERR_INVALID, "rounds outside [0, 16]");
+    if (!(c2 > 0.0) || !std::isfinite(c2)) return fail(MH_ERR_INVALID, "c2 is not a finite positive number");
+    int rc = require_points(e);
+    if (rc) return rc;
+    const size_t mm = (size_t)m;
+    HIPCHK(e->rw_labels.reserve(e->n));
+    HIPCHK(e->rw_H.reserve(18 * mm));
+    HIPCHK(e->rw_gain.reserve(2 * mm));
+    HIPCHK(e->rw_info.reserve(4 * mm));
+    HIPCHK(hipMemcpyAsync(e->rw_labels.p, labels, sizeof(int) * (size_t)e->n, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->rw_H.p, H_in, sizeof(double) * 9 * mm, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(launch_reweight_h(e->pts(), e->rw_labels.p, e->rw_H.p, m, c2, rounds, e->rw_H.p + 9 * mm, e->rw_gain.p, e->rw_info.p,
+                             nullptr, e->stream));
+    HIPCHK(hipMemcpyAsync(H_out, e->rw_H.p + 9 * mm, sizeof(double) * 9 * mm, hipMemcpyDeviceToHost, e->stream));
+    if (gain) HIPCHK(hipMemcpyAsync(gain, e->rw_gain.p, sizeof(double) * 2 * mm, hipMemcpyDeviceToHost, e->stream));
+    if (info) HIPCHK(hipMemcpyAsync(info, e->rw_info.p, sizeof(int) * 4 * mm, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MH_OK;
+    });
+}
+
 int mh_inlier_moments(mh_engine* e, double thr2, double* moments, double* min_eig)
 {
     return guarded([&]() -> int {

@@ -127,6 +127,15 @@ constexpr int POLISH_H_MAX_MODELS = 65536;
 hipError_t launch_polish_h(const Points& p, const int* labels, const double* H_in, int m, int max_iterations, double* H_out,
                            double* cost, int* info, hipStream_t s);
 
+// --- reweight_h.hip: iteratively reweighted N-point DLT refits, one homography per label, every round inside one launch of one
+// workgroup per model (mh_reweight_homographies; the MH_ESTIMATOR_DLT re-estimator under mh_set_estimator_reweighting) ---
+// labels: p.n ints on the device; H_in, H_out: m x 9 doubles (may be the same array); gain: m x 2 doubles (W of H_in, W of
+// H_out); info: m x 4 ints (members, support of H_out, rounds done, status); counts: m ints (members) — the last three nullable
+constexpr int REWEIGHT_H_MAX_ROUNDS = 16;
+constexpr int REWEIGHT_H_MAX_MODELS = 65536;     // of a call of mh_reweight_homographies
+hipError_t launch_reweight_h(const Points& p, const int* labels, const double* H_in, int m, double c2, int rounds, double* H_out,
+                             double* gain, int* info, int* counts, hipStream_t s);
+
 // --- datacost.hip -----------------------------------------------------------
 // the data cost of every model against every point, int32, model-major with pitch ldc (datacost.hip)
 inline long long cost_ld(int n) { return ((long long)n + 31) & ~31ll; }

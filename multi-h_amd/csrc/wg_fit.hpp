@@ -1,5 +1,5 @@
 // wg_fit.hpp — what the per-model fit kernels share: k_fund_refit, k_moments, k_haf_reestimate, k_3pt_reestimate, k_refit_h,
-// k_polish_h and k_dlt_reestimate.  One 256-thread workgroup per model, strided passes over the points, thread 0 solves.
+// k_polish_h, k_dlt_reestimate and k_reweight_h.  One 256-thread workgroup per model, strided passes over the points, thread 0 solves.
 //
 // The order of every FP64 sum, stated here once: thread t adds its members t, t + 256, ... in ascending index from 0.0, then
 // the binary tree v[t] += v[t + s], s = 128 .. 1, over the workgroup's LDS buffer (wg_tree).  The twins (oracle/mh_oracle.cpp
@@ -12,6 +12,9 @@
 //     dlt_accumulate                   pass 3: one correspondence into the 24 sums G0..G3 over the six products p_a p_b
 //     dlt_solve                        thread 0: the 9 x 9 normal matrix, cyclic Jacobi, k_dlt4's de-normalisation, norm and sign
 // k_refit_h and k_dlt_reestimate are these pieces around their own membership and exits; k_fund_refit shares the first two.
+// wfit(H), the same fit with every member's terms weighted (mh_reweight_homographies; k_reweight_h): the weighted steps stand
+// beside the unweighted ones (hartley_centroids_w, hartley_distances_w, hartley_scales_w, dlt_accumulate_w); Hartley and
+// dlt_solve serve both.  With every weight 1.0 they give the unweighted steps' bits (w * t is exact, the sum of the weights is c).
 // (k_dlt_reestimate writes pass 1's counted tree out: as a call it changes the instructions of its label fetch.)
 #pragma once
 #include "mh_device.hpp"
@@ -97,6 +100,17 @@ __device__ __forceinline__ void hartley_centroids(const double* sums, int c, dou
     hartley_get_centroids(par, hn);
 }
 
+// ... weighted: the four sums of w * coordinate and W, the sum of the weights
+__device__ __forceinline__ void hartley_centroids_w(const double* sums, double W, double* par, int t, Hartley& hn)
+{
+    if (t == 0) {
+        const double inv = 1.0 / W;
+        par[0] = sums[0] * inv; par[1] = sums[1] * inv; par[2] = sums[2] * inv; par[3] = sums[3] * inv;
+    }
+    __syncthreads();
+    hartley_get_centroids(par, hn);
+}
+
 // pass 2's term of one member: its distances to the two centroids
 __device__ __forceinline__ void hartley_distances(const Hartley& hn, double x, double y, double u, double v, double& d1, double& d2)
 {
@@ -105,12 +119,32 @@ __device__ __forceinline__ void hartley_distances(const Hartley& hn, double x, d
     d2 = d2 + sqrt(bx * bx + by * by);
 }
 
+// ... weighted by w
+__device__ __forceinline__ void hartley_distances_w(const Hartley& hn, double w, double x, double y, double u, double v, double& d1,
+                                                    double& d2)
+{
+    const double ax = x - hn.cx1, ay = y - hn.cy1, bx = u - hn.cx2, by = v - hn.cy2;
+    d1 = d1 + w * sqrt(ax * ax + ay * ay);
+    d2 = d2 + w * sqrt(bx * bx + by * by);
+}
+
 // Pass 2's two distance sums -> the scales, in par[4], par[5] and hn; called like hartley_centroids.
 __device__ __forceinline__ void hartley_scales(const double* sums, int c, double* par, int t, Hartley& hn)
 {
     if (t == 0) {
         par[4] = sqrt(2.0) / (sums[0] / (double)c);
         par[5] = sqrt(2.0) / (sums[1] / (double)c);
+    }
+    __syncthreads();
+    hn.s1 = par[4]; hn.s2 = par[5];
+}
+
+// ... from the weighted distance sums and W
+__device__ __forceinline__ void hartley_scales_w(const double* sums, double W, double* par, int t, Hartley& hn)
+{
+    if (t == 0) {
+        par[4] = sqrt(2.0) / (sums[0] / W);
+        par[5] = sqrt(2.0) / (sums[1] / W);
     }
     __syncthreads();
     hn.s1 = par[4]; hn.s2 = par[5];
@@ -135,6 +169,28 @@ __device__ __forceinline__ void dlt_accumulate(const Hartley& hn, double x0, dou
             acc[6 + k] = acc[6 + k] + u * tt;
             acc[12 + k] = acc[12 + k] + v * tt;
             acc[18 + k] = acc[18 + k] + w * tt;
+            ++k;
+        }
+}
+
+// ... weighted: every term of the member carries wt = w * (p_a p_b)
+__device__ __forceinline__ void dlt_accumulate_w(const Hartley& hn, double wgt, double x0, double y0, double u0, double v0,
+                                                 double (&acc)[DLT_SUMS])
+{
+    const double x = (x0 - hn.cx1) * hn.s1, y = (y0 - hn.cy1) * hn.s1, u = (u0 - hn.cx2) * hn.s2, v = (v0 - hn.cy2) * hn.s2;
+    const double p[3] = { x, y, 1.0 };
+    const double w = u * u + v * v;
+    int k = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b) {
+            const double tt = p[a] * p[b];
+            const double wt = wgt * tt;
+            acc[k] = acc[k] + wt;
+            acc[6 + k] = acc[6 + k] + u * wt;
+            acc[12 + k] = acc[12 + k] + v * wt;
+            acc[18 + k] = acc[18 + k] + w * wt;
             ++k;
         }
 }

@@ -37,6 +37,9 @@
 #pragma weak mh_refit_homography
 // ... and for the LM polish of the results (SetTailPolish, SetModelPolish): without its entry point those modes fail with a message.
 #pragma weak mh_polish_homographies
+// ... and for the reweighted refits (SetModelReweight, SetEstimatorReweight): the same.
+#pragma weak mh_reweight_homographies
+#pragma weak mh_set_estimator_reweighting
 // ... and for the selection ranked by weight (SetSelectionScore): without its entry point that mode fails with a message.
 #pragma weak mh_select_greedy_msac
 // ... and for the HAF proposals (SetProposalSource): without its entry point that source fails with a message.
@@ -399,6 +402,34 @@ bool MultiH::Run(bool points_only)
         std::cerr << "Error: the engine library has no single-model read-back for the tail's polish (mh_get_model)\n";
         return false;
     }
+    // whether the final models and the loop's DLT re-estimator run reweighted rounds
+    if (model_reweight < 0 || model_reweight > 16 || estimator_reweight < 0 || estimator_reweight > 16) {
+        std::cerr << "Error: reweighting rounds " << model_reweight << " (final) / " << estimator_reweight << " (estimator) outside [0, 16]\n";
+        return false;
+    }
+    if (!(model_reweight_scale >= 0.0) || !(estimator_reweight_scale >= 0.0) || std::isinf(model_reweight_scale) ||
+        std::isinf(estimator_reweight_scale)) {
+        std::cerr << "Error: reweighting scale " << model_reweight_scale << " (final) / " << estimator_reweight_scale
+                  << " (estimator) is not a finite number >= 0\n";
+        return false;
+    }
+    if (model_reweight > 0 && !mh_reweight_homographies) {
+        std::cerr << "Error: the engine library has no reweighted refit (mh_reweight_homographies)\n";
+        return false;
+    }
+    {
+        // sticky on the engine, and engines are reused: set on every call, off unless the DLT estimator runs with rounds
+        const int rw = est == MH_ESTIMATOR_DLT ? estimator_reweight : 0;
+        const double px = estimator_reweight_scale > 0.0 ? estimator_reweight_scale : threshold_homography;
+        if (!mh_set_estimator_reweighting) {
+            if (rw > 0) {
+                std::cerr << "Error: the engine library has no reweighted estimator (mh_set_estimator_reweighting)\n";
+                return false;
+            }
+        } else if (!Check(mh_set_estimator_reweighting(engine, rw, px * px), "mh_set_estimator_reweighting")) {
+            return false;
+        }
+    }
     // how ProposeModels ranks a batch (INIT_STABLE_SETS proposes nothing: the mode is not looked at)
     if (init_mode != INIT_STABLE_SETS) {
         if (selection_score != SELECTION_SCORE_COUNT && selection_score != SELECTION_SCORE_MSAC) {
@@ -616,11 +647,12 @@ bool MultiH::Run(bool points_only)
         labeling.resize(src_points.size(), -1);
         cluster_homographies.resize(0);
         HandleDegenerateCase();
-    } else if (model_polish > 0) {
-        // every cluster's homography polished over its labelled (refined) correspondences: the engine still holds them
+    } else if (model_reweight > 0 || model_polish > 0) {
+        // every cluster's homography refitted (reweighted rounds, then the polish) over its labelled (refined) correspondences:
+        // the engine still holds them
         const int nh = static_cast<int>(cluster_homographies.size());
         if (labeling.size() != src_points.size()) {
-            std::cerr << "Error: model polish: " << labeling.size() << " labels for " << src_points.size() << " correspondences\n";
+            std::cerr << "Error: model refit: " << labeling.size() << " labels for " << src_points.size() << " correspondences\n";
             return false;
         }
         std::vector<double> H(9 * (size_t)nh);
@@ -628,7 +660,14 @@ bool MultiH::Run(bool points_only)
             const double* p = reinterpret_cast<const double*>(cluster_homographies[i].data);
             for (int k = 0; k < 9; ++k) H[9 * (size_t)i + k] = p[k];
         }
-        if (!Check(mh_polish_homographies(engine, labeling.data(), H.data(), nh, model_polish, H.data(), nullptr, nullptr),
+        if (model_reweight > 0) {
+            const double px = model_reweight_scale > 0.0 ? model_reweight_scale : threshold_homography;
+            if (!Check(mh_reweight_homographies(engine, labeling.data(), H.data(), nh, px * px, model_reweight, H.data(), nullptr, nullptr),
+                       "mh_reweight_homographies"))
+                return false;
+        }
+        if (model_polish > 0 &&
+            !Check(mh_polish_homographies(engine, labeling.data(), H.data(), nh, model_polish, H.data(), nullptr, nullptr),
                    "mh_polish_homographies"))
             return false;
         for (int i = 0; i < nh; ++i) cluster_homographies[i] = MatFrom9(&H[9 * (size_t)i]);
@@ -1273,6 +1312,13 @@ extern "C" __attribute__((visibility("default")))
 void mhh_set_tail_polish(int iterations) { g_tail_polish = iterations; }
 extern "C" __attribute__((visibility("default")))
 void mhh_set_model_polish(int iterations) { g_model_polish = iterations; }
+// MultiH::SetModelReweight and MultiH::SetEstimatorReweight (scale: the class default, the homography threshold) for the next
+// mhh_run_process calls (< 0: the class default)
+static int g_model_reweight = -1, g_estimator_reweight = -1;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_model_reweight(int rounds) { g_model_reweight = rounds; }
+extern "C" __attribute__((visibility("default")))
+void mhh_set_estimator_reweight(int rounds) { g_estimator_reweight = rounds; }
 // MultiH::SetEstimator (-1: leave as is, the class default) and MultiH::SetEpipolarFree for the next mhh_run_process calls
 static int g_estimator = -1, g_epipolar_free = 0;
 extern "C" __attribute__((visibility("default")))
@@ -1365,6 +1411,8 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     if (g_tail_refit >= 0) mh.SetTailRefit(g_tail_refit);
     if (g_tail_polish >= 0) mh.SetTailPolish(g_tail_polish);
     if (g_model_polish >= 0) mh.SetModelPolish(g_model_polish);
+    if (g_model_reweight >= 0) mh.SetModelReweight(g_model_reweight);
+    if (g_estimator_reweight >= 0) mh.SetEstimatorReweight(g_estimator_reweight);
     if (g_selection_score >= 0) mh.SetSelectionScore(g_selection_score);
     if (g_estimator >= 0) mh.SetEstimator(g_estimator);
     mh.SetEpipolarFree(g_epipolar_free != 0);

@@ -174,6 +174,16 @@ public:
     // iteration count are unchanged.  0 (default) off; n in [1, 32]; works on the point-only route and on every rank of a
     // sharded run alike.  Any other value makes Process() fail with a message.
     void SetModelPolish(int iterations) { model_polish = iterations; }
+    // Reweighted refit of the final models (mh_reweight_homographies, include/multih_hip.h): where SetModelPolish runs, and in
+    // front of it when both are set, every cluster's homography is refitted over the correspondences that carry its label by
+    // at most `rounds` reweighted N-point DLT rounds, weights 1 - d2 / scale_px^2 under the model that stands (scale_px = 0:
+    // the homography threshold).  Labels, energy and iteration count are unchanged.  0 (default) off; rounds in [1, 16]; reads
+    // the points alone, so every route can use it.  Any other value makes Process() fail with a message.
+    void SetModelReweight(int rounds, double scale_px = 0) { model_reweight = rounds; model_reweight_scale = scale_px; }
+    // The same rounds inside the loop: under ESTIMATOR_DLT (SetEpipolarFree(true) included) every re-estimation starts from the
+    // label's standing model and runs `rounds` reweighted rounds instead of the plain fit (mh_set_estimator_reweighting).  The
+    // other estimators ignore it.  0 (default) off; rounds in [1, 16]; any other value makes Process() fail with a message.
+    void SetEstimatorReweight(int rounds, double scale_px = 0) { estimator_reweight = rounds; estimator_reweight_scale = scale_px; }
     // How ProposeModels ranks the hypotheses of a batch — the initial batch, the iterative ones and the sharded route alike:
     // SELECTION_SCORE_COUNT (default) by inlier count (mh_select_greedy), SELECTION_SCORE_MSAC by the MSAC weight among the
     // hypotheses with at least min_inliers-or-8 inliers (mh_select_greedy_msac, include/multih_hip.h: the count makes a hypothesis
@@ -302,6 +312,8 @@ protected:
     int tail_score = TAIL_SCORE_COUNT;
     int tail_refit = 0;
     int tail_polish = 0, model_polish = 0;
+    int model_reweight = 0, estimator_reweight = 0;
+    double model_reweight_scale = 0.0, estimator_reweight_scale = 0.0;
     int selection_score = SELECTION_SCORE_COUNT;
     int proposal_sampler = PROPOSAL_UNIFORM, proposal_sampler_k = 32, proposal_uniform_per_16 = 4;
     bool proposal_local_run = false;      // this Process() call proposes with the local sampler (its table is on the engine)

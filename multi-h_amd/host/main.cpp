@@ -36,6 +36,11 @@
 //                                0, the default, off; N <= 32); --tail-refit 1 --tail-polish 10 is cv::findHomography's sequence
 //                  [--polish N]       every final cluster's homography polished the same way over its labelled correspondences
 //                                (MultiH::SetModelPolish; 0, the default, off; N <= 32)
+//                  [--reweight n[:scale]]   every final cluster's homography refitted by n reweighted N-point DLT rounds over its
+//                                labelled correspondences, weights 1 - d2 / scale^2 (MultiH::SetModelReweight; 0, the default, off;
+//                                n <= 16; scale in pixels, default thrH); runs in front of --polish
+//                  [--estimator-reweight n[:scale]]   the same rounds as the loop's re-estimator under --estimator dlt and
+//                                --no-epipolar (MultiH::SetEstimatorReweight; 0, the default, off)
 //                  [--select-score count|msac]   how the proposal batches are ranked (MultiH::SetSelectionScore): count, the default,
 //                                by inlier count (mh_select_greedy); msac by the MSAC weight among the hypotheses with enough
 //                                inliers (mh_select_greedy_msac)
@@ -126,7 +131,7 @@ int main(int argc, char** argv)
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
                      "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] [--f-estimator ls8|minimal] "
-                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--data-term reference|rising] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
+                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--data-term reference|rising] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--reweight n[:scale]] [--estimator-reweight n[:scale]] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
         return 2;
     }
     double thrF = 2.6, thrH = 2.2, locality = 0.005, lambda = 0.5;     // M/main.cpp:55-59
@@ -142,6 +147,8 @@ int main(int argc, char** argv)
     int data_term = MultiH::DATA_TERM_REFERENCE;
     int tail_score = MultiH::TAIL_SCORE_COUNT;
     int tail_refit = 0, tail_polish = 0, model_polish = 0;
+    int model_reweight = 0, estimator_reweight = 0;
+    double model_reweight_scale = 0.0, estimator_reweight_scale = 0.0;
     int select_score = MultiH::SELECTION_SCORE_COUNT;
     int sampler = MultiH::PROPOSAL_UNIFORM, sampler_k = 32, sampler_u = 4;
     int proposals = MultiH::PROPOSAL_SOURCE_DLT, haf_members = 16, haf_stride = 1;
@@ -183,6 +190,25 @@ int main(int argc, char** argv)
                 return 2;
             }
             (k == "--polish" ? model_polish : tail_polish) = atoi(v);
+        }
+        else if (k == "--reweight" || k == "--estimator-reweight") {
+            // n | n:scale — a whole number of rounds in [0, 16], a scale in pixels > 0 (default: the homography threshold)
+            const std::string tv = v;
+            const size_t colon = tv.find(':');
+            const std::string nv = tv.substr(0, colon);
+            double scale = 0.0;
+            bool ok = !nv.empty() && nv.size() <= 2 && nv.find_first_not_of("0123456789") == std::string::npos && atoi(nv.c_str()) <= 16;
+            if (ok && colon != std::string::npos) {
+                char* end = nullptr;
+                scale = strtod(tv.c_str() + colon + 1, &end);
+                ok = end != tv.c_str() + colon + 1 && *end == '\0' && scale > 0.0 && scale <= 1e150;
+            }
+            if (!ok) {
+                std::cerr << k << ": n[:scale], n a whole number in [0, 16], scale a number of pixels > 0\n";
+                return 2;
+            }
+            (k == "--reweight" ? model_reweight : estimator_reweight) = atoi(nv.c_str());
+            (k == "--reweight" ? model_reweight_scale : estimator_reweight_scale) = scale;
         }
         else if (k == "--select-score") {
             if (std::string(v) == "count") select_score = MultiH::SELECTION_SCORE_COUNT;
@@ -389,6 +415,8 @@ int main(int argc, char** argv)
     multiH->SetTailRefit(tail_refit);
     multiH->SetTailPolish(tail_polish);
     multiH->SetModelPolish(model_polish);
+    multiH->SetModelReweight(model_reweight, model_reweight_scale);
+    multiH->SetEstimatorReweight(estimator_reweight, estimator_reweight_scale);
     multiH->SetSelectionScore(select_score);
     multiH->SetProposalSampler(sampler, sampler_k, sampler_u);
     multiH->SetProposalSource(proposals, haf_members, haf_stride);
