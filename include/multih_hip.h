@@ -473,6 +473,56 @@ MH_API int mh_reweight_homographies(mh_engine* e, const int* labels /* n */, con
                                     double c2, int rounds, double* H_out /* m x 9 */,
                                     double* gain /* m x 2: W of H_in, W of H_out; nullable */,
                                     int* info /* m x 4: members, support of H_out, rounds done, status; nullable */);
+/* Per label, one order statistic of its members' transfer errors under a model: the robust scale estimate the reweighted fit
+ * lacks (a median of a label's own residuals follows that label's noise, whatever the caller knows about it).  There is no
+ * counterpart in the reference, so this comment is the definition (tests/label_scale_numpy.py restates it).  One launch of one
+ * 256-thread workgroup per model (csrc/label_scale.hip, k_label_quantile): a radix select on the 64-bit pattern of the key.
+ *   Members     S_k = { i : labels[i] == k }, c = |S_k|; every other value (-1, >= m) belongs to nobody.
+ *   Key         of member i: d2, the forward transfer error under H[k] in the reference's operation order (M/MultiH.cpp:434-441),
+ *               always the forward error, whatever mh_set_residual_mode says; a NaN counts as +inf.  d2 is a sum of two squares:
+ *               never negative, never -0, so its 64-bit pattern orders like the number.
+ *   Rank        r = ((long long)(c - 1) * num) / den, integer division: num / den = 1/2 the lower median, 0/1 the minimum, 1/1
+ *               the maximum.
+ *   Result      d2_out[k] = the element at 0-based rank r of the ascending multiset of the keys: exact, and independent of any
+ *               evaluation order.  info[k] = (c, r, the number of members whose key is strictly smaller than d2_out[k], status).
+ *               status 1: c == 0 — d2_out[k] is the quiet NaN 0x7ff8000000000000, rank and below are 0.  There is no other
+ *               status: a model with entries that are not finite simply produces NaN keys, which count as +inf.
+ * MH_ERR_INVALID for a null engine, labels, H or d2_out, m outside [1, 65536], den outside [1, MH_QUANTILE_MAX_DEN], num outside
+ * [0, den]; MH_ERR_NOT_SET without correspondences.  It reads the points only and leaves the engine's state untouched, like
+ * mh_polish_homographies (its launch is timed in the MH_K_REESTIMATE slot).  Deterministic, so every rank of a sharded run gets the
+ * same result without an exchange. */
+#define MH_QUANTILE_MAX_DEN 65536
+MH_API int mh_label_residual_quantile(mh_engine* e, const int* labels /* n */, const double* H /* m x 9 */, int m,
+                                      int num, int den, double* d2_out /* m */,
+                                      int* info /* m x 4: members, rank, members strictly below the value, status; nullable */);
+/* mh_reweight_homographies with the scale taken from the data in every round (csrc/label_scale.hip, k_autoscale_reweight_h: all
+ * rounds in one launch of one workgroup per model; per round the selection passes of mh_label_residual_quantile, then wfit's
+ * three passes and solve as they stand).  Members, weight, sums and wfit are those of mh_reweight_homographies.
+ *   scale(H)    q = the order statistic of mh_label_residual_quantile (num, den) over the label's members under H; s = kappa2 * q
+ *               (one multiplication); c2 = s < c2_min ? c2_min : (s > c2_max ? c2_max : s).  s is never a NaN (q is not, and
+ *               kappa2 > 0 is finite); q = +inf or an overflow gives c2_max.
+ *   Rounds      cur = H_in[k], done = 0; for r = 1 .. rounds:
+ *     1. c2 = scale(cur);
+ *     2. cand = wfit(cur) with the weights d2 < c2 ? 1.0 - (d2 / c2) : 0.0; stop when it fails;
+ *     3. stop when cand equals cur bit for bit;
+ *     4. cur = cand, ++done.
+ *   Outputs     H_out[k] = cur — with done == 0 H_in[k]'s nine doubles unchanged; scale[k] = (scale(H_in[k]), scale(H_out[k]));
+ *               gain[k] = (W under H_in[k] at scale(H_in[k]), W under H_out[k] at scale(H_out[k])): the two W belong to DIFFERENT
+ *               scales and are NOT comparable as an objective (a model with a smaller median error gets a smaller c2 and may
+ *               get a smaller W); info[k] = (|S_k|, support of H_out[k] at its scale, done, status), statuses 1 (|S_k| < 4) and
+ *               2 (an entry of H_in[k] not finite) as in mh_reweight_homographies: with either, gain[k] = scale[k] = (0, 0), the
+ *               support and done 0 and H_out[k] H_in[k]'s bits.  rounds = 0 reports the scale, W and support of H_in.
+ *   Degenerate  with c2_min == c2_max == c2 the call is mh_reweight_homographies(.., c2, rounds, ..) bit for bit in H_out, gain
+ *               and info.
+ * MH_ERR_INVALID under the conditions of mh_reweight_homographies (without its c2), for num / den as in
+ * mh_label_residual_quantile, a kappa2 that is not finite or <= 0, bounds that are not finite or violate 0 < c2_min <= c2_max;
+ * MH_ERR_NOT_SET without correspondences.  H_out may be H_in.  Reads the points only; deterministic. */
+MH_API int mh_reweight_homographies_auto(mh_engine* e, const int* labels /* n */, const double* H_in /* m x 9 */, int m,
+                                         int num, int den, double kappa2, double c2_min, double c2_max, int rounds,
+                                         double* H_out /* m x 9 */,
+                                         double* gain  /* m x 2: W of H_in at its scale, W of H_out at its scale; nullable */,
+                                         double* scale /* m x 2: c2 under H_in, c2 under H_out; nullable */,
+                                         int* info     /* m x 4: members, support of H_out at its scale, rounds done, status; nullable */);
 /* Trial statistics of HomographyCompatibilityCheck (M/MultiH.cpp:128-196; host/merge_step.cpp ClusterMedian) for
  * `clusters` clusters of at least 19 points each.  pts_xyxy: the clusters' points back to back in cluster order, 4 doubles
  * each (x1 y1 x2 y2); cluster_begin[c] .. cluster_begin[c+1] (cluster_begin[0] = 0); per (cluster, trial): tri = the
@@ -689,6 +739,14 @@ MH_API int mh_set_estimator(mh_engine* e, int estimator);
  * Sticky per engine; mh_set_correspondences does not reset it.  MH_ERR_INVALID for a null engine, rounds outside
  * [0, MH_REWEIGHT_MAX_ROUNDS], or with rounds > 0 a c2 that is not finite or <= 0 (with rounds = 0 c2 is not looked at). */
 MH_API int mh_set_estimator_reweighting(mh_engine* e, int rounds, double c2);
+/* The same with the scale taken from the data: with rounds in [1, MH_REWEIGHT_MAX_ROUNDS] the MH_ESTIMATOR_DLT re-estimator is
+ * mh_reweight_homographies_auto(labels, H, Nh, num, den, kappa2, c2_min, c2_max, rounds) in place on the resident models;
+ * MH_BUF_LABEL_COUNTS receives |S_k|.  Of the two setters the last call decides which rule runs: mh_set_estimator_reweighting
+ * switches this rule off (whatever its rounds), this call replaces the fixed one; rounds = 0 switches reweighting off altogether.
+ * The other estimators, the key-30 refit of the greedy selections and their mode word ignore it, as they ignore the fixed setting.
+ * Sticky per engine.  MH_ERR_INVALID for a null engine, rounds outside [0, MH_REWEIGHT_MAX_ROUNDS], or with rounds > 0 the
+ * argument conditions of mh_reweight_homographies_auto (with rounds = 0 the other arguments are not looked at). */
+MH_API int mh_set_estimator_reweighting_auto(mh_engine* e, int rounds, int num, int den, double kappa2, double c2_min, double c2_max);
 /* GetHomographyHAFNonminimal for every label (M/MultiH.cpp:913-989 + the 1/lambda rescale of
  * Homography_RefineHAFCallback.h:33-34), or the 3-point fit under MH_ESTIMATOR_3PT, or the N-point DLT under MH_ESTIMATOR_DLT.
  * labels: -1..Nh-1 per point.  Updates the current model set in place (the data cost goes stale); H_out (nullable) receives a

@@ -31,8 +31,8 @@ SYMBOLS = [
     "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_propose_fund7", "mh_get_fund7_samples", "mh_estimate_fundamental_minimal", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons", "mh_refine_points",
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
     "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_propose_haf", "mh_get_haf_support", "mh_propose_3pt", "mh_set_residual_mode", "mh_score", "mh_score_msac", "mh_select_best_msac",
-    "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_select_greedy_msac", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_refit_homography", "mh_polish_homographies", "mh_reweight_homographies", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
-    "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_set_estimator_reweighting", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
+    "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_select_greedy_msac", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_refit_homography", "mh_polish_homographies", "mh_reweight_homographies", "mh_label_residual_quantile", "mh_reweight_homographies_auto", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
+    "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_set_estimator_reweighting", "mh_set_estimator_reweighting_auto", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
     "mh_profile_get", "mh_set_tuning",
 ]
 
@@ -521,6 +521,41 @@ class Engine:
                                                       _p(out, C.c_double), _p(gain, C.c_double), _p(info, C.c_int)))
         return out, gain, info
 
+    def label_residual_quantile(self, labels, H, num: int, den: int):
+        """mh_label_residual_quantile: per row of H (m x 9) the element at rank ((c - 1) * num) / den of the ascending forward
+        transfer errors of the c correspondences that carry its label (1/2: the lower median).  Returns (d2 [m] — the quiet
+        NaN for a label without members —, info int32 [m, 4] = members, rank, members strictly below the value, status)."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        if labels.size != self.n:
+            raise ValueError(f"labels: {labels.size} values for {self.n} correspondences")
+        H = np.ascontiguousarray(H, dtype=np.float64).reshape(-1, 9)
+        m = H.shape[0]
+        d2 = np.empty(m, dtype=np.float64)
+        info = np.empty((m, 4), dtype=np.int32)
+        self._check(self.lib.mh_label_residual_quantile(self._h, _p(labels, C.c_int), _p(H, C.c_double), m, int(num), int(den),
+                                                        _p(d2, C.c_double), _p(info, C.c_int)))
+        return d2, info
+
+    def reweight_homographies_auto(self, labels, H, num: int, den: int, kappa2: float, c2_min: float, c2_max: float, rounds: int):
+        """mh_reweight_homographies_auto: reweight_homographies with c2 = clamp(kappa2 * the (num, den) order statistic of the
+        label's errors under the model that stands, c2_min, c2_max), re-estimated in every round.  Returns (H_out [m, 9],
+        gain [m, 2] = W under H_in and under H_out, each at its own scale, scale [m, 2] = c2 under H_in and under H_out,
+        info int32 [m, 4] = members, support of H_out, rounds done, status)."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        if labels.size != self.n:
+            raise ValueError(f"labels: {labels.size} values for {self.n} correspondences")
+        H = np.ascontiguousarray(H, dtype=np.float64).reshape(-1, 9)
+        m = H.shape[0]
+        out = np.empty((m, 9), dtype=np.float64)
+        gain = np.empty((m, 2), dtype=np.float64)
+        scale = np.empty((m, 2), dtype=np.float64)
+        info = np.empty((m, 4), dtype=np.int32)
+        self._check(self.lib.mh_reweight_homographies_auto(self._h, _p(labels, C.c_int), _p(H, C.c_double), m, int(num), int(den),
+                                                           C.c_double(kappa2), C.c_double(c2_min), C.c_double(c2_max), int(rounds),
+                                                           _p(out, C.c_double), _p(gain, C.c_double), _p(scale, C.c_double),
+                                                           _p(info, C.c_int)))
+        return out, gain, scale, info
+
     def inlier_moments(self, thr2: float):
         m = self.model_count
         mo = np.empty((m, 6), dtype=np.float64)
@@ -608,6 +643,14 @@ class Engine:
         """mh_set_estimator_reweighting: under the "dlt" estimator, mh_reestimate and mh_labeling_step run `rounds` reweighted
         rounds at scale c2 from each label's standing model instead of the plain fit; 0 (default) off.  Sticky."""
         self._check(self.lib.mh_set_estimator_reweighting(self._h, int(rounds), C.c_double(c2)))
+
+    def set_estimator_reweighting_auto(self, rounds: int, num: int = 1, den: int = 2, kappa2: float = 1.0, c2_min: float = 1.0,
+                                       c2_max: float = 1.0):
+        """mh_set_estimator_reweighting_auto: as set_estimator_reweighting with the scale of every round taken from the label's
+        own errors (reweight_homographies_auto's rule); replaces the fixed rule, and set_estimator_reweighting replaces this
+        one; 0 rounds off.  Sticky."""
+        self._check(self.lib.mh_set_estimator_reweighting_auto(self._h, int(rounds), int(num), int(den), C.c_double(kappa2),
+                                                               C.c_double(c2_min), C.c_double(c2_max)))
 
     def set_data_term(self, name: str):
         """mh_set_data_term: "reference" (default) or "rising" (the cost grows with the error); sticky, marks the data cost stale."""

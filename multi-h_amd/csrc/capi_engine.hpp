@@ -219,7 +219,8 @@ struct mh_engine : ResidentBatch {                    // (e->m, e->origin, e->ha
     DevBuf<int> ph_labels, ph_info;           // mh_polish_homographies: the labels (n) and per model members, iterations, steps, status,
     DevBuf<double> ph_H, ph_cost;             // H_in and H_out (2 x m x 9), S before and after (m x 2)
     DevBuf<int> rw_labels, rw_info;           // mh_reweight_homographies: the labels (n) and per model members, support, rounds, status,
-    DevBuf<double> rw_H, rw_gain;             // H_in and H_out (2 x m x 9), W before and after (m x 2)
+    DevBuf<double> rw_H, rw_gain;             // H_in and H_out (2 x m x 9), W before and after (m x 2); mh_reweight_homographies_auto: then the
+                                              //   scales (m x 2); mh_label_residual_quantile: the labels, H, d2_out in rw_gain, info
     DevBuf<double> moments, min_eig;
     DevBuf<double> cp_pts, cp_H, cp_out;     // mh_compat_trial_stats staging
     DevBuf<int> cp_begin, cp_tri;
@@ -299,6 +300,8 @@ struct mh_engine : ResidentBatch {                    // (e->m, e->origin, e->ha
     int estimator = MH_ESTIMATOR_HAF;        // mh_set_estimator: the re-estimator of mh_reestimate, mh_labeling_step and the key-30 refit
     int est_rw_rounds = 0;                   // mh_set_estimator_reweighting: > 0 = the MH_ESTIMATOR_DLT re-estimator runs that many reweighted rounds
     double est_rw_c2 = 0.0;                  //   at this scale from each label's standing model (reweight_h.hip) instead of the plain fit; sticky
+    bool est_rw_auto = false;                //   mh_set_estimator_reweighting_auto (the last of the two setters decides): the scale of each round is
+    AutoScale est_rw_scale{ 1, 2, 1.0, 1.0, 1.0 };   //   taken from the label's residuals by this rule (label_scale.hip)
     int data_term = MH_DATA_TERM_REFERENCE;  // mh_set_data_term: the data term of mh_data_cost, mh_cost_matrix and mh_labeling_step (changes results: not a tuning key)
     DevBuf<int> r3_scratch;                  // member lists of the 3-point re-estimator (reestimate3pt.hip)
     int tune_3pt_form = 0;                   // key 34 (measurement libraries): 0 by size, 1 the match loop, 2 the compacted member lists (reestimate3pt.hip)

@@ -365,6 +365,11 @@ namespace mhe {
 int launch_estimator(mh_engine* e, const int* labels_dev, int Nh, double* H_dev, int* counts_dev)
 {
     ScopedTimer t(e, MH_K_REESTIMATE);
+    if (e->estimator == MH_ESTIMATOR_DLT && e->est_rw_rounds > 0 && e->est_rw_auto) {   // mh_set_estimator_reweighting_auto: the same, the scale from the data
+        HIPCHK(launch_autoscale_reweight_h(e->pts(), labels_dev, H_dev, Nh, e->est_rw_scale, e->est_rw_rounds, H_dev, nullptr, nullptr,
+                                           nullptr, counts_dev, e->stream));
+        return MH_OK;
+    }
     if (e->estimator == MH_ESTIMATOR_DLT && e->est_rw_rounds > 0) {      // mh_set_estimator_reweighting: from each label's standing model, in place
         HIPCHK(launch_reweight_h(e->pts(), labels_dev, H_dev, Nh, e->est_rw_c2, e->est_rw_rounds, H_dev, nullptr, nullptr, counts_dev,
                                  e->stream));
@@ -410,6 +415,23 @@ int mh_set_estimator_reweighting(mh_engine* e, int rounds, double c2)
         return fail(MH_ERR_INVALID, "c2 is not a finite positive number");
     e->est_rw_rounds = rounds;
     e->est_rw_c2 = rounds > 0 ? c2 : 0.0;
+    e->est_rw_auto = false;                      // of the two setters the last call decides
+    return MH_OK;
+    });
+}
+
+int mh_set_estimator_reweighting_auto(mh_engine* e, int rounds, int num, int den, double kappa2, double c2_min, double c2_max)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (rounds < 0 || rounds > REWEIGHT_H_MAX_ROUNDS) return fail(MH_ERR_INVALID, "rounds outside [0, 16]");
+    const AutoScale a{ num, den, kappa2, c2_min, c2_max };
+    if (rounds > 0 && !autoscale_ok(a))
+        return fail(MH_ERR_INVALID, "num / den outside 0 <= num <= den <= 65536, kappa2 not finite and > 0, or bounds not finite with 0 < c2_min <= c2_max");
+    e->est_rw_rounds = rounds;
+    e->est_rw_c2 = 0.0;
+    e->est_rw_auto = rounds > 0;
+    if (rounds > 0) e->est_rw_scale = a;
     return MH_OK;
     });
 }

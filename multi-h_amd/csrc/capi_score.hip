@@ -543,6 +543,70 @@ int mh_reweight_homographies(mh_engine* e, const int* labels, const double* H_in
     });
 }
 
+int mh_label_residual_quantile(mh_engine* e, const int* labels, const double* H, int m, int num, int den, double* d2_out, int* info)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (!labels) return fail(MH_ERR_INVALID, "null labels");
+    if (!H || !d2_out) return fail(MH_ERR_INVALID, "null homographies or result");
+    if (m < 1 || m > REWEIGHT_H_MAX_MODELS) return fail(MH_ERR_INVALID, "m outside [1, 65536]");
+    if (den < 1 || den > LABEL_QUANTILE_MAX_DEN) return fail(MH_ERR_INVALID, "den outside [1, 65536]");
+    if (num < 0 || num > den) return fail(MH_ERR_INVALID, "num outside [0, den]");
+    int rc = require_points(e);
+    if (rc) return rc;
+    const size_t mm = (size_t)m;
+    HIPCHK(e->rw_labels.reserve(e->n));
+    HIPCHK(e->rw_H.reserve(18 * mm));
+    HIPCHK(e->rw_gain.reserve(4 * mm));
+    HIPCHK(e->rw_info.reserve(4 * mm));
+    HIPCHK(hipMemcpyAsync(e->rw_labels.p, labels, sizeof(int) * (size_t)e->n, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->rw_H.p, H, sizeof(double) * 9 * mm, hipMemcpyHostToDevice, e->stream));
+    {
+        ScopedTimer t(e, MH_K_REESTIMATE);        // (the per-label kernels share this slot)
+        HIPCHK(launch_label_quantile(e->pts(), e->rw_labels.p, e->rw_H.p, m, num, den, e->rw_gain.p, e->rw_info.p, e->stream));
+    }
+    HIPCHK(hipMemcpyAsync(d2_out, e->rw_gain.p, sizeof(double) * mm, hipMemcpyDeviceToHost, e->stream));
+    if (info) HIPCHK(hipMemcpyAsync(info, e->rw_info.p, sizeof(int) * 4 * mm, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MH_OK;
+    });
+}
+
+int mh_reweight_homographies_auto(mh_engine* e, const int* labels, const double* H_in, int m, int num, int den, double kappa2,
+                                  double c2_min, double c2_max, int rounds, double* H_out, double* gain, double* scale, int* info)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (!labels) return fail(MH_ERR_INVALID, "null labels");
+    if (!H_in || !H_out) return fail(MH_ERR_INVALID, "null homographies");
+    if (m < 1 || m > REWEIGHT_H_MAX_MODELS) return fail(MH_ERR_INVALID, "m outside [1, 65536]");
+    if (rounds < 0 || rounds > REWEIGHT_H_MAX_ROUNDS) return fail(MH_ERR_INVALID, "rounds outside [0, 16]");
+    const AutoScale a{ num, den, kappa2, c2_min, c2_max };
+    if (!autoscale_ok(a))
+        return fail(MH_ERR_INVALID, "num / den outside 0 <= num <= den <= 65536, kappa2 not finite and > 0, or bounds not finite with 0 < c2_min <= c2_max");
+    int rc = require_points(e);
+    if (rc) return rc;
+    const size_t mm = (size_t)m;
+    HIPCHK(e->rw_labels.reserve(e->n));
+    HIPCHK(e->rw_H.reserve(18 * mm));
+    HIPCHK(e->rw_gain.reserve(4 * mm));          // gain (m x 2), then scale (m x 2)
+    HIPCHK(e->rw_info.reserve(4 * mm));
+    HIPCHK(hipMemcpyAsync(e->rw_labels.p, labels, sizeof(int) * (size_t)e->n, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->rw_H.p, H_in, sizeof(double) * 9 * mm, hipMemcpyHostToDevice, e->stream));
+    {
+        ScopedTimer t(e, MH_K_REESTIMATE);
+        HIPCHK(launch_autoscale_reweight_h(e->pts(), e->rw_labels.p, e->rw_H.p, m, a, rounds, e->rw_H.p + 9 * mm, e->rw_gain.p,
+                                           e->rw_gain.p + 2 * mm, e->rw_info.p, nullptr, e->stream));
+    }
+    HIPCHK(hipMemcpyAsync(H_out, e->rw_H.p + 9 * mm, sizeof(double) * 9 * mm, hipMemcpyDeviceToHost, e->stream));
+    if (gain) HIPCHK(hipMemcpyAsync(gain, e->rw_gain.p, sizeof(double) * 2 * mm, hipMemcpyDeviceToHost, e->stream));
+    if (scale) HIPCHK(hipMemcpyAsync(scale, e->rw_gain.p + 2 * mm, sizeof(double) * 2 * mm, hipMemcpyDeviceToHost, e->stream));
+    if (info) HIPCHK(hipMemcpyAsync(info, e->rw_info.p, sizeof(int) * 4 * mm, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MH_OK;
+    });
+}
+
 int mh_inlier_moments(mh_engine* e, double thr2, double* moments, double* min_eig)
 {
     return guarded([&]() -> int {

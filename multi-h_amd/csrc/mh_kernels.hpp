@@ -136,6 +136,21 @@ constexpr int REWEIGHT_H_MAX_MODELS = 65536;     // of a call of mh_reweight_hom
 hipError_t launch_reweight_h(const Points& p, const int* labels, const double* H_in, int m, double c2, int rounds, double* H_out,
                              double* gain, int* info, int* counts, hipStream_t s);
 
+// --- label_scale.hip: per label, one order statistic of its members' forward transfer errors (mh_label_residual_quantile), and
+// the reweighted rounds of reweight_h.hip with c2 = clamp(kappa2 * that statistic under the model that stands) re-estimated in
+// every round, all rounds in one launch (mh_reweight_homographies_auto; the MH_ESTIMATOR_DLT re-estimator under
+// mh_set_estimator_reweighting_auto).  One workgroup per model ---
+constexpr int LABEL_QUANTILE_MAX_DEN = 65536;
+struct AutoScale { int num, den; double kappa2, c2_min, c2_max; };          // rank ((c - 1) * num) / den; c2 in [c2_min, c2_max]
+bool autoscale_ok(const AutoScale& a);           // num / den in range, kappa2 finite and > 0, 0 < c2_min <= c2_max finite
+// labels: p.n ints on the device; H: m x 9 doubles; d2_out: m doubles; info: m x 4 ints (members, rank, members strictly below
+// the value, status), nullable
+hipError_t launch_label_quantile(const Points& p, const int* labels, const double* H, int m, int num, int den, double* d2_out,
+                                 int* info, hipStream_t s);
+// as launch_reweight_h; scale: m x 2 doubles (c2 under H_in, c2 under H_out), nullable
+hipError_t launch_autoscale_reweight_h(const Points& p, const int* labels, const double* H_in, int m, const AutoScale& a, int rounds,
+                                       double* H_out, double* gain, double* scale, int* info, int* counts, hipStream_t s);
+
 // --- datacost.hip -----------------------------------------------------------
 // the data cost of every model against every point, int32, model-major with pitch ldc (datacost.hip)
 inline long long cost_ld(int n) { return ((long long)n + 31) & ~31ll; }

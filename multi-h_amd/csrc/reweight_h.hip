@@ -30,9 +30,6 @@ namespace {
 
 constexpr int RW_HEAD = 7;                       // pass 1's columns: four weighted coordinate sums, W, members, support
 
-// the weight of a member at squared transfer error d2: one IEEE division, one subtraction; 0 at and beyond c2 and for a NaN
-__device__ __forceinline__ double reweight_w(double d2, double c2) { return d2 < c2 ? 1.0 - (d2 / c2) : 0.0; }
-
 } // namespace
 
 // H_in, H_out: m x 9 (may be the same array: a workgroup reads its row before it writes it); gain: m x 2 (W of H_in, W of

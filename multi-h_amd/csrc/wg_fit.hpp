@@ -1,5 +1,5 @@
 // wg_fit.hpp — what the per-model fit kernels share: k_fund_refit, k_moments, k_haf_reestimate, k_3pt_reestimate, k_refit_h,
-// k_polish_h, k_dlt_reestimate and k_reweight_h.  One 256-thread workgroup per model, strided passes over the points, thread 0 solves.
+// k_polish_h, k_dlt_reestimate, k_reweight_h and k_autoscale_reweight_h (k_label_quantile: the member loop).  One 256-thread workgroup per model, strided passes over the points, thread 0 solves.
 //
 // The order of every FP64 sum, stated here once: thread t adds its members t, t + 256, ... in ascending index from 0.0, then
 // the binary tree v[t] += v[t + s], s = 128 .. 1, over the workgroup's LDS buffer (wg_tree).  The twins (oracle/mh_oracle.cpp
@@ -99,6 +99,10 @@ __device__ __forceinline__ void hartley_centroids(const double* sums, int c, dou
     __syncthreads();
     hartley_get_centroids(par, hn);
 }
+
+// The weight of a member at squared transfer error d2 (k_reweight_h, k_autoscale_reweight_h): one IEEE division, one
+// subtraction; 0 at and beyond c2 and for a NaN.
+__device__ __forceinline__ double reweight_w(double d2, double c2) { return d2 < c2 ? 1.0 - (d2 / c2) : 0.0; }
 
 // ... weighted: the four sums of w * coordinate and W, the sum of the weights
 __device__ __forceinline__ void hartley_centroids_w(const double* sums, double W, double* par, int t, Hartley& hn)

@@ -5,6 +5,7 @@
 #include "MultiH.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <chrono>
 #include <climits>
 #include <cmath>
@@ -40,6 +41,8 @@
 // ... and for the reweighted refits (SetModelReweight, SetEstimatorReweight): the same.
 #pragma weak mh_reweight_homographies
 #pragma weak mh_set_estimator_reweighting
+#pragma weak mh_reweight_homographies_auto
+#pragma weak mh_set_estimator_reweighting_auto
 // ... and for the selection ranked by weight (SetSelectionScore): without its entry point that mode fails with a message.
 #pragma weak mh_select_greedy_msac
 // ... and for the HAF proposals (SetProposalSource): without its entry point that source fails with a message.
@@ -430,6 +433,40 @@ bool MultiH::Run(bool points_only)
             return false;
         }
     }
+    // ... or reweighted rounds whose scale follows each label's own residuals (SetModelReweightAuto, SetEstimatorReweightAuto)
+    if (model_reweight_auto < 0 || model_reweight_auto > 16 || estimator_reweight_auto < 0 || estimator_reweight_auto > 16) {
+        std::cerr << "Error: self-scaled reweighting rounds " << model_reweight_auto << " (final) / " << estimator_reweight_auto
+                  << " (estimator) outside [0, 16]\n";
+        return false;
+    }
+    if (!(model_reweight_kappa >= 0.0) || !(estimator_reweight_kappa >= 0.0) || model_reweight_kappa > 1e150 ||
+        estimator_reweight_kappa > 1e150) {
+        std::cerr << "Error: self-scaled reweighting kappa " << model_reweight_kappa << " (final) / " << estimator_reweight_kappa
+                  << " (estimator) is not a finite number >= 0\n";
+        return false;
+    }
+    if ((model_reweight > 0 && model_reweight_auto > 0) || (estimator_reweight > 0 && estimator_reweight_auto > 0)) {
+        std::cerr << "Error: both the fixed and the self-scaled reweighting are set for the "
+                  << (model_reweight > 0 && model_reweight_auto > 0 ? "final refit" : "estimator") << "; choose one\n";
+        return false;
+    }
+    if (model_reweight_auto > 0 && !mh_reweight_homographies_auto) {
+        std::cerr << "Error: the engine library has no self-scaled reweighted refit (mh_reweight_homographies_auto)\n";
+        return false;
+    }
+    {
+        // set behind the fixed setting, and only with rounds: of the engine's two setters the last call decides
+        const int rw = est == MH_ESTIMATOR_DLT ? estimator_reweight_auto : 0;
+        if (rw > 0) {
+            if (!mh_set_estimator_reweighting_auto) {
+                std::cerr << "Error: the engine library has no self-scaled reweighted estimator (mh_set_estimator_reweighting_auto)\n";
+                return false;
+            }
+            if (!Check(mh_set_estimator_reweighting_auto(engine, rw, 1, 2, AutoKappa2(estimator_reweight_kappa), DBL_MIN, AutoScaleMax()),
+                       "mh_set_estimator_reweighting_auto"))
+                return false;
+        }
+    }
     // how ProposeModels ranks a batch (INIT_STABLE_SETS proposes nothing: the mode is not looked at)
     if (init_mode != INIT_STABLE_SETS) {
         if (selection_score != SELECTION_SCORE_COUNT && selection_score != SELECTION_SCORE_MSAC) {
@@ -647,7 +684,7 @@ bool MultiH::Run(bool points_only)
         labeling.resize(src_points.size(), -1);
         cluster_homographies.resize(0);
         HandleDegenerateCase();
-    } else if (model_reweight > 0 || model_polish > 0) {
+    } else if (model_reweight > 0 || model_reweight_auto > 0 || model_polish > 0) {
         // every cluster's homography refitted (reweighted rounds, then the polish) over its labelled (refined) correspondences:
         // the engine still holds them
         const int nh = static_cast<int>(cluster_homographies.size());
@@ -666,6 +703,11 @@ bool MultiH::Run(bool points_only)
                        "mh_reweight_homographies"))
                 return false;
         }
+        if (model_reweight_auto > 0 &&
+            !Check(mh_reweight_homographies_auto(engine, labeling.data(), H.data(), nh, 1, 2, AutoKappa2(model_reweight_kappa), DBL_MIN,
+                                                 AutoScaleMax(), model_reweight_auto, H.data(), nullptr, nullptr, nullptr),
+                   "mh_reweight_homographies_auto"))
+            return false;
         if (model_polish > 0 &&
             !Check(mh_polish_homographies(engine, labeling.data(), H.data(), nh, model_polish, H.data(), nullptr, nullptr),
                    "mh_polish_homographies"))
@@ -1319,6 +1361,12 @@ extern "C" __attribute__((visibility("default")))
 void mhh_set_model_reweight(int rounds) { g_model_reweight = rounds; }
 extern "C" __attribute__((visibility("default")))
 void mhh_set_estimator_reweight(int rounds) { g_estimator_reweight = rounds; }
+// MultiH::SetModelReweightAuto and MultiH::SetEstimatorReweightAuto (kappa: the class default) the same way
+static int g_model_reweight_auto = -1, g_estimator_reweight_auto = -1;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_model_reweight_auto(int rounds) { g_model_reweight_auto = rounds; }
+extern "C" __attribute__((visibility("default")))
+void mhh_set_estimator_reweight_auto(int rounds) { g_estimator_reweight_auto = rounds; }
 // MultiH::SetEstimator (-1: leave as is, the class default) and MultiH::SetEpipolarFree for the next mhh_run_process calls
 static int g_estimator = -1, g_epipolar_free = 0;
 extern "C" __attribute__((visibility("default")))
@@ -1413,6 +1461,8 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     if (g_model_polish >= 0) mh.SetModelPolish(g_model_polish);
     if (g_model_reweight >= 0) mh.SetModelReweight(g_model_reweight);
     if (g_estimator_reweight >= 0) mh.SetEstimatorReweight(g_estimator_reweight);
+    if (g_model_reweight_auto >= 0) mh.SetModelReweightAuto(g_model_reweight_auto);
+    if (g_estimator_reweight_auto >= 0) mh.SetEstimatorReweightAuto(g_estimator_reweight_auto);
     if (g_selection_score >= 0) mh.SetSelectionScore(g_selection_score);
     if (g_estimator >= 0) mh.SetEstimator(g_estimator);
     mh.SetEpipolarFree(g_epipolar_free != 0);

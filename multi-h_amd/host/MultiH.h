@@ -184,6 +184,16 @@ public:
     // label's standing model and runs `rounds` reweighted rounds instead of the plain fit (mh_set_estimator_reweighting).  The
     // other estimators ignore it.  0 (default) off; rounds in [1, 16]; any other value makes Process() fail with a message.
     void SetEstimatorReweight(int rounds, double scale_px = 0) { estimator_reweight = rounds; estimator_reweight_scale = scale_px; }
+    // The same two with the scale taken from the data (mh_reweight_homographies_auto, mh_set_estimator_reweighting_auto): in every
+    // round c2 = kappa^2 * the lower median of the label's squared transfer errors under the model that stands, kept inside
+    // [DBL_MIN, the labeling's truncation threshold thr_hom^2 * 81 / 16 — beyond it the labeling would not have assigned the member].
+    // kappa = 0: kappa^2 = log2(100) — for two-dimensional Gaussian residuals d2 / sigma^2 is chi-squared with two degrees of
+    // freedom, median 2 ln 2 and 0.99 quantile 2 ln 100, so the default cuts where 1 % of a clean label's members lie.  With
+    // c2_min = DBL_MIN a label whose median error is 0 weighs only its exact fits, and keeps its model when they are fewer than
+    // four or reproduce it.  0 (default) off; rounds in [1, 16]; kappa finite and >= 0.  Asking for a fixed and a self-scaled
+    // final refit, or for both estimator settings, makes Process() fail with a message, as any other value does.
+    void SetModelReweightAuto(int rounds, double kappa = 0) { model_reweight_auto = rounds; model_reweight_kappa = kappa; }
+    void SetEstimatorReweightAuto(int rounds, double kappa = 0) { estimator_reweight_auto = rounds; estimator_reweight_kappa = kappa; }
     // How ProposeModels ranks the hypotheses of a batch — the initial batch, the iterative ones and the sharded route alike:
     // SELECTION_SCORE_COUNT (default) by inlier count (mh_select_greedy), SELECTION_SCORE_MSAC by the MSAC weight among the
     // hypotheses with at least min_inliers-or-8 inliers (mh_select_greedy_msac, include/multih_hip.h: the count makes a hypothesis
@@ -314,6 +324,11 @@ protected:
     int tail_polish = 0, model_polish = 0;
     int model_reweight = 0, estimator_reweight = 0;
     double model_reweight_scale = 0.0, estimator_reweight_scale = 0.0;
+    int model_reweight_auto = 0, estimator_reweight_auto = 0;
+    double model_reweight_kappa = 0.0, estimator_reweight_kappa = 0.0;
+    // the self-scaled rule's numbers: kappa^2 (kappa = 0: log2(100), the nearest double) and the upper bound of c2
+    static double AutoKappa2(double kappa) { return kappa > 0.0 ? kappa * kappa : 6.643856189774724; }
+    double AutoScaleMax() const { return threshold_homography * threshold_homography * 81.0 / 16.0; }
     int selection_score = SELECTION_SCORE_COUNT;
     int proposal_sampler = PROPOSAL_UNIFORM, proposal_sampler_k = 32, proposal_uniform_per_16 = 4;
     bool proposal_local_run = false;      // this Process() call proposes with the local sampler (its table is on the engine)

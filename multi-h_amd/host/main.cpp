@@ -41,6 +41,10 @@
 //                                n <= 16; scale in pixels, default thrH); runs in front of --polish
 //                  [--estimator-reweight n[:scale]]   the same rounds as the loop's re-estimator under --estimator dlt and
 //                                --no-epipolar (MultiH::SetEstimatorReweight; 0, the default, off)
+//                  [--reweight-auto n[:kappa]] [--estimator-reweight-auto n[:kappa]]   the same two with the scale of every round
+//                                taken from the data: kappa^2 times the lower median of the label's squared transfer errors
+//                                (MultiH::SetModelReweightAuto / SetEstimatorReweightAuto; default kappa^2 = log2(100)); an option
+//                                and its -auto twin, both with n > 0, are refused
 //                  [--select-score count|msac]   how the proposal batches are ranked (MultiH::SetSelectionScore): count, the default,
 //                                by inlier count (mh_select_greedy); msac by the MSAC weight among the hypotheses with enough
 //                                inliers (mh_select_greedy_msac)
@@ -131,7 +135,7 @@ int main(int argc, char** argv)
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
                      "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] [--f-estimator ls8|minimal] "
-                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--data-term reference|rising] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--reweight n[:scale]] [--estimator-reweight n[:scale]] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
+                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--data-term reference|rising] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--reweight n[:scale]] [--estimator-reweight n[:scale]] [--reweight-auto n[:kappa]] [--estimator-reweight-auto n[:kappa]] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
         return 2;
     }
     double thrF = 2.6, thrH = 2.2, locality = 0.005, lambda = 0.5;     // M/main.cpp:55-59
@@ -149,6 +153,8 @@ int main(int argc, char** argv)
     int tail_refit = 0, tail_polish = 0, model_polish = 0;
     int model_reweight = 0, estimator_reweight = 0;
     double model_reweight_scale = 0.0, estimator_reweight_scale = 0.0;
+    int model_reweight_auto = 0, estimator_reweight_auto = 0;
+    double model_reweight_kappa = 0.0, estimator_reweight_kappa = 0.0;
     int select_score = MultiH::SELECTION_SCORE_COUNT;
     int sampler = MultiH::PROPOSAL_UNIFORM, sampler_k = 32, sampler_u = 4;
     int proposals = MultiH::PROPOSAL_SOURCE_DLT, haf_members = 16, haf_stride = 1;
@@ -209,6 +215,26 @@ int main(int argc, char** argv)
             }
             (k == "--reweight" ? model_reweight : estimator_reweight) = atoi(nv.c_str());
             (k == "--reweight" ? model_reweight_scale : estimator_reweight_scale) = scale;
+        }
+        else if (k == "--reweight-auto" || k == "--estimator-reweight-auto") {
+            // n | n:kappa — a whole number of rounds in [0, 16], a factor kappa > 0 on the root of the label's median squared error
+            // (default: kappa^2 = log2(100))
+            const std::string tv = v;
+            const size_t colon = tv.find(':');
+            const std::string nv = tv.substr(0, colon);
+            double kappa = 0.0;
+            bool ok = !nv.empty() && nv.size() <= 2 && nv.find_first_not_of("0123456789") == std::string::npos && atoi(nv.c_str()) <= 16;
+            if (ok && colon != std::string::npos) {
+                char* end = nullptr;
+                kappa = strtod(tv.c_str() + colon + 1, &end);
+                ok = end != tv.c_str() + colon + 1 && *end == '\0' && kappa > 0.0 && kappa <= 1e150;
+            }
+            if (!ok) {
+                std::cerr << k << ": n[:kappa], n a whole number in [0, 16], kappa a number > 0\n";
+                return 2;
+            }
+            (k == "--reweight-auto" ? model_reweight_auto : estimator_reweight_auto) = atoi(nv.c_str());
+            (k == "--reweight-auto" ? model_reweight_kappa : estimator_reweight_kappa) = kappa;
         }
         else if (k == "--select-score") {
             if (std::string(v) == "count") select_score = MultiH::SELECTION_SCORE_COUNT;
@@ -288,6 +314,11 @@ int main(int argc, char** argv)
         }
         else if (k == "--stages") stages_path = v;
         else { std::cerr << "unknown option " << k << "\n"; return 2; }
+    }
+    if ((model_reweight > 0 && model_reweight_auto > 0) || (estimator_reweight > 0 && estimator_reweight_auto > 0)) {
+        const char* base = model_reweight > 0 && model_reweight_auto > 0 ? "--reweight" : "--estimator-reweight";
+        std::cerr << base << " and " << base << "-auto: one scale rule, not both\n";
+        return 2;
     }
 
     // --ranks N: fork ranks 1..N-1 now — no HIP call has been made yet — then every rank joins the communicator.  RCCL's
@@ -417,6 +448,8 @@ int main(int argc, char** argv)
     multiH->SetModelPolish(model_polish);
     multiH->SetModelReweight(model_reweight, model_reweight_scale);
     multiH->SetEstimatorReweight(estimator_reweight, estimator_reweight_scale);
+    multiH->SetModelReweightAuto(model_reweight_auto, model_reweight_kappa);
+    multiH->SetEstimatorReweightAuto(estimator_reweight_auto, estimator_reweight_kappa);
     multiH->SetSelectionScore(select_score);
     multiH->SetProposalSampler(sampler, sampler_k, sampler_u);
     multiH->SetProposalSource(proposals, haf_members, haf_stride);
