@@ -538,6 +538,40 @@ MH_API int mh_compat_trial_stats(mh_engine* e, const double* pts_xyxy, const int
  * (host/merge_step.cpp, Homography3PTLinear).  H_out (clusters x trials x 9) / ok_out (clusters x trials): nullable, the fits. */
 MH_API int mh_compat_trial_stats_fit(mh_engine* e, const double* pts_xyxy, const int* cluster_begin, int clusters, const int* tri,
                               const double F[9], int trials, double* stats_out, double* H_out, unsigned char* ok_out);
+/* The compatibility check WITHOUT F: per cluster the median over `trials` trials of the median forward transfer error of the
+ * cluster's other points under a 4-point DLT fit to four random members.  There is no reference counterpart (the reference's
+ * trials are 3-point fits with F, above); this comment is the definition.
+ *   Input       pts_xyxy and cluster_begin as in mh_compat_trial_stats: the clusters' points back to back, four doubles each;
+ *               cluster c = [begin[c], begin[c+1]), begin[0] == 0.  nc = its size, b0 = begin[c].  Independent of the resident
+ *               correspondences.
+ *   Tuple       trial t of cluster c is hypothesis m = c * trials + t of the call, with the counter first + m.  Its four local
+ *               positions follow the uniform rule of mh_propose_dlt4 over nc indices: draw j = 0, 1, .. gives
+ *               r = splitmix64(seed + (counter << 8) + j) and the position ((r >> 32) * nc) >> 32; a position already in the
+ *               tuple is rejected; at most 64 draws; slots still empty then take the first position.  idx_out holds
+ *               b0 + position (positions in the concatenated array).
+ *   Fit         mh_propose_dlt4's normalised 4-point DLT on those four points, the same operations in the same order: unit
+ *               Frobenius norm, h33 >= 0.  A result that is not finite stays as it is.
+ *   Trial value a member is left out if and only if its local position equals one of the four tuple entries; rest = the number
+ *               of the others (nc - 4 unless the tuple holds repeats).  The key of a member is its forward transfer error d2
+ *               under the trial's H, in the reference's operation order (M/MultiH.cpp:434-441: the engine's residual); a NaN key
+ *               counts as +inf (0x7ff0000000000000), as in mh_label_residual_quantile.  trial_out[c][t] = the key at 0-based
+ *               rank (rest - 1) / 2 of the ascending multiset (the lower median): exact, independent of any evaluation order.
+ *   Cluster     medians_out[c] = the element at 0-based rank (trials - 1) / 2 of the ascending multiset of the cluster's trial
+ *               values.
+ * MH_ERR_INVALID for a null engine, pts_xyxy, cluster_begin or medians_out; clusters < 1; a cluster_begin that does not start at
+ * 0 or is not non-decreasing; a cluster of fewer than MH_COMPAT_DLT_MIN_POINTS points; trials outside
+ * [1, MH_COMPAT_DLT_MAX_TRIALS]; first < 0; clusters * trials > 2^22.
+ * The call reads nothing of the engine's state and changes none of it: the resident model set, samples, counts, weights, data
+ * cost, graph and prefetch queue stay untouched.  Deterministic, so the ranks of a sharded run need no exchange.  Three launches
+ * on the engine's stream, timed in the slots MH_K_DLT4 (the fits), MH_K_SCORE (the trial values) and MH_K_REESTIMATE (the
+ * cluster values). */
+enum { MH_COMPAT_DLT_MIN_POINTS = 5, MH_COMPAT_DLT_MAX_TRIALS = 4096 };
+MH_API int mh_compat_dlt_medians(mh_engine* e, const double* pts_xyxy, const int* cluster_begin, int clusters,
+                                 unsigned long long seed, long long first, int trials,
+                                 double* medians_out   /* clusters */,
+                                 double* trial_out     /* clusters x trials, nullable */,
+                                 double* H_out         /* clusters x trials x 9, nullable */,
+                                 int* idx_out          /* clusters x trials x 4, nullable */);
 /* ---- multi-GPU transport (one process per GPU, hypotheses sharded, correspondences replicated) ------
  * The reference is a single process; the one exchange north_star adds is an all-gather of per-model inlier scores.
  * The engine calls the transport with DEVICE pointers: send `bytes_per_rank` bytes, receive world * bytes_per_rank in

@@ -31,7 +31,7 @@ SYMBOLS = [
     "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_propose_fund7", "mh_get_fund7_samples", "mh_estimate_fundamental_minimal", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons", "mh_refine_points",
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
     "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_propose_haf", "mh_get_haf_support", "mh_propose_3pt", "mh_set_residual_mode", "mh_score", "mh_score_msac", "mh_select_best_msac",
-    "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_select_greedy_msac", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_refit_homography", "mh_polish_homographies", "mh_reweight_homographies", "mh_label_residual_quantile", "mh_reweight_homographies_auto", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
+    "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_select_greedy_msac", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_refit_homography", "mh_polish_homographies", "mh_reweight_homographies", "mh_label_residual_quantile", "mh_reweight_homographies_auto", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_compat_dlt_medians", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
     "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_set_estimator_reweighting", "mh_set_estimator_reweighting_auto", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
     "mh_profile_get", "mh_set_tuning",
 ]
@@ -607,6 +607,24 @@ class Engine:
         self._check(self.lib.mh_compat_trial_stats_fit(self._h, _p(pts, C.c_double), _p(begin, C.c_int), clusters, _p(tri, C.c_int),
                                                        _p(F, C.c_double), trials, _p(out, C.c_double), _p(H, C.c_double), _p(ok, C.c_ubyte)))
         return out, H, ok
+
+    def compat_dlt_medians(self, pts_xyxy, cluster_begin, seed: int, first: int, trials: int):
+        """mh_compat_dlt_medians: the compatibility check without F.  Per cluster `trials` 4-point DLT fits to random members,
+        each trial's lower median of the other members' forward transfer errors, and the lower median of those.  Returns
+        (medians [clusters], trial values [clusters, trials], H [clusters, trials, 9], idx int32 [clusters, trials, 4] —
+        positions in the concatenated points)."""
+        pts = _f64(pts_xyxy).reshape(-1, 4)
+        begin = np.ascontiguousarray(cluster_begin, dtype=np.int32).reshape(-1)
+        clusters, trials = begin.size - 1, int(trials)
+        shape = (max(clusters, 0), max(trials, 0))
+        med = np.empty(shape[0], dtype=np.float64)
+        val = np.empty(shape, dtype=np.float64)
+        H = np.empty(shape + (9,), dtype=np.float64)
+        idx = np.empty(shape + (4,), dtype=np.int32)
+        self._check(self.lib.mh_compat_dlt_medians(self._h, _p(pts, C.c_double), _p(begin, C.c_int), clusters, C.c_ulonglong(seed),
+                                                   C.c_longlong(first), trials, _p(med, C.c_double), _p(val, C.c_double),
+                                                   _p(H, C.c_double), _p(idx, C.c_int)))
+        return med, val, H, idx
 
     def expand_stats(self):
         st = (C.c_longlong * 24)()

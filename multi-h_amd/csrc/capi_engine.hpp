@@ -224,6 +224,7 @@ struct mh_engine : ResidentBatch {                    // (e->m, e->origin, e->ha
     DevBuf<double> moments, min_eig;
     DevBuf<double> cp_pts, cp_H, cp_out;     // mh_compat_trial_stats staging
     DevBuf<int> cp_begin, cp_tri;
+    DevBuf<int> cp_idx;                      // mh_compat_dlt_medians: the trials' 4-tuples (it stages its points in cp_pts, its fits in cp_H, its values in cp_out)
     DevBuf<unsigned char> cp_ok;
     // greedy selection (select.hip): two candidate lists, control words, exchange buffers
     DevBuf<int> sel_orig[2], sel_counts, sel_carried[2], sel_left, sel_rec, sel_scores, sel_gathered;     // (sel_carried / sel_left: r05, the decremental rounds of mh_select_greedy)

@@ -237,6 +237,59 @@ int mh_compat_trial_stats_fit(mh_engine* e, const double* pts_xyxy, const int* c
     });
 }
 
+// The check without F (the definition: include/multih_hip.h).  The packed points are staged as a structure of arrays (x1 | y1 |
+// x2 | y2 in cp_pts), which is what k_dlt4 reads; nothing but the cp_ staging buffers is written.
+int mh_compat_dlt_medians(mh_engine* e, const double* pts_xyxy, const int* cluster_begin, int clusters, unsigned long long seed,
+                          long long first, int trials, double* medians_out, double* trial_out, double* H_out, int* idx_out)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (!pts_xyxy || !cluster_begin || !medians_out) return fail(MH_ERR_INVALID, "null argument");
+    if (clusters < 1) return fail(MH_ERR_INVALID, "no cluster");
+    if (trials < 1 || trials > MH_COMPAT_DLT_MAX_TRIALS) return fail(MH_ERR_INVALID, "trials outside [1, MH_COMPAT_DLT_MAX_TRIALS]");
+    if (first < 0) return fail(MH_ERR_INVALID, "negative first counter");
+    if ((long long)clusters * trials > (1ll << 22)) return fail(MH_ERR_INVALID, "more than 2^22 trials in one call");
+    if (cluster_begin[0] != 0) return fail(MH_ERR_INVALID, "cluster_begin[0] must be 0");
+    for (int c = 0; c < clusters; ++c) {
+        if (cluster_begin[c + 1] < cluster_begin[c]) return fail(MH_ERR_INVALID, "cluster_begin must not decrease");
+        if (cluster_begin[c + 1] - cluster_begin[c] < MH_COMPAT_DLT_MIN_POINTS)
+            return fail(MH_ERR_INVALID, "a cluster of fewer than MH_COMPAT_DLT_MIN_POINTS points: the caller keeps those itself");
+    }
+    const size_t total = (size_t)cluster_begin[clusters], ct = (size_t)clusters * (size_t)trials;
+    std::vector<double> soa(4 * total);                                   // (alive until the copies below have been waited for)
+    for (size_t i = 0; i < total; ++i)
+        for (int k = 0; k < 4; ++k) soa[k * total + i] = pts_xyxy[4 * i + k];
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(e->cp_pts.reserve(4 * total)); HIPCHK(e->cp_begin.reserve(clusters + 1)); HIPCHK(e->cp_idx.reserve(4 * ct));
+    HIPCHK(e->cp_H.reserve(9 * ct)); HIPCHK(e->cp_out.reserve(ct + clusters));
+    const double* x1 = e->cp_pts.p;
+    const double *y1 = x1 + total, *x2 = x1 + 2 * total, *y2 = x1 + 3 * total;
+    double* trial_dev = e->cp_out.p;
+    double* med_dev = e->cp_out.p + ct;
+    HIPCHK(hipMemcpyAsync(e->cp_pts.p, soa.data(), sizeof(double) * 4 * total, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->cp_begin.p, cluster_begin, sizeof(int) * (clusters + 1), hipMemcpyHostToDevice, e->stream));
+    {
+        ScopedTimer t(e, MH_K_DLT4);
+        HIPCHK(launch_dlt4_segments(x1, y1, x2, y2, (int)total, e->cp_begin.p, trials, seed, first, (int)ct, e->cp_idx.p, e->cp_H.p,
+                                    e->stream));
+    }
+    {
+        ScopedTimer t(e, MH_K_SCORE);
+        HIPCHK(launch_compat_median4(x1, y1, x2, y2, e->cp_begin.p, clusters, e->cp_idx.p, e->cp_H.p, trials, trial_dev, e->stream));
+    }
+    {
+        ScopedTimer t(e, MH_K_REESTIMATE);
+        HIPCHK(launch_compat_cluster_median(trial_dev, clusters, trials, med_dev, e->stream));
+    }
+    HIPCHK(hipMemcpyAsync(medians_out, med_dev, sizeof(double) * clusters, hipMemcpyDeviceToHost, e->stream));
+    if (trial_out) HIPCHK(hipMemcpyAsync(trial_out, trial_dev, sizeof(double) * ct, hipMemcpyDeviceToHost, e->stream));
+    if (H_out) HIPCHK(hipMemcpyAsync(H_out, e->cp_H.p, sizeof(double) * 9 * ct, hipMemcpyDeviceToHost, e->stream));
+    if (idx_out) HIPCHK(hipMemcpyAsync(idx_out, e->cp_idx.p, sizeof(int) * 4 * ct, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MH_OK;
+    });
+}
+
 int mh_data_cost(mh_engine* e, int* cost)
 {
     return guarded([&]() -> int {

@@ -14,9 +14,14 @@
 // host, compiled with -ffp-contract=off: the statistics are bit-identical to std::nth_element / partial_sort on the
 // host's values.  Integer/byte work apart from 30 FP64 operations per (point, trial, pass); latency bound at these
 // sizes (501 x 6 workgroups of a few thousand points), reported as milliseconds per check.
+//
+// The check WITHOUT F (mh_compat_dlt_medians) stands at the end of the file: its trials are k_dlt4's 4-point fits
+// (dlt4.hip, the segment sampler), k_compat_median4 takes one rank per trial and k_compat_cluster_median one rank per cluster,
+// both through wg_select.hpp.
 
 #include "mh_kernels.hpp"
 #include "mh_device.hpp"
+#include "wg_select.hpp"
 
 namespace mh {
 
@@ -193,6 +198,70 @@ hipError_t launch_compat_select(const double* pts, const int* begin, int cluster
     if (clusters <= 0 || trials <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_compat_select, dim3((unsigned)clusters * (unsigned)trials), dim3(256), 0, s, pts, begin, tri, H, ok,
                        trials, out);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// mh_compat_dlt_medians (include/multih_hip.h): the trials of the compatibility check without F.  x1 .. y2: the clusters' points
+// back to back (structure of arrays); begin[c] .. begin[c + 1]: cluster c, at least 5 points; per (cluster, trial): idx = the four
+// positions in the packed arrays that k_dlt4's segment sampler drew, H = its fit (any bits: a fit that is not finite gives keys
+// that are NaN -> +inf, and the selection returns +inf).
+//
+// k_compat_median4: one workgroup per (cluster, trial).  The members are the cluster's positions that are none of the tuple's
+// four (a tuple with repeats leaves out fewer); the key is the pattern of fwd_d2 under the trial's H, recomputed in every pass,
+// NaN -> +inf; the result is the key at rank (members - 1) / 2: at most eight byte passes (wg_select.hpp), no statistics pass
+// and no stale entries — the rule is this feature's own, not the reference's buffer.
+// k_compat_cluster_median: one workgroup per cluster, the same selection over the cluster's `trials` trial values.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_compat_median4(const double* __restrict__ x1, const double* __restrict__ y1, const double* __restrict__ x2,
+                 const double* __restrict__ y2, const int* __restrict__ begin, const int* __restrict__ idx,
+                 const double* __restrict__ H, int trials, double* __restrict__ trial_out)
+{
+    const int c = (int)blockIdx.x / trials;
+    const int t = (int)threadIdx.x;
+    const int b0 = begin[c], nc = begin[c + 1] - b0;
+    __shared__ unsigned s_hist[256];
+    __shared__ int s_sel[5];
+    const double* h = H + 9 * (size_t)blockIdx.x;
+    const double h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3], h4 = h[4], h5 = h[5], h6 = h[6], h7 = h[7], h8 = h[8];
+    const int* tu = idx + 4 * (size_t)blockIdx.x;
+    const int t0 = tu[0], t1 = tu[1], t2 = tu[2], t3 = tu[3];          // positions in the packed arrays, like n below
+    auto members = [&](auto&& f) {
+        for (int n = b0 + t; n < b0 + nc; n += 256)
+            if (n != t0 && n != t1 && n != t2 && n != t3) f(n);
+    };
+    auto key_of = [&](int n) { return quantile_key(fwd_d2(h0, h1, h2, h3, h4, h5, h6, h7, h8, x1[n], y1[n], x2[n], y2[n])); };
+    const Quantile q = label_quantile(members, key_of, 1, 2, s_hist, s_sel, t);
+    if (t == 0) trial_out[blockIdx.x] = __longlong_as_double((long long)q.key);      // (members >= 1: nc >= 5)
+}
+
+__global__ void __launch_bounds__(256)
+k_compat_cluster_median(const double* __restrict__ trial, int trials, double* __restrict__ medians_out)
+{
+    const int t = (int)threadIdx.x;
+    __shared__ unsigned s_hist[256];
+    __shared__ int s_sel[5];
+    const double* v = trial + (size_t)blockIdx.x * (size_t)trials;
+    auto members = [&](auto&& f) { for (int n = t; n < trials; n += 256) f(n); };
+    auto key_of = [&](int n) { return quantile_key(v[n]); };
+    const Quantile q = label_quantile(members, key_of, 1, 2, s_hist, s_sel, t);
+    if (t == 0) medians_out[blockIdx.x] = __longlong_as_double((long long)q.key);
+}
+
+hipError_t launch_compat_median4(const double* x1, const double* y1, const double* x2, const double* y2, const int* begin,
+                                 int clusters, const int* idx, const double* H, int trials, double* trial_out, hipStream_t s)
+{
+    if (clusters <= 0 || trials <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_compat_median4, dim3((unsigned)clusters * (unsigned)trials), dim3(256), 0, s, x1, y1, x2, y2, begin, idx, H,
+                       trials, trial_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_compat_cluster_median(const double* trial, int clusters, int trials, double* medians_out, hipStream_t s)
+{
+    if (clusters <= 0 || trials <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_compat_cluster_median, dim3((unsigned)clusters), dim3(256), 0, s, trial, trials, medians_out);
     return hipGetLastError();
 }
 

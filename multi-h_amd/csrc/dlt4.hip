@@ -121,7 +121,7 @@ __device__ __forceinline__ void null9_vector(double (*W)[HPW], int hs, double g[
 // At most 72 VGPRs: that is what the resident residual sweep leaves free on every SIMD (5 waves of 88 registers), so a
 // workgroup of this kernel fits beside it on any compute unit (residual.hip, k_residual_resident).
 // SAMPLER / TABLE: DLT_SAMPLER_UNIFORM and no further argument, or DLT_SAMPLER_LOCAL and the table (const int* nbr, int k,
-// int uniform_per_16; sample4_by).  The local instantiation keeps the 72 registers: it fits beside the sweep like the uniform one.
+// int uniform_per_16; sample4_by); DLT_SAMPLER_SEGMENT (const int* cluster_begin, int trials, long long first) has the register form only.  The local instantiation keeps the 72 registers: it fits beside the sweep like the uniform one.
 template <int SAMPLER, class... TABLE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(72)))
 k_dlt4_lds(const double* __restrict__ x1, const double* __restrict__ y1,
@@ -129,7 +129,7 @@ k_dlt4_lds(const double* __restrict__ x1, const double* __restrict__ y1,
        unsigned long long seed, long long first, int M, int* __restrict__ idx_out,
        double* __restrict__ H_out, TABLE... table)
 {
-    static_assert(sizeof...(TABLE) == (SAMPLER == DLT_SAMPLER_LOCAL ? 3 : 0), "the local sampler takes nbr, k, uniform_per_16");
+    static_assert(sizeof...(TABLE) == dlt_sampler_args(SAMPLER), "the local sampler takes nbr, k, uniform_per_16; the segment sampler cluster_begin, trials, first");
     // Issue priority above the sweep's waves (priority 0).  A SIMD issues from its oldest ready wave first; beside five
     // resident sweep waves that always have an FP64 instruction ready, a wave of this kernel hardly ever issued: the DLT
     // of the next batch took the whole sweep and its own run time again after it, whatever the stream's priority and
@@ -340,7 +340,7 @@ k_dlt4(const double* __restrict__ x1, const double* __restrict__ y1,
        unsigned long long seed, long long first, int M, int* __restrict__ idx_out,
        double* __restrict__ H_out, TABLE... table)
 {
-    static_assert(sizeof...(TABLE) == (SAMPLER == DLT_SAMPLER_LOCAL ? 3 : 0), "the local sampler takes nbr, k, uniform_per_16");
+    static_assert(sizeof...(TABLE) == dlt_sampler_args(SAMPLER), "the local sampler takes nbr, k, uniform_per_16; the segment sampler cluster_begin, trials, first");
     __builtin_amdgcn_s_setprio(3);           // (as k_dlt4_lds; this form runs alone on the device, where it changes nothing)
     __shared__ double sN[4][9][HPW];         // column norms, then the null vector: 1.1 KB per wave
     __shared__ double sK[4][6][HPW];         // the normalisation, parked while the sweeps need the registers
@@ -834,6 +834,21 @@ hipError_t launch_dlt4(const Points& p, unsigned long long seed, long long first
     else
         hipLaunchKernelGGL(k_dlt4<DLT_SAMPLER_UNIFORM>, grid, dim3(256), 0, s, p.x1, p.y1,
                            p.x2, p.y2, p.n, seed, first, M, idx_out, H_out);
+    return hipGetLastError();
+}
+
+// The trials of mh_compat_dlt_medians: M = segments x trials hypotheses over the packed points (x1 .. y2: total each), hypothesis
+// m in segment m / trials = [begin[m / trials], begin[m / trials + 1]), every segment of at least 4 points; idx_out (M x 4)
+// holds positions in the packed arrays.  The register form with the segment sampler.
+hipError_t launch_dlt4_segments(const double* x1, const double* y1, const double* x2, const double* y2, int total, const int* begin,
+                                int trials, unsigned long long seed, long long first, int M, int* idx_out, double* H_out,
+                                hipStream_t s)
+{
+    if (M <= 0) return hipSuccess;
+    if (total < 4 || trials < 1 || !begin || !idx_out || !H_out) return hipErrorInvalidValue;
+    const int per_block = 4 * HPW;
+    hipLaunchKernelGGL((k_dlt4<DLT_SAMPLER_SEGMENT, const int*, int, long long>), dim3((M + per_block - 1) / per_block), dim3(256), 0,
+                       s, x1, y1, x2, y2, total, seed, first, M, idx_out, H_out, begin, trials, first);
     return hipGetLastError();
 }
 

@@ -81,6 +81,14 @@ hipError_t launch_compat_select(const double* pts /* total x 4 */, const int* be
 // the trials' 3-point homographies (GetHomography3PT without refinement, M/MultiH.cpp:154) — H: 9 doubles per (cluster, trial), ok: 1 where finite
 hipError_t launch_compat_fit(const double* pts, const int* begin, int clusters, const int* tri, const double F[9], int trials,
                              double* H, unsigned char* ok, hipStream_t s);
+// the check without F (mh_compat_dlt_medians): per (cluster, trial) the key at rank (rest - 1) / 2 of the forward transfer errors
+// of the cluster's points that are none of the trial's four (idx: positions in the packed structure-of-arrays points, as
+// launch_dlt4_segments writes them), NaN -> +inf; then per cluster the value at rank (trials - 1) / 2 of its trial values
+hipError_t launch_compat_median4(const double* x1, const double* y1, const double* x2, const double* y2, const int* begin /* clusters + 1 */,
+                                 int clusters, const int* idx /* clusters x trials x 4 */, const double* H /* clusters x trials x 9 */,
+                                 int trials, double* trial_out /* clusters x trials */, hipStream_t s);
+hipError_t launch_compat_cluster_median(const double* trial /* clusters x trials */, int clusters, int trials,
+                                        double* medians_out /* clusters */, hipStream_t s);
 
 // --- dlt4.hip ---------------------------------------------------------------
 // local.nbr != null: the neighbourhood-guided sampler (dlt4.hip, sample4_by) over the n x k table nbr, every entry in [0, n)
@@ -88,6 +96,11 @@ struct Dlt4Local { const int* nbr = nullptr; int k = 0; int uniform_per_16 = 0; 
 hipError_t launch_dlt4(const Points& p, unsigned long long seed, long long first, int M,
                        int* idx_out, double* H_out, hipStream_t s, int variant = 0 /* 1: the LDS-staged form */,
                        Dlt4Local local = Dlt4Local{});
+// the register form under the segment sampler (mh_sampler.hpp): M = segments x trials hypotheses over packed points, hypothesis m
+// draws inside segment m / trials = [begin[m / trials], begin[m / trials + 1]); idx_out: M x 4 positions in the packed arrays
+hipError_t launch_dlt4_segments(const double* x1, const double* y1, const double* x2, const double* y2, int total, const int* begin,
+                                int trials, unsigned long long seed, long long first, int M, int* idx_out, double* H_out,
+                                hipStream_t s);
 
 hipError_t launch_fund8(const Points& p, unsigned long long seed, long long first, int M,
                         int* idx_out /* M x 8 */, double* F_out, hipStream_t s);

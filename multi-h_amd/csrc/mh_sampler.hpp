@@ -43,7 +43,13 @@ __device__ __forceinline__ void sample4(unsigned long long seed, unsigned long l
 // j = 1 .. 63 proposes nbr[i0 k + (((r_j >> 32) k) >> 32)], taken unless it is already in the tuple; slots still empty after
 // draw 63 take out[0] (sample_tuple's exhaustion rule).  One more dependent load per index than the uniform form; the indices
 // live in named registers, not in an indexed array (no scratch).
-constexpr int DLT_SAMPLER_UNIFORM = 0, DLT_SAMPLER_LOCAL = 1;
+// DLT_SAMPLER_SEGMENT (the trials of mh_compat_dlt_medians, register form only): the hypotheses of a launch are `trials` per
+// segment of the point array; hypothesis c - first belongs to segment q = (c - first) / trials = [begin[q], begin[q + 1]), draws
+// sample4's tuple for counter c over the segment's begin[q + 1] - begin[q] positions and adds begin[q].  The arguments are
+// cluster_begin, trials, first.
+constexpr int DLT_SAMPLER_UNIFORM = 0, DLT_SAMPLER_LOCAL = 1, DLT_SAMPLER_SEGMENT = 2;
+// how many trailing arguments k_dlt4 / k_dlt4_lds hand on to sample4_by under a sampler
+constexpr int dlt_sampler_args(int sampler) { return sampler == DLT_SAMPLER_UNIFORM ? 0 : 3; }
 
 __device__ __forceinline__ void sample4_by(unsigned long long seed, unsigned long long c, unsigned int N, int out[4])
 {
@@ -72,6 +78,32 @@ __device__ __forceinline__ void sample4_by(unsigned long long seed, unsigned lon
     out[1] = got > 1 ? o1 : i0;
     out[2] = got > 2 ? o2 : i0;
     out[3] = got > 3 ? o3 : i0;
+}
+
+// sample_tuple<4, 64> over the nc positions of the hypothesis' segment, shifted by the segment's start: the same draws, the same
+// rejection and the same exhaustion rule, the tuple in named registers.  (The point count N of the launch is not read.)
+__device__ __forceinline__ void sample4_by(unsigned long long seed, unsigned long long c, unsigned int, int out[4],
+                                           const int* __restrict__ cluster_begin, int trials, long long first)
+{
+    const int q = (int)((long long)c - first) / trials;
+    const int b0 = cluster_begin[q];
+    const unsigned long long nc = (unsigned long long)(unsigned int)(cluster_begin[q + 1] - b0);
+    const unsigned long long base = seed + (c << 8);
+    int o0 = -1, o1 = -1, o2 = -1, o3 = -1, got = 0;                // (-1 equals no position)
+    for (unsigned int j = 0; j < 64 && got < 4; ++j) {
+        const int cand = (int)(((splitmix64(base + j) >> 32) * nc) >> 32);
+        if (cand != o0 && cand != o1 && cand != o2) {
+            o0 = got == 0 ? cand : o0;
+            o1 = got == 1 ? cand : o1;
+            o2 = got == 2 ? cand : o2;
+            o3 = got == 3 ? cand : o3;
+            ++got;
+        }
+    }
+    out[0] = b0 + o0;
+    out[1] = b0 + (got > 1 ? o1 : o0);
+    out[2] = b0 + (got > 2 ? o2 : o0);
+    out[3] = b0 + (got > 3 ? o3 : o0);
 }
 
 } // namespace mh

@@ -49,6 +49,8 @@
 #pragma weak mh_propose_haf
 // ... and for the 3-point proposals (PROPOSAL_SOURCE_3PT): the same.
 #pragma weak mh_propose_3pt
+// ... and for the compatibility check without F (SetCompatibilityFit(COMPAT_FIT_DLT)): without its entry point that mode fails with a message.
+#pragma weak mh_compat_dlt_medians
 
 namespace {
 
@@ -302,6 +304,20 @@ bool MultiH::Run(bool points_only)
         if (proposal_source == PROPOSAL_SOURCE_HAF || proposal_source == PROPOSAL_SOURCE_3PT) {
             std::cerr << "Error: " << (proposal_source == PROPOSAL_SOURCE_HAF ? "HAF proposals (PROPOSAL_SOURCE_HAF)" : "3-point proposals (PROPOSAL_SOURCE_3PT)")
                       << " need the fundamental matrix; the epipolar-free route (SetEpipolarFree) cannot use them\n";
+            return false;
+        }
+    }
+    if (compat_fit != COMPAT_FIT_3PT && compat_fit != COMPAT_FIT_DLT) {
+        std::cerr << "Error: unknown compatibility fit " << compat_fit << " (COMPAT_FIT_3PT or COMPAT_FIT_DLT)\n";
+        return false;
+    }
+    if (compat_fit == COMPAT_FIT_DLT && run_compatibility_check) {
+        if (!mh_compat_dlt_medians) {
+            std::cerr << "Error: the engine library has no compatibility check with 4-point trials (mh_compat_dlt_medians)\n";
+            return false;
+        }
+        if (compat_trials < 1 || compat_trials > MH_COMPAT_DLT_MAX_TRIALS || !(compat_limit_scale >= 0.0) || std::isinf(compat_limit_scale)) {
+            std::cerr << "Error: SetCompatibilityFit: trials outside [1, " << MH_COMPAT_DLT_MAX_TRIALS << "] or a limit scale that is negative or not finite\n";
             return false;
         }
     }
@@ -666,7 +682,16 @@ bool MultiH::Run(bool points_only)
     ClusterMergingAndLabeling();
     stage("neighbourhood + alternation");
 
-    if (cluster_homographies.size() > 1 && run_compatibility_check && epipolar_free) {
+    if (cluster_homographies.size() > 1 && run_compatibility_check && compat_fit == COMPAT_FIT_DLT) {
+        const int before = static_cast<int>(cluster_homographies.size());
+        auto t0 = std::chrono::system_clock::now();
+        post_filter_failed = false;
+        HomographyCompatibilityCheckDlt();
+        if (post_filter_failed) return false;                                // the engine refused: no host fallback
+        std::chrono::duration<double> el = std::chrono::system_clock::now() - t0;
+        printf("[Multi-H] Compatibility check (4-point trials) time = %f secs (%d clusters removed from %d)\n", el.count(),
+               before - (int)cluster_homographies.size(), before);
+    } else if (cluster_homographies.size() > 1 && run_compatibility_check && epipolar_free) {
         printf("[Multi-H] Epipolar-free route: the compatibility check is skipped (its trials are 3-point fits with F).\n");
     } else if (cluster_homographies.size() > 1 && run_compatibility_check) {        // :78-86
         const int before = static_cast<int>(cluster_homographies.size());
@@ -753,6 +778,35 @@ void MultiH::HomographyCompatibilityCheck()
                                                 fundamental_matrix, sqr_threshold_homography,
                                                 minimum_inlier_number, proposal_seed ^ 0xc0117a7ull, nullptr,
                                                 engine ? &on_engine : nullptr, &failed, engine != nullptr);
+    if (failed) { post_filter_failed = true; return; }
+    cluster_homographies.clear();
+    for (int i = 0; i < kept; ++i) cluster_homographies.push_back(MatFrom9(&H[9 * (size_t)i]));
+}
+
+void MultiH::HomographyCompatibilityCheckDlt()
+{
+    const int N = static_cast<int>(src_points.size());
+    const int nh = static_cast<int>(cluster_homographies.size());
+    if (nh == 0 || (int)labeling.size() != N) return;
+    std::vector<double> s(2 * (size_t)N), d(2 * (size_t)N), H(9 * (size_t)nh);
+    for (int i = 0; i < N; ++i) {
+        s[2 * i] = src_points[i].x; s[2 * i + 1] = src_points[i].y;
+        d[2 * i] = dst_points[i].x; d[2 * i + 1] = dst_points[i].y;
+    }
+    for (int i = 0; i < nh; ++i) {
+        const double* p = reinterpret_cast<const double*>(cluster_homographies[i].data);
+        for (int k = 0; k < 9; ++k) H[9 * (size_t)i + k] = p[k];
+    }
+    const multih::CompatDltFn on_engine = [this](const double* pts, const int* begin, int clusters, uint64_t seed, int trials,
+                                                 double* medians) {
+        return Check(mh_compat_dlt_medians(engine, pts, begin, clusters, seed, 0, trials, medians, nullptr, nullptr, nullptr),
+                     "mh_compat_dlt_medians");
+    };
+    const double scale = compat_limit_scale > 0.0 ? compat_limit_scale : COMPAT_DLT_LIMIT_SCALE;
+    bool failed = false;
+    const int kept = multih::CompatibilityCheckDlt(s.data(), d.data(), N, labeling.data(), H.data(), nh,
+                                                   scale * sqr_threshold_homography, minimum_inlier_number,
+                                                   proposal_seed ^ 0xc0117a7ull, compat_trials, nullptr, &on_engine, &failed);
     if (failed) { post_filter_failed = true; return; }
     cluster_homographies.clear();
     for (int i = 0; i < kept; ++i) cluster_homographies.push_back(MatFrom9(&H[9 * (size_t)i]));
@@ -1373,6 +1427,11 @@ extern "C" __attribute__((visibility("default")))
 void mhh_set_estimator(int estimator) { g_estimator = estimator; }
 extern "C" __attribute__((visibility("default")))
 void mhh_set_epipolar_free(int on) { g_epipolar_free = on; }
+// MultiH::SetCompatibilityFit for mhh_run_process; the initial value (COMPAT_FIT_3PT, 501, 0) is the class's default
+static int g_compat_fit = 0, g_compat_trials = 501;
+static double g_compat_limit_scale = 0.0;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_compat_fit(int mode, int trials, double limit_scale) { g_compat_fit = mode; g_compat_trials = trials; g_compat_limit_scale = limit_scale; }
 // MultiH::SetSelectionScore for the next mhh_run_process calls (< 0: the class default)
 static int g_selection_score = -1;
 extern "C" __attribute__((visibility("default")))
@@ -1416,6 +1475,21 @@ int mhh_compatibility_medians_on_engine(mh_engine* engine, const double* src_xy,
     bool failed = false;
     const int kept = multih::CompatibilityCheck(src_xy, dst_xy, n, labels, H, nh, F, sqr_thr, min_inliers, seed, medians, &fn, &failed,
                                                 g_compat_fits_on_engine != 0);
+    return failed ? -1 : kept;
+}
+
+// multih::CompatibilityCheckDlt with the statistics from an engine (mh_compat_dlt_medians), as Process() runs it under
+// COMPAT_FIT_DLT, returning the per-cluster medians too (NaN where a cluster got none); -1 if the engine fails.  For the GPU tests.
+extern "C" __attribute__((visibility("default")))
+int mhh_compatibility_dlt_on_engine(mh_engine* engine, const double* src_xy, const double* dst_xy, int n, int* labels, double* H,
+                                    int nh, double limit, int min_inliers, unsigned long long seed, int trials, double* medians)
+{
+    if (!mh_compat_dlt_medians) return -1;
+    const multih::CompatDltFn fn = [engine](const double* pts, const int* begin, int clusters, uint64_t sd, int tr, double* out) {
+        return mh_compat_dlt_medians(engine, pts, begin, clusters, sd, 0, tr, out, nullptr, nullptr, nullptr) == MH_OK;
+    };
+    bool failed = false;
+    const int kept = multih::CompatibilityCheckDlt(src_xy, dst_xy, n, labels, H, nh, limit, min_inliers, seed, trials, medians, &fn, &failed);
     return failed ? -1 : kept;
 }
 
@@ -1466,6 +1540,7 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     if (g_selection_score >= 0) mh.SetSelectionScore(g_selection_score);
     if (g_estimator >= 0) mh.SetEstimator(g_estimator);
     mh.SetEpipolarFree(g_epipolar_free != 0);
+    mh.SetCompatibilityFit(g_compat_fit, g_compat_trials, g_compat_limit_scale);
     if (g_fund_estimator >= 0) mh.SetFundamentalEstimator(g_fund_estimator, g_fund_max_samples, g_fund_confidence);
     for (const auto& kv : g_tuning) mh.SetEngineTuning(kv.first, kv.second);
     if (g_radius > 0.0 && g_max_hits > 0) { mh.SetNeighbourRadius(g_radius, g_max_hits); if (g_knn > 0) mh.SetFallbackK(g_knn); }

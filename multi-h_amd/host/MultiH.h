@@ -73,6 +73,9 @@ public:
     // Post-filter of the reference (M/MultiH.cpp:100-222): multih::CompatibilityCheck with the trials' order statistics
     // from the engine (mh_compat_trial_stats).
     void HomographyCompatibilityCheck();
+    // The same place in Process() under COMPAT_FIT_DLT: multih::CompatibilityCheckDlt with the statistics from the engine
+    // (mh_compat_dlt_medians).  Needs no F.
+    void HomographyCompatibilityCheckDlt();
 
     // ---- extension points: outputs of the reference's OpenCV front half ----
     // fundamental_matrix (row-major) and epipole_2 = (x, y, 1) (M/MultiH.cpp:775-799).
@@ -138,8 +141,9 @@ public:
     // forms estimate no F and refine or drop no correspondence (GetFrontStages() reports the input count four times; a
     // caller's SetEpipolarGeometry is ignored with one log line), run the engine under ESTIMATOR_DLT without mh_set_epipolar
     // (affinities are uploaded if given and never read), take the medoid of each mean-shift mode as MergingStep's candidate
-    // (multih::MergeCandidatesMedoid) and skip HomographyCompatibilityCheck, whose trials are 3-point fits with F (one log
-    // line).  INIT_STABLE_SETS, PROPOSAL_SOURCE_HAF and PROPOSAL_SOURCE_3PT need F: Process() refuses them with a message.
+    // (multih::MergeCandidatesMedoid) and, under COMPAT_FIT_3PT only, skip HomographyCompatibilityCheck, whose trials are then
+    // 3-point fits with F (one log line); under COMPAT_FIT_DLT the check runs here too (SetCompatibilityFit).
+    // INIT_STABLE_SETS, PROPOSAL_SOURCE_HAF and PROPOSAL_SOURCE_3PT need F: Process() refuses them with a message.
     void SetEpipolarFree(bool on) { epipolar_free = on; }
     // The data term of the labeling (mh_set_data_term, include/multih_hip.h): DATA_TERM_REFERENCE is dataEnergy
     // (M/MultiH.cpp:473-504), whose cost inside the truncation threshold FALLS as the fit gets worse (default);
@@ -275,6 +279,19 @@ public:
     // The post-filter of Process() (HomographyCompatibilityCheck, M/MultiH.cpp:78-86) can be switched off to look at
     // what the merge <-> label loop itself produced (parity tests against the oracle of that loop).
     void SetCompatibilityCheck(bool on) { run_compatibility_check = on; }
+    // What the trials of the post-filter fit.  COMPAT_FIT_3PT (default): the reference's 3-point fits with F; nothing changes
+    // anywhere, and the route without epipolar geometry skips the check.  COMPAT_FIT_DLT: multih::CompatibilityCheckDlt stands
+    // where that check stood, on both routes: `trials` 4-point DLT trials per cluster on the engine (mh_compat_dlt_medians, seed
+    // proposal_seed ^ 0xc0117a7), a cluster going when its statistic exceeds limit_scale * thr_hom^2.  limit_scale = 0 takes
+    // COMPAT_DLT_LIMIT_SCALE, the measured statistic of a clean plane whose noise equals the inlier threshold.
+    // SetCompatibilityCheck(false) switches either off; SetModelReweight* and SetModelPolish run on what the check kept.
+    // Process() fails with a message for another mode, trials outside [1, 4096] or a limit_scale that is negative or not finite.
+    enum { COMPAT_FIT_3PT = 0, COMPAT_FIT_DLT = 1 };
+    static constexpr double COMPAT_DLT_LIMIT_SCALE = 256.0;
+    void SetCompatibilityFit(int mode, int trials = 501, double limit_scale = 0.0)
+    {
+        compat_fit = mode; compat_trials = trials; compat_limit_scale = limit_scale;
+    }
     void SetDevice(int d) { device = d; }
     // schedule knob of the engine (mh_set_tuning; results never depend on it), applied when the engine is created
     void SetEngineTuning(int key, int value) { engine_tuning.emplace_back(key, value); }
@@ -347,6 +364,8 @@ protected:
     FrontStages front_stages;
     int init_mode = INIT_DLT;
     bool run_compatibility_check = true;
+    int compat_fit = COMPAT_FIT_3PT, compat_trials = 501;      // SetCompatibilityFit
+    double compat_limit_scale = 0.0;
     bool post_filter_failed = false;             // the engine's part of HomographyCompatibilityCheck returned an error
     uint64_t merge_rng_counter = 0;
     double loop_seconds = 0.0;

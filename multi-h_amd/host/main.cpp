@@ -25,6 +25,11 @@
 //                                is the reference's); --points takes 3pt unless dlt (the N-point DLT, which reads no F) is asked for
 //                  [--no-epipolar]   the route without epipolar geometry (MultiH::SetEpipolarFree): no F is estimated, no row is
 //                                filtered (the load filter included), DLT refits, medoid merge candidates, no compatibility check
+//                                (unless --compat-fit dlt)
+//                  [--compat-fit dlt[:trials[:limit_scale]]]   the post-filter's trials are 4-point DLT fits, which need no F
+//                                (MultiH::SetCompatibilityFit): it then runs on either route, trials per cluster (default 501, at
+//                                most 4096), a cluster going when its statistic exceeds limit_scale * thrH^2 (default: the
+//                                measured 256); "Compatibility check (4-point trials) .. clusters removed" reports it
 //                  [--data-term reference|rising]   the data term of the labeling (MultiH::SetDataTerm): reference, the default, is
 //                                the reference's dataEnergy (the cost falls as the fit gets worse); rising drops its `1.0 -`
 //                  [--tail-score count|msac]   how the degenerate tail ranks its DLT hypotheses (MultiH::SetTailScore): count, the
@@ -135,7 +140,7 @@ int main(int argc, char** argv)
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
                      "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] [--f-estimator ls8|minimal] "
-                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--data-term reference|rising] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--reweight n[:scale]] [--estimator-reweight n[:scale]] [--reweight-auto n[:kappa]] [--estimator-reweight-auto n[:kappa]] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
+                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--compat-fit dlt[:trials[:limit_scale]]] [--data-term reference|rising] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--reweight n[:scale]] [--estimator-reweight n[:scale]] [--reweight-auto n[:kappa]] [--estimator-reweight-auto n[:kappa]] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
         return 2;
     }
     double thrF = 2.6, thrH = 2.2, locality = 0.005, lambda = 0.5;     // M/main.cpp:55-59
@@ -151,6 +156,8 @@ int main(int argc, char** argv)
     int data_term = MultiH::DATA_TERM_REFERENCE;
     int tail_score = MultiH::TAIL_SCORE_COUNT;
     int tail_refit = 0, tail_polish = 0, model_polish = 0;
+    int compat_fit = MultiH::COMPAT_FIT_3PT, compat_trials = 501;
+    double compat_limit_scale = 0.0;
     int model_reweight = 0, estimator_reweight = 0;
     double model_reweight_scale = 0.0, estimator_reweight_scale = 0.0;
     int model_reweight_auto = 0, estimator_reweight_auto = 0;
@@ -196,6 +203,28 @@ int main(int argc, char** argv)
                 return 2;
             }
             (k == "--polish" ? model_polish : tail_polish) = atoi(v);
+        }
+        else if (k == "--compat-fit") {
+            // dlt | dlt:trials | dlt:trials:limit_scale — trials a whole number in [1, 4096], limit_scale a number > 0
+            const std::string tv = v;
+            const size_t c1 = tv.find(':'), c2 = c1 == std::string::npos ? c1 : tv.find(':', c1 + 1);
+            bool ok = tv.substr(0, c1) == "dlt";
+            if (ok && c1 != std::string::npos) {
+                const std::string nv = tv.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1);
+                ok = !nv.empty() && nv.size() <= 4 && nv.find_first_not_of("0123456789") == std::string::npos && atoi(nv.c_str()) >= 1 &&
+                     atoi(nv.c_str()) <= 4096;
+                if (ok) compat_trials = atoi(nv.c_str());
+            }
+            if (ok && c2 != std::string::npos) {
+                char* end = nullptr;
+                compat_limit_scale = strtod(tv.c_str() + c2 + 1, &end);
+                ok = end != tv.c_str() + c2 + 1 && *end == '\0' && compat_limit_scale > 0.0 && compat_limit_scale <= 1e150;
+            }
+            if (!ok) {
+                std::cerr << "--compat-fit: dlt[:trials[:limit_scale]], trials a whole number in [1, 4096], limit_scale a number > 0\n";
+                return 2;
+            }
+            compat_fit = MultiH::COMPAT_FIT_DLT;
         }
         else if (k == "--reweight" || k == "--estimator-reweight") {
             // n | n:scale — a whole number of rounds in [0, 16], a scale in pixels > 0 (default: the homography threshold)
@@ -441,6 +470,7 @@ int main(int argc, char** argv)
     else if (neighbourhood == "approx") multiH->SetNeighbourApprox(4, 32, 0x464c414e4eull + seed);   // ... as FLANN's default search answers it
     multiH->SetEstimator(estimator);
     multiH->SetEpipolarFree(no_epipolar);
+    multiH->SetCompatibilityFit(compat_fit, compat_trials, compat_limit_scale);
     multiH->SetDataTerm(data_term);
     multiH->SetTailScore(tail_score);
     multiH->SetTailRefit(tail_refit);

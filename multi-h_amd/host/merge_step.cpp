@@ -647,6 +647,22 @@ double MedianFromStats(const TrialStats* st, int rest, int trials)
     return trials % 2 ? distances[trials / 2] : 0.5 * (distances[trials / 2] + distances[trials / 2 + 1]);   // :193
 }
 
+// :208-221: the removed clusters' labels become -1, the labels above them move down, H is compacted; returns the new count
+int RemoveClusters(const std::vector<char>& remove, int n, int* labels, double* H, int nh)
+{
+    int kept = nh;
+    for (int c = nh - 1; c >= 0; --c) {
+        if (!remove[c]) continue;
+        for (int j = 0; j < n; ++j) {
+            if (labels[j] == c) labels[j] = -1;
+            else if (labels[j] > c) --labels[j];
+        }
+        for (int q = c; q + 1 < kept; ++q) std::memcpy(H + 9 * (size_t)q, H + 9 * (size_t)(q + 1), 9 * sizeof(double));
+        --kept;
+    }
+    return kept;
+}
+
 } // namespace
 
 static_assert(sizeof(TrialStats) == 8 * sizeof(double), "the statistics travel as 8 doubles per trial");
@@ -744,17 +760,46 @@ int CompatibilityCheck(const double* src_xy, const double* dst_xy, int n, int* l
         if (medians) medians[c] = median[c];
         if (has_median[c]) remove[c] = median[c] > sqr_thr * 81.0 / 16.0;  // :195
     }
-    int kept = nh;
-    for (int c = nh - 1; c >= 0; --c) {                                       // :208-221
-        if (!remove[c]) continue;
-        for (int j = 0; j < n; ++j) {
-            if (labels[j] == c) labels[j] = -1;
-            else if (labels[j] > c) --labels[j];
+    return RemoveClusters(remove, n, labels, H, nh);
+}
+
+int CompatibilityCheckDlt(const double* src_xy, const double* dst_xy, int n, int* labels, double* H, int nh, double limit,
+                          int min_inliers, uint64_t seed, int trials, double* medians, const CompatDltFn* stats_fn, bool* failed)
+{
+    if (failed) *failed = false;
+    std::vector<int> count(nh, 0);
+    for (int i = 0; i < n; ++i) if (labels[i] > -1 && labels[i] < nh) ++count[labels[i]];
+    std::vector<char> remove(nh, 0);
+    std::vector<int> slot(nh, -1), begin(1, 0);                           // slot: a cluster's place in the packed list
+    for (int c = 0; c < nh; ++c) {
+        if (count[c] < min_inliers) remove[c] = 1;                         // the rule of M/MultiH.cpp:199-200
+        else if (count[c] >= std::max(min_inliers, 5)) {                   // (5: MH_COMPAT_DLT_MIN_POINTS)
+            slot[c] = (int)begin.size() - 1;
+            begin.push_back(begin.back() + count[c]);
         }
-        for (int q = c; q + 1 < kept; ++q) std::memcpy(H + 9 * (size_t)q, H + 9 * (size_t)(q + 1), 9 * sizeof(double));
-        --kept;
     }
-    return kept;
+    const int packed = (int)begin.size() - 1;
+    std::vector<double> med(packed, 0.0);
+    if (packed > 0) {
+        std::vector<double> pts(4 * (size_t)begin[packed]);
+        std::vector<int> cursor(begin.begin(), begin.end() - 1);
+        for (int i = 0; i < n; ++i) {
+            const int l = labels[i];
+            if (l < 0 || l >= nh || slot[l] < 0) continue;
+            double* q = &pts[4 * (size_t)cursor[slot[l]]++];
+            q[0] = src_xy[2 * (size_t)i]; q[1] = src_xy[2 * (size_t)i + 1]; q[2] = dst_xy[2 * (size_t)i]; q[3] = dst_xy[2 * (size_t)i + 1];
+        }
+        // first = 0: cluster q of the packed list owns the counters [q trials, (q + 1) trials)
+        if (!stats_fn || !*stats_fn || !(*stats_fn)(pts.data(), begin.data(), packed, seed, trials, med.data())) {
+            if (failed) *failed = true;
+            return nh;
+        }
+    }
+    for (int c = 0; c < nh; ++c) {
+        if (slot[c] >= 0) remove[c] = med[slot[c]] > limit;                // (+inf goes; a statistic is never a NaN)
+        if (medians) medians[c] = slot[c] >= 0 ? med[slot[c]] : std::nan("");
+    }
+    return RemoveClusters(remove, n, labels, H, nh);
 }
 
 void Homography3PTClusters(const double* src_xy, const double* dst_xy, const std::vector<std::vector<int>>& members, const double F[9],

@@ -84,6 +84,22 @@ int CompatibilityCheck(const double* src_xy, const double* dst_xy, int n, int* l
                        // called with H = ok = nullptr and the host fits none
                        bool stats_fn_fits = false);
 
+// The compatibility check WITHOUT F (MultiH::SetCompatibilityFit(COMPAT_FIT_DLT)): the statistic of a cluster is
+// the median over `trials` trials of the median forward transfer error of its other members under a 4-point DLT fit to four random
+// members (the engine's mh_compat_dlt_medians, whose header comment is the definition).  With N = the cluster's size:
+//   N < min_inliers               removed (M/MultiH.cpp:199-200);
+//   N >= max(min_inliers, 5)      gets a statistic and is removed if and only if it exceeds `limit` (+inf is removed);
+//   otherwise                     kept without a statistic; its median is reported as NaN.
+// The clusters that get a statistic are packed in cluster order, their points in point order, and handed to stats_fn with
+// first = 0: cluster q of the packed list owns the counters [q trials, (q + 1) trials).  Removal, renumbering and the compaction
+// of H are CompatibilityCheck's.  stats_fn returns false on failure (and a missing stats_fn counts as one: the host has no
+// 4-point solver of its own), reported through *failed with the labels and H untouched.
+using CompatDltFn = std::function<bool(const double* pts_xyxy, const int* cluster_begin, int clusters, uint64_t seed, int trials,
+                                       double* medians_out)>;
+int CompatibilityCheckDlt(const double* src_xy, const double* dst_xy, int n, int* labels, double* H, int nh, double limit,
+                          int min_inliers, uint64_t seed, int trials, double* medians /* nh, nullable */,
+                          const CompatDltFn* stats_fn, bool* failed = nullptr);
+
 // r06: one 3-point least-squares homography with LM refinement per cluster of at least three members (EstablishStablePointSets,
 // M/MultiH.cpp:664-688), the clusters spread over the host's cores (each fit is independent; the results are taken in cluster
 // order, so nothing depends on the number of threads).  H: 9 doubles per cluster; ok: 1 where the cluster had >= 3 members and its
