@@ -286,9 +286,34 @@ MH_API int mh_propose_3pt(mh_engine* e, unsigned long long seed, long long first
  *                         an extension with no reference counterpart (H^-1 = adjugate, same rounding
  *                         discipline; the definition is checked in exact rationals, tests/test_symmetric_exact.py).
  *                         Used by mh_score, mh_residual_matrix, mh_get_residual_rows and (r05) mh_select_greedy;
- *                         data cost / labeling always use the forward formula. */
+ *                         the data cost, the labeling, the moments and the single-model labelling follow it under
+ *                         MH_RESIDUAL_SCOPE_ROUTE alone (mh_set_residual_scope below; forward by default).
+ * The symmetric d2, stated once: fwd(H; p1, p2) + fwd(adj(H); p2, p1), where fwd is the forward formula above in the
+ * reference's operation order, adj(H) entry by entry is (mul, mul, sub) with every operation rounded once, and the two
+ * terms meet in one final rounded addition; no fused multiply-add anywhere.  A NaN d2 is neither an inlier nor inside
+ * the data term's truncation T. */
 enum { MH_RESIDUAL_FORWARD = 0, MH_RESIDUAL_SYMMETRIC = 1 };
 MH_API int mh_set_residual_mode(mh_engine* e, int mode);
+/* Which calls follow mh_set_residual_mode.
+ *   MH_RESIDUAL_SCOPE_SCORE (default)  the score family listed above, and nothing else;
+ *   MH_RESIDUAL_SCOPE_ROUTE            ... and the calls behind the selection: mh_data_cost, mh_labeling_step (its table, hence
+ *                                      its labels and energy), mh_cost_matrix (costs and the fused counts; always the FP64
+ *                                      kernel under the symmetric mode, whatever mh_set_tuning keys 15 and 23 say: the FP32
+ *                                      pre-test is proved for the forward error only), mh_inlier_moments, mh_inliers_of_model
+ *                                      and mh_inliers_of_homography.
+ * Under SCOPE_SCORE, or under MH_RESIDUAL_FORWARD with either scope, those calls are the forward launches, bit for bit.
+ * The data term's table (mh_set_data_term) is unchanged with the symmetric d2 in place of the forward one: both terms, label
+ * 0, the truncation T = thr_hom^2 * 81 / 16 and C round().
+ * What stays forward whatever mode and scope say: mh_score_msac and mh_select_greedy_msac (they refuse the symmetric mode),
+ * mh_refit_homography, mh_polish_homographies, mh_reweight_homographies*, mh_label_residual_quantile, the compatibility
+ * statistics and mh_propose_haf's consistency test.  The scope does not enter the selection records' mode word: the
+ * selection never reads it.
+ * Sticky per engine; mh_set_correspondences does not reset it.  Setting it (to any value) marks the data cost stale exactly as
+ * mh_set_data_term does (mh_expand answers MH_ERR_NOT_SET until mh_data_cost has run); under SCOPE_ROUTE mh_set_residual_mode
+ * marks it stale too, under SCOPE_SCORE it does not.  Another value, or a null engine: MH_ERR_INVALID, nothing changed. */
+#define MH_RESIDUAL_SCOPE_SCORE 0
+#define MH_RESIDUAL_SCOPE_ROUTE 1
+MH_API int mh_set_residual_scope(mh_engine* e, int scope);
 /* Inlier count of every current model over all points, forward transfer error, strict
  * d2 < thr2 (M/MultiH.cpp:430-443).  point_mask (n bytes, nullable) restricts the count to
  * points with mask != 0.  counts (m ints, nullable) receives a host copy; the counts also
@@ -681,7 +706,8 @@ MH_API int mh_inlier_moments(mh_engine* e, double thr2, double* moments /* m x 6
 /* The data term of mh_data_cost, mh_cost_matrix and mh_labeling_step.  With lam = 100 / lambda and T = thr_hom^2 * 81 / 16
  * (both computed in double, in that order of operations), B = (int)round(lam * T), and d2 the forward transfer error of the
  * pair in the reference's operation order (M/MultiH.cpp:434-441: s = h6 x + h7 y + h8; u = (h0 x + h1 y + h2) / s;
- * v = (h3 x + h4 y + h5) / s; d2 = (x2 - u)^2 + (y2 - v)^2, every operation rounded once), the int32 cost of (point, label) is
+ * v = (h3 x + h4 y + h5) / s; d2 = (x2 - u)^2 + (y2 - v)^2, every operation rounded once) — or, under MH_RESIDUAL_SYMMETRIC
+ * with MH_RESIDUAL_SCOPE_ROUTE, the symmetric d2 as stated at mh_set_residual_mode —, the int32 cost of (point, label) is
  *                               MH_DATA_TERM_REFERENCE (default)             MH_DATA_TERM_RISING
  *   label 0 (outlier)           B                                            B
  *   d2 < T (strictly)           (int)round(lam * (1.0 - (d2 / T)))           (int)round(lam * (d2 / T))

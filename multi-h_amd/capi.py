@@ -20,6 +20,7 @@ BUF_COUNTS, BUF_MODELS, BUF_RESIDUALS, BUF_LABELS, BUF_COST, BUF_LABEL_COUNTS, B
 MSAC_SCALE = 256                       # MH_MSAC_SCALE
 ESTIMATORS = {"haf": 0, "3pt": 1, "dlt": 2}      # MH_ESTIMATOR_HAF, MH_ESTIMATOR_3PT, MH_ESTIMATOR_DLT
 SAMPLER_UNIFORM, SAMPLER_LOCAL = 0, 1  # MH_SAMPLER_UNIFORM, MH_SAMPLER_LOCAL
+RESIDUAL_SCOPES = {"score": 0, "route": 1}      # MH_RESIDUAL_SCOPE_SCORE, MH_RESIDUAL_SCOPE_ROUTE
 DATA_TERMS = {"reference": 0, "rising": 1}      # MH_DATA_TERM_REFERENCE, MH_DATA_TERM_RISING
 K_DLT4, K_RESIDUAL, K_SCORE, K_DATACOST, K_EXPAND, K_REESTIMATE, K_COSTMATRIX = 0, 1, 2, 3, 4, 5, 6
 
@@ -30,7 +31,7 @@ SYMBOLS = [
     "mh_set_neighbors_csr", "mh_build_neighbors_knn", "mh_build_neighbors_knn_radius", "mh_build_neighbors_radius", "mh_get_sym_graph", "mh_set_fundamental_metric", "mh_propose_fund8",
     "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_propose_fund7", "mh_get_fund7_samples", "mh_estimate_fundamental_minimal", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons", "mh_refine_points",
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
-    "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_propose_haf", "mh_get_haf_support", "mh_propose_3pt", "mh_set_residual_mode", "mh_score", "mh_score_msac", "mh_select_best_msac",
+    "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_propose_haf", "mh_get_haf_support", "mh_propose_3pt", "mh_set_residual_mode", "mh_set_residual_scope", "mh_score", "mh_score_msac", "mh_select_best_msac",
     "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_select_greedy_msac", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_refit_homography", "mh_polish_homographies", "mh_reweight_homographies", "mh_label_residual_quantile", "mh_reweight_homographies_auto", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_compat_dlt_medians", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
     "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_set_estimator_reweighting", "mh_set_estimator_reweighting_auto", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
     "mh_profile_get", "mh_set_tuning",
@@ -350,6 +351,13 @@ class Engine:
     # -- score --------------------------------------------------------------
     def set_residual_mode(self, symmetric: bool):
         self._check(self.lib.mh_set_residual_mode(self._h, 1 if symmetric else 0))
+
+    def set_residual_scope(self, name: str):
+        """mh_set_residual_scope: "score" (default: the score family follows set_residual_mode) or "route" (so do data_cost,
+        labeling_step, cost_matrix, inlier_moments and inliers_of_model / _of_homography); sticky, marks the data cost stale."""
+        if name not in RESIDUAL_SCOPES:
+            raise ValueError(f"unknown residual scope {name!r}; one of {sorted(RESIDUAL_SCOPES)}")
+        self._check(self.lib.mh_set_residual_scope(self._h, RESIDUAL_SCOPES[name]))
 
     def score(self, thr2: float, mask=None, fetch: bool = True):
         cnt = np.empty(self.model_count, dtype=np.int32) if fetch else None

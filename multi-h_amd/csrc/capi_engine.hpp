@@ -369,6 +369,9 @@ struct mh_engine : ResidentBatch {                    // (e->m, e->origin, e->ha
     int tune_ld = 0;                         // measurement builds only: row pitch of R in doubles (0 = residual_ld)
     int tune_score_variant = 0;
     int residual_mode = MH_RESIDUAL_FORWARD;
+    int residual_scope = MH_RESIDUAL_SCOPE_SCORE;   // mh_set_residual_scope: which calls follow residual_mode (changes results: not a tuning key)
+    // "is the route symmetric": what the data cost, the cost matrix, the moments and the single-model labelling are launched with
+    bool route_symmetric() const { return residual_scope == MH_RESIDUAL_SCOPE_ROUTE && residual_mode == MH_RESIDUAL_SYMMETRIC; }
     int tune_ms_batch = 6;                   // mean-shift climb iterations per host round trip
     int tune_reduce = 2;                     // dominance-reduction rounds per launch (0 = off); 2 measured best (loop 0.262 s at 4, 0.250 s at 2)
     int tune_reduce_launches = 1;            // reduction launches per move in front of the solver (1 = the compacting one alone, 2; loop 0.250 vs 0.254 s)

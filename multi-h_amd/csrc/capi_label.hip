@@ -37,7 +37,7 @@ int do_data_cost(mh_engine* e)
     {
         ScopedTimer t(e, MH_K_DATACOST);
         HIPCHK(launch_data_cost(e->pts(), e->H.p, e->m, e->lambda, e->thr_H * e->thr_H, e->cost.p, e->stream,
-                                e->data_term == MH_DATA_TERM_RISING));
+                                e->data_term == MH_DATA_TERM_RISING, e->route_symmetric()));
     }
     e->cost_L = L;
     return MH_OK;
@@ -496,6 +496,17 @@ int mh_set_data_term(mh_engine* e, int term)
     if (term != MH_DATA_TERM_REFERENCE && term != MH_DATA_TERM_RISING) return fail(MH_ERR_INVALID, "unknown data term");
     e->data_term = term;
     e->cost_L = 0;                                               // as mh_set_params: the table on the device is another term's
+    return MH_OK;
+    });
+}
+
+int mh_set_residual_scope(mh_engine* e, int scope)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (scope != MH_RESIDUAL_SCOPE_SCORE && scope != MH_RESIDUAL_SCOPE_ROUTE) return fail(MH_ERR_INVALID, "unknown residual scope");
+    e->residual_scope = scope;
+    e->cost_L = 0;                                               // as mh_set_data_term: the table on the device may be another error's
     return MH_OK;
     });
 }

@@ -189,6 +189,7 @@ int mh_set_residual_mode(mh_engine* e, int mode)
     if (!e) return fail(MH_ERR_INVALID, "null engine");
     if (mode != MH_RESIDUAL_FORWARD && mode != MH_RESIDUAL_SYMMETRIC) return fail(MH_ERR_INVALID, "unknown residual mode");
     e->residual_mode = mode;
+    if (e->residual_scope == MH_RESIDUAL_SCOPE_ROUTE) e->cost_L = 0;      // the data cost follows the mode under that scope alone
     return MH_OK;
     });
 }
@@ -327,7 +328,8 @@ int mh_cost_matrix(mh_engine* e, int* C_host, int* counts)
     {
         ScopedTimer t(e, MH_K_COSTMATRIX);
         const double thr2 = e->thr_H * e->thr_H;
-        if (pretest_usable(e, thr2, false)) {      // the FP32 pre-test (k_cost32, score32.hip); same matrix
+        const bool sym = e->route_symmetric();     // the FP32 pre-test is proved for the forward error only
+        if (!sym && pretest_usable(e, thr2, false)) {      // the FP32 pre-test (k_cost32, score32.hip); same matrix
             HIPCHK(e->H32.reserve((size_t)e->m * 16));
             HIPCHK(launch_model32(e->H.p, e->m, e->absmax_x, e->absmax_y, e->absmax_dst, e->H32.p, e->stream));
             int* ctl = nullptr;
@@ -341,7 +343,7 @@ int mh_cost_matrix(mh_engine* e, int* C_host, int* counts)
                                  e->data_term == MH_DATA_TERM_RISING));
         } else
             HIPCHK(launch_cost_matrix(e->pts(), e->H.p, e->m, e->lambda, thr2, e->C.p, e->ldc, e->counts.p, e->stream,
-                                      e->data_term == MH_DATA_TERM_RISING));
+                                      e->data_term == MH_DATA_TERM_RISING, sym));
     }
     counts_scored(e);
     if (C_host)
@@ -435,7 +437,7 @@ int mh_inliers_of_model(mh_engine* e, int idx, double thr2, int label_value, int
     if (idx < 0 || idx >= e->m || !labels) return fail(MH_ERR_INVALID, "bad model index or null labels");
     HIPCHK(e->labels_pts.reserve(e->n));
     HIPCHK(hipMemcpyAsync(e->labels_pts.p, labels, sizeof(int) * e->n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(launch_inliers_of_model(e->pts(), e->H.p, idx, thr2, label_value, e->labels_pts.p, e->stream));
+    HIPCHK(launch_inliers_of_model(e->pts(), e->H.p, idx, thr2, label_value, e->labels_pts.p, e->stream, e->route_symmetric()));
     HIPCHK(hipMemcpyAsync(labels, e->labels_pts.p, sizeof(int) * e->n, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return MH_OK;
@@ -452,7 +454,7 @@ int mh_inliers_of_homography(mh_engine* e, const double* H, double thr2, int lab
     HIPCHK(e->labels_pts.reserve(e->n));
     HIPCHK(hipMemcpyAsync(e->H_one.p, H, sizeof(double) * 9, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->labels_pts.p, labels, sizeof(int) * e->n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(launch_inliers_of_model(e->pts(), e->H_one.p, 0, thr2, label_value, e->labels_pts.p, e->stream));
+    HIPCHK(launch_inliers_of_model(e->pts(), e->H_one.p, 0, thr2, label_value, e->labels_pts.p, e->stream, e->route_symmetric()));
     HIPCHK(hipMemcpyAsync(labels, e->labels_pts.p, sizeof(int) * e->n, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return MH_OK;
@@ -614,7 +616,7 @@ int mh_inlier_moments(mh_engine* e, double thr2, double* moments, double* min_ei
     if (rc) return rc;
     HIPCHK(e->moments.reserve((size_t)e->m * 6));
     HIPCHK(e->min_eig.reserve(e->m));
-    HIPCHK(launch_moments(e->pts(), e->H.p, e->m, thr2, e->moments.p, e->min_eig.p, e->stream));
+    HIPCHK(launch_moments(e->pts(), e->H.p, e->m, thr2, e->moments.p, e->min_eig.p, e->stream, e->route_symmetric()));
     if (moments)
         HIPCHK(hipMemcpyAsync(moments, e->moments.p, sizeof(double) * 6 * e->m, hipMemcpyDeviceToHost, e->stream));
     if (min_eig)

@@ -19,7 +19,33 @@ __device__ __forceinline__ double fwd_d2(double h0, double h1, double h2, double
     return dx * dx + dy * dy;
 }
 
-// The data term of one (point, model) pair from its forward error d2 (include/multih_hip.h, mh_set_data_term): one IEEE
+// adj(H), H^-1 up to scale: each entry is (mul, mul, sub), every operation rounded once.
+__device__ __forceinline__ void adjugate(const double* __restrict__ h, double* __restrict__ a)
+{
+    a[0] = h[4] * h[8] - h[5] * h[7]; a[1] = h[2] * h[7] - h[1] * h[8]; a[2] = h[1] * h[5] - h[2] * h[4];
+    a[3] = h[5] * h[6] - h[3] * h[8]; a[4] = h[0] * h[8] - h[2] * h[6]; a[5] = h[2] * h[3] - h[0] * h[5];
+    a[6] = h[3] * h[7] - h[4] * h[6]; a[7] = h[1] * h[6] - h[0] * h[7]; a[8] = h[0] * h[4] - h[1] * h[3];
+}
+
+// Symmetric transfer error of one (point, model) pair (include/multih_hip.h, mh_set_residual_mode): the forward error plus
+// the forward error of adj(H) on the swapped pair, one final rounded addition.  What select.hip's sel_d2 spells out and the
+// symmetric sweep (residual.hip) computes with adj(H) staged per workgroup.
+// a = adjugate(h), for a caller that meets one model with many points.
+__device__ __forceinline__ double sym_d2(const double* __restrict__ h, const double* __restrict__ a, double x, double y,
+                                         double x2, double y2)
+{
+    const double f = fwd_d2(h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], x, y, x2, y2);
+    return f + fwd_d2(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], x2, y2, x, y);
+}
+
+__device__ __forceinline__ double sym_d2(const double* __restrict__ h, double x, double y, double x2, double y2)
+{
+    double a[9];
+    adjugate(h, a);
+    return sym_d2(h, a, x, y, x2, y2);
+}
+
+// The data term of one (point, model) pair from its error d2 — forward, or sym_d2 under the symmetric route — (include/multih_hip.h, mh_set_data_term): one IEEE
 // division, one rounded multiplication, C round(); a NaN d2 fails `d2 < T` and takes `beyond`.  RISING = false is
 // dataEnergy (M/MultiH.cpp:496-503); RISING = true drops its `1.0 -` and nothing else.
 template <bool RISING>

@@ -69,10 +69,12 @@ hipError_t launch_msac32(const Points& p, const double* H, const float* H32, int
 hipError_t launch_msac64(const Points& p, const double* H, int M, double thr2, const unsigned char* mask, int* counts, int* weights,
                          hipStream_t s);
 // occ_cache (both launchers): the caller's per-engine cache of the resident kernel's workgroups per compute unit (-1 = not asked yet)
+// symmetric (both, and the two launchers of datacost.hip): 0 the forward transfer error, 1 the symmetric one — the engine's
+// route_symmetric() (capi_engine.hpp, mh_set_residual_scope)
 hipError_t launch_inliers_of_model(const Points& p, const double* H, int idx, double thr2,
-                                   int label_value, int* labels, hipStream_t s);
+                                   int label_value, int* labels, hipStream_t s, int symmetric = 0);
 hipError_t launch_moments(const Points& p, const double* H, int M, double thr2, double* moments,
-                          double* min_eig, hipStream_t s);
+                          double* min_eig, hipStream_t s, int symmetric = 0);
 
 // --- compat.hip: order statistics of the post-filter's trials (HomographyCompatibilityCheck, M/MultiH.cpp:128-196)
 hipError_t launch_compat_select(const double* pts /* total x 4 */, const int* begin /* clusters + 1 */, int clusters,
@@ -169,9 +171,9 @@ hipError_t launch_autoscale_reweight_h(const Points& p, const int* labels, const
 inline long long cost_ld(int n) { return ((long long)n + 31) & ~31ll; }
 // rising (here and in launch_cost32): 0 the reference's data term, 1 MH_DATA_TERM_RISING (include/multih_hip.h)
 hipError_t launch_cost_matrix(const Points& p, const double* H, int M, double lambda, double thr2, int* C, long long ldc,
-                              int* counts, hipStream_t s, int rising = 0);
+                              int* counts, hipStream_t s, int rising = 0, int symmetric = 0);
 hipError_t launch_data_cost(const Points& p, const double* H, int Nh, double lambda, double thr2,
-                            int* cost, hipStream_t s, int rising = 0);
+                            int* cost, hipStream_t s, int rising = 0, int symmetric = 0);
 
 // --- reestimate.hip ---------------------------------------------------------
 hipError_t launch_reestimate(const Points& p, const Affines& a, const int* labels, int Nh,

@@ -495,7 +495,9 @@ hipError_t launch_score(const Points& p, const double* H, int M, double thr2,
 #include "residual_variants.hpp"
 #endif
 
-// ComputeInliersOfHomography, M/MultiH.cpp:743-768.
+// ComputeInliersOfHomography, M/MultiH.cpp:743-768.  SYM (the symmetric route, mh_set_residual_scope): the same decision on
+// sym_d2 of mh_device.hpp.
+template <bool SYM>
 __global__ void __launch_bounds__(256)
 k_inliers_of_model(const double* __restrict__ x1, const double* __restrict__ y1,
                    const double* __restrict__ x2, const double* __restrict__ y2, int N,
@@ -505,15 +507,16 @@ k_inliers_of_model(const double* __restrict__ x1, const double* __restrict__ y1,
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
     const double* h = H + 9 * (size_t)idx;
-    const double d2 = fwd_d2(h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], x1[n], y1[n],
-                             x2[n], y2[n]);
+    const double d2 = SYM ? sym_d2(h, x1[n], y1[n], x2[n], y2[n])
+                          : fwd_d2(h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], x1[n], y1[n],
+                                   x2[n], y2[n]);
     if (d2 < thr2) labels[n] = label_value;
 }
 
 hipError_t launch_inliers_of_model(const Points& p, const double* H, int idx, double thr2,
-                                   int label_value, int* labels, hipStream_t s)
+                                   int label_value, int* labels, hipStream_t s, int symmetric)
 {
-    hipLaunchKernelGGL(k_inliers_of_model, dim3((p.n + 255) / 256), dim3(256), 0, s, p.x1, p.y1,
+    hipLaunchKernelGGL(symmetric ? k_inliers_of_model<true> : k_inliers_of_model<false>, dim3((p.n + 255) / 256), dim3(256), 0, s, p.x1, p.y1,
                        p.x2, p.y2, p.n, H, idx, thr2, label_value, labels);
     return hipGetLastError();
 }
@@ -521,8 +524,10 @@ hipError_t launch_inliers_of_model(const Points& p, const double* H, int idx, do
 // ---------------------------------------------------------------------------
 // Collinearity moments (M/MultiH.cpp:446-463).  One workgroup per model.  The
 // FP64 sums use the engine's deterministic order (wg_fit.hpp).  Thread 0
-// finishes with a cyclic-Jacobi 3x3 eigen solve.
+// finishes with a cyclic-Jacobi 3x3 eigen solve.  SYM (the symmetric route): the inlier test on the symmetric error,
+// adj(H) once per thread in front of the point loop; sums, tree and Jacobi are the same.
 // ---------------------------------------------------------------------------
+template <bool SYM>
 __global__ void __launch_bounds__(256)
 k_moments(const double* __restrict__ x1, const double* __restrict__ y1,
           const double* __restrict__ x2, const double* __restrict__ y2, int N,
@@ -534,6 +539,9 @@ k_moments(const double* __restrict__ x1, const double* __restrict__ y1,
     const double* h = H + 9 * (size_t)m;
     const double h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3], h4 = h[4], h5 = h[5], h6 = h[6],
                  h7 = h[7], h8 = h[8];
+    const double hh[9] = { h0, h1, h2, h3, h4, h5, h6, h7, h8 };
+    double a[9];
+    if (SYM) adjugate(hh, a);
     double acc[5] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
     int cnt = 0;
     // (latency bound — a trip to memory per point and lane —: the coordinates of eight of the lane's points are fetched
@@ -550,7 +558,7 @@ k_moments(const double* __restrict__ x1, const double* __restrict__ y1,
         for (int j = 0; j < UNROLL; ++j) {
             if (n0 + 256 * j >= N) continue;
             const double x = px[j], y = py[j];
-            const double d2 = fwd_d2(h0, h1, h2, h3, h4, h5, h6, h7, h8, x, y, qx[j], qy[j]);
+            const double d2 = SYM ? sym_d2(hh, a, x, y, qx[j], qy[j]) : fwd_d2(h0, h1, h2, h3, h4, h5, h6, h7, h8, x, y, qx[j], qy[j]);
             if (d2 < thr2) {
                 acc[0] = acc[0] + x;
                 acc[1] = acc[1] + y;
@@ -586,10 +594,10 @@ k_moments(const double* __restrict__ x1, const double* __restrict__ y1,
 }
 
 hipError_t launch_moments(const Points& p, const double* H, int M, double thr2, double* moments,
-                          double* min_eig, hipStream_t s)
+                          double* min_eig, hipStream_t s, int symmetric)
 {
     if (M <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_moments, dim3(M), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, thr2,
+    hipLaunchKernelGGL(symmetric ? k_moments<true> : k_moments<false>, dim3(M), dim3(256), 0, s, p.x1, p.y1, p.x2, p.y2, p.n, H, thr2,
                        moments, min_eig);
     return hipGetLastError();
 }

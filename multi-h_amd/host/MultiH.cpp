@@ -30,6 +30,9 @@
 #pragma weak mh_build_sample_neighbours
 // ... and for the data term (SetDataTerm): without its entry point the rising term fails with a message.
 #pragma weak mh_set_data_term
+// ... and for the error of the route (SetResidual): without its entry points the symmetric error fails with a message.
+#pragma weak mh_set_residual_mode
+#pragma weak mh_set_residual_scope
 // ... and for the MSAC tail (SetTailScore): without its entry points that tail fails with a message.
 #pragma weak mh_score_msac
 #pragma weak mh_select_best_msac
@@ -384,6 +387,24 @@ bool MultiH::Run(bool points_only)
             return false;
         }
     } else if (!Check(mh_set_data_term(engine, data_term), "mh_set_data_term")) {
+        return false;
+    }
+    // the error of the whole route (sticky on the engine, and engines are reused: set both ways)
+    if (residual != RESIDUAL_FORWARD && residual != RESIDUAL_SYMMETRIC) {
+        std::cerr << "Error: unknown residual " << residual << " (RESIDUAL_FORWARD or RESIDUAL_SYMMETRIC)\n";
+        return false;
+    }
+    if (residual == RESIDUAL_SYMMETRIC && (tail_score == TAIL_SCORE_MSAC || (init_mode != INIT_STABLE_SETS && selection_score == SELECTION_SCORE_MSAC))) {
+        std::cerr << "Error: the MSAC weights (TAIL_SCORE_MSAC, SELECTION_SCORE_MSAC) measure the forward error only; they do not combine with RESIDUAL_SYMMETRIC\n";
+        return false;
+    }
+    if (!mh_set_residual_mode || !mh_set_residual_scope) {
+        if (residual != RESIDUAL_FORWARD) {
+            std::cerr << "Error: the engine library has no symmetric route (mh_set_residual_mode, mh_set_residual_scope)\n";
+            return false;
+        }
+    } else if (!Check(mh_set_residual_mode(engine, residual == RESIDUAL_SYMMETRIC ? MH_RESIDUAL_SYMMETRIC : MH_RESIDUAL_FORWARD), "mh_set_residual_mode") ||
+               !Check(mh_set_residual_scope(engine, residual == RESIDUAL_SYMMETRIC ? MH_RESIDUAL_SCOPE_ROUTE : MH_RESIDUAL_SCOPE_SCORE), "mh_set_residual_scope")) {
         return false;
     }
     // how the degenerate tail ranks its hypotheses
@@ -1394,6 +1415,10 @@ void mhh_set_fundamental_estimator(int mode, int max_samples, double confidence)
 static int g_data_term = -1;
 extern "C" __attribute__((visibility("default")))
 void mhh_set_data_term(int term) { g_data_term = term; }
+// MultiH::SetResidual for the next mhh_run_process calls (< 0: the class default)
+static int g_residual = -1;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_residual(int residual) { g_residual = residual; }
 // MultiH::SetTailScore for the next mhh_run_process calls (< 0: the class default)
 static int g_tail_score = -1;
 extern "C" __attribute__((visibility("default")))
@@ -1529,6 +1554,7 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     if (g_proposal_source != 0) mh.SetProposalSource(g_proposal_source, g_proposal_haf_members, g_proposal_haf_stride);
     if (g_fund_metric >= 0) mh.SetFundamentalMetric(g_fund_metric);
     if (g_data_term >= 0) mh.SetDataTerm(g_data_term);
+    if (g_residual >= 0) mh.SetResidual(g_residual);
     if (g_tail_score >= 0) mh.SetTailScore(g_tail_score);
     if (g_tail_refit >= 0) mh.SetTailRefit(g_tail_refit);
     if (g_tail_polish >= 0) mh.SetTailPolish(g_tail_polish);

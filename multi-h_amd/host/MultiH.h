@@ -152,6 +152,19 @@ public:
     // (the loop's energy is the engine's).  Any other value makes Process() fail with a message.
     enum { DATA_TERM_REFERENCE = 0, DATA_TERM_RISING = 1 };
     void SetDataTerm(int t) { data_term = t; }
+    // The error the whole route measures (mh_set_residual_mode with mh_set_residual_scope(MH_RESIDUAL_SCOPE_ROUTE),
+    // include/multih_hip.h): RESIDUAL_FORWARD is the reference's one-way transfer error |H p1 - p2|^2 (default);
+    // RESIDUAL_SYMMETRIC adds the backward term |adj(H) p2 - p1|^2.  Under it the route scores and selects its proposals,
+    // merges (the moments' inliers), labels (the data term's table) and finishes (the one-cluster exit, the degenerate tail)
+    // by the symmetric error at the caller's thr_hom, unscaled — the symmetric error of a well-fitted pair is about twice
+    // the forward one, so a caller who wants the same inlier band passes thr_hom * sqrt(2).  Process() applies mode and
+    // scope to its engine on every call, both ways, on every route (point-only, epipolar-free, sharded: the ranks' records
+    // carry the mode).  TAIL_SCORE_MSAC and SELECTION_SCORE_MSAC are forward-only: together with RESIDUAL_SYMMETRIC
+    // Process() refuses them up front with a message.  The refit, polish, reweight and compatibility modes (SetTailRefit,
+    // SetTailPolish, SetModelPolish, SetModelReweight*, SetEstimatorReweight*, SetCompatibilityFit) combine with it and keep
+    // measuring the forward error inside.  Any other value makes Process() fail with a message.
+    enum { RESIDUAL_FORWARD = 0, RESIDUAL_SYMMETRIC = 1 };
+    void SetResidual(int r) { residual = r; }
     // How the degenerate tail (HandleDegenerateCase) ranks its DLT hypotheses: TAIL_SCORE_COUNT by the inlier count (mh_score
     // and the first maximum; default), TAIL_SCORE_MSAC by the MSAC weight of include/multih_hip.h (mh_score_msac +
     // mh_select_best_msac: among hypotheses the one whose inliers fit best, the lowest index on ties; only the winning H is
@@ -336,6 +349,7 @@ protected:
     int estimator = ESTIMATOR_HAF;
     bool epipolar_free = false;
     int data_term = DATA_TERM_REFERENCE;
+    int residual = RESIDUAL_FORWARD;
     int tail_score = TAIL_SCORE_COUNT;
     int tail_refit = 0;
     int tail_polish = 0, model_polish = 0;

@@ -32,6 +32,10 @@
 //                                measured 256); "Compatibility check (4-point trials) .. clusters removed" reports it
 //                  [--data-term reference|rising]   the data term of the labeling (MultiH::SetDataTerm): reference, the default, is
 //                                the reference's dataEnergy (the cost falls as the fit gets worse); rising drops its `1.0 -`
+//                  [--residual forward|symmetric]   the error of the whole route (MultiH::SetResidual): forward, the default, is the
+//                                reference's one-way transfer error; symmetric adds the backward term through adj(H) — proposals
+//                                are scored and selected, clusters merged, points labelled and the tail finished by it at thrH,
+//                                unscaled; not together with --tail-score msac or --select-score msac
 //                  [--tail-score count|msac]   how the degenerate tail ranks its DLT hypotheses (MultiH::SetTailScore): count, the
 //                                default, by inlier count; msac by the fit-weighted score of mh_score_msac
 //                  [--tail-refit N]   the degenerate tail refits its winner to all its inliers, at most N rounds (MultiH::SetTailRefit;
@@ -140,7 +144,7 @@ int main(int argc, char** argv)
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
                      "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] [--f-estimator ls8|minimal] "
-                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--compat-fit dlt[:trials[:limit_scale]]] [--data-term reference|rising] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--reweight n[:scale]] [--estimator-reweight n[:scale]] [--reweight-auto n[:kappa]] [--estimator-reweight-auto n[:kappa]] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
+                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--compat-fit dlt[:trials[:limit_scale]]] [--data-term reference|rising] [--residual forward|symmetric] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--reweight n[:scale]] [--estimator-reweight n[:scale]] [--reweight-auto n[:kappa]] [--estimator-reweight-auto n[:kappa]] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
         return 2;
     }
     double thrF = 2.6, thrH = 2.2, locality = 0.005, lambda = 0.5;     // M/main.cpp:55-59
@@ -154,6 +158,7 @@ int main(int argc, char** argv)
     bool points_only = false, no_epipolar = false;
     int estimator = MultiH::ESTIMATOR_HAF;
     int data_term = MultiH::DATA_TERM_REFERENCE;
+    int residual = MultiH::RESIDUAL_FORWARD;
     int tail_score = MultiH::TAIL_SCORE_COUNT;
     int tail_refit = 0, tail_polish = 0, model_polish = 0;
     int compat_fit = MultiH::COMPAT_FIT_3PT, compat_trials = 501;
@@ -182,6 +187,11 @@ int main(int argc, char** argv)
             if (std::string(v) == "reference") data_term = MultiH::DATA_TERM_REFERENCE;
             else if (std::string(v) == "rising") data_term = MultiH::DATA_TERM_RISING;
             else { std::cerr << "--data-term: reference or rising\n"; return 2; }
+        }
+        else if (k == "--residual") {
+            if (std::string(v) == "forward") residual = MultiH::RESIDUAL_FORWARD;
+            else if (std::string(v) == "symmetric") residual = MultiH::RESIDUAL_SYMMETRIC;
+            else { std::cerr << "--residual: forward or symmetric\n"; return 2; }
         }
         else if (k == "--tail-score") {
             if (std::string(v) == "count") tail_score = MultiH::TAIL_SCORE_COUNT;
@@ -472,6 +482,7 @@ int main(int argc, char** argv)
     multiH->SetEpipolarFree(no_epipolar);
     multiH->SetCompatibilityFit(compat_fit, compat_trials, compat_limit_scale);
     multiH->SetDataTerm(data_term);
+    multiH->SetResidual(residual);
     multiH->SetTailScore(tail_score);
     multiH->SetTailRefit(tail_refit);
     multiH->SetTailPolish(tail_polish);
