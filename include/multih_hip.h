@@ -819,6 +819,42 @@ MH_API int mh_reestimate(mh_engine* e, const int* labels, double* H_out);
  * mh_set_epipolar. */
 MH_API int mh_labeling_step(mh_engine* e, int warm, int* labeling, double* energy, int* cycles);
 
+/* ---- the energy of a given labeling, and what joining two labels would do to it (csrc/merge_energy.hip) ----
+ * Notation of mh_data_cost / mh_expand: lam = 100 / lambda, T = thr_hom^2 * 81 / 16, potts = round(100 * lambda);
+ * cost(i, H) the engine's data term (mh_set_data_term) of the forward error — of the symmetric error under
+ * MH_RESIDUAL_SYMMETRIC with MH_RESIDUAL_SCOPE_ROUTE —, the arithmetic of mh_data_cost; w_pq the symmetric graph's
+ * multiplicity; an undirected neighbour pair counts once.  All sums are int64.  Neither call needs F or affinities.
+ *
+ * mh_labeling_energy: labels in -1..Nh-1 (anything else: MH_ERR_INVALID).
+ *     data   = sum_i (labels[i] < 0 ? round(lam * T) : cost(i, H[labels[i]]))
+ *     smooth = potts * sum w_pq [labels[p] != labels[q]]
+ *     energy = data + smooth;  parts (nullable) = { data, smooth }.
+ * On the labels mh_expand returns (minus one) this is mh_expand's energy.
+ *
+ * mh_merge_deltas: per pair (a, b), 0 <= a < b < Nh, with S_a = { i : labels[i] == a }, S_b likewise, S = S_a u S_b
+ * (a label outside 0..Nh-1 belongs to nobody):
+ *     H_ab     = fit(S), the N-point DLT stated under mh_refit_homography (the summation order of the per-label fits)
+ *     data_old = sum_{i in S} cost(i, H[labels[i]])        (the resident models)
+ *     data_new = sum_{i in S} cost(i, H_ab)
+ *     cut      = potts * sum w_pq over the undirected pairs with one end in S_a and the other in S_b
+ *     delta    = data_new - data_old - cut;   parts (nullable) = { |S|, data_old, data_new, cut } per pair
+ * status: MH_MERGE_OK, MH_MERGE_EMPTY (S_a or S_b has no member) or MH_MERGE_NO_FIT (fewer than 4 members, a scale or an entry
+ * of the fit not finite); not OK: delta = LLONG_MAX, the pair's H_out row and parts stay as the caller passed them.
+ * The contract: relabelling b -> a and replacing model a by H_ab changes mh_labeling_energy by exactly delta; the deltas of
+ * pairs that share no label add.  The call changes nothing in the engine: models, data-cost freshness, labels, counts and
+ * mode words stay.  The union's model is the N-point DLT whatever mh_set_estimator says.
+ * MH_ERR_INVALID: null engine; null labels / pairs / delta / status with npairs > 0; npairs < 0 or > 2^20; a pair with
+ * a >= b or a label outside [0, Nh).  MH_ERR_NOT_SET without correspondences, models or a neighbour graph.  npairs == 0:
+ * MH_OK, nothing is launched. */
+#define MH_MERGE_OK      0
+#define MH_MERGE_EMPTY   1
+#define MH_MERGE_NO_FIT  2
+#define MH_MERGE_MAX_PAIRS (1 << 20)
+MH_API int mh_merge_deltas(mh_engine* e, const int* labels /* n */, const int* pairs /* npairs x 2 */, int npairs,
+                           double* H_out /* npairs x 9, nullable */, long long* delta /* npairs */,
+                           long long* parts /* npairs x 4, nullable */, int* status /* npairs */);
+MH_API int mh_labeling_energy(mh_engine* e, const int* labels /* n */, long long* energy, long long* parts /* 2, nullable */);
+
 /* ---- device-side access (bench / multi-GPU plumbing) --------------------- */
 enum { MH_BUF_COUNTS = 0, MH_BUF_MODELS = 1, MH_BUF_RESIDUALS = 2, MH_BUF_LABELS = 3, MH_BUF_COST = 4, MH_BUF_GATHERED_SCORES = 5,
        MH_BUF_LABEL_COUNTS = 6 /* per label, its member count in the last re-estimation (mh_reestimate / mh_labeling_step) */,

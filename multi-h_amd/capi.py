@@ -22,6 +22,8 @@ ESTIMATORS = {"haf": 0, "3pt": 1, "dlt": 2}      # MH_ESTIMATOR_HAF, MH_ESTIMATO
 SAMPLER_UNIFORM, SAMPLER_LOCAL = 0, 1  # MH_SAMPLER_UNIFORM, MH_SAMPLER_LOCAL
 RESIDUAL_SCOPES = {"score": 0, "route": 1}      # MH_RESIDUAL_SCOPE_SCORE, MH_RESIDUAL_SCOPE_ROUTE
 DATA_TERMS = {"reference": 0, "rising": 1}      # MH_DATA_TERM_REFERENCE, MH_DATA_TERM_RISING
+MERGE_OK, MERGE_EMPTY, MERGE_NO_FIT = 0, 1, 2   # MH_MERGE_*
+MERGE_NO_DELTA = 2**63 - 1                      # LLONG_MAX: the delta of a pair that is not OK
 K_DLT4, K_RESIDUAL, K_SCORE, K_DATACOST, K_EXPAND, K_REESTIMATE, K_COSTMATRIX = 0, 1, 2, 3, 4, 5, 6
 
 # every symbol include/multih_hip.h declares (tests check the export table against this)
@@ -33,7 +35,7 @@ SYMBOLS = [
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
     "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_propose_haf", "mh_get_haf_support", "mh_propose_3pt", "mh_set_residual_mode", "mh_set_residual_scope", "mh_score", "mh_score_msac", "mh_select_best_msac",
     "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_select_greedy_msac", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_refit_homography", "mh_polish_homographies", "mh_reweight_homographies", "mh_label_residual_quantile", "mh_reweight_homographies_auto", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_compat_dlt_medians", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
-    "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_set_estimator_reweighting", "mh_set_estimator_reweighting_auto", "mh_reestimate", "mh_labeling_step", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
+    "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_set_estimator_reweighting", "mh_set_estimator_reweighting_auto", "mh_reestimate", "mh_labeling_step", "mh_merge_deltas", "mh_labeling_energy", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
     "mh_profile_get", "mh_set_tuning",
 ]
 
@@ -696,6 +698,31 @@ class Engine:
         self._check(self.lib.mh_labeling_step(self._h, int(bool(warm)), _p(lab, C.c_int), C.byref(energy),
                                               C.byref(cycles)))
         return lab, energy.value, cycles.value
+
+    def merge_deltas(self, labels, pairs, H_out=None):
+        """mh_merge_deltas: per pair (a, b) of labels the N-point fit of the union, the energy change `delta` of relabelling
+        b -> a with that fit as model a, parts = (|S|, data_old, data_new, cut) and status (MERGE_OK / MERGE_EMPTY /
+        MERGE_NO_FIT).  A pair that is not OK has delta = MERGE_NO_DELTA and keeps its rows of H_out / parts (zeros when no
+        H_out is given).  Returns (H [npairs, 9], delta int64, parts int64 [npairs, 4], status int32)."""
+        labels = _i32(labels)
+        pairs = _i32(pairs).reshape(-1, 2)
+        npairs = pairs.shape[0]
+        H = np.zeros((npairs, 9), dtype=np.float64) if H_out is None else H_out
+        if H.dtype != np.float64 or H.shape != (npairs, 9) or not H.flags.c_contiguous:
+            raise ValueError("H_out must be a C-contiguous float64 array of shape (npairs, 9)")
+        delta = np.zeros(npairs, dtype=np.int64)
+        parts = np.zeros((npairs, 4), dtype=np.int64)
+        status = np.zeros(npairs, dtype=np.int32)
+        self._check(self.lib.mh_merge_deltas(self._h, _p(labels, C.c_int), _p(pairs, C.c_int), npairs, _p(H, C.c_double),
+                                             _p(delta, C.c_longlong), _p(parts, C.c_longlong), _p(status, C.c_int)))
+        return H, delta, parts, status
+
+    def labeling_energy(self, labels):
+        """mh_labeling_energy: (energy, data, smooth) of the labeling (-1..Nh-1 per point) under the resident models."""
+        labels = _i32(labels)
+        energy, parts = C.c_longlong(0), (C.c_longlong * 2)()
+        self._check(self.lib.mh_labeling_energy(self._h, _p(labels, C.c_int), C.byref(energy), parts))
+        return int(energy.value), int(parts[0]), int(parts[1])
 
     # -- device access / profiling -----------------------------------------
     def device_buffer(self, which: int):

@@ -221,6 +221,9 @@ struct mh_engine : ResidentBatch {                    // (e->m, e->origin, e->ha
     DevBuf<int> rw_labels, rw_info;           // mh_reweight_homographies: the labels (n) and per model members, support, rounds, status,
     DevBuf<double> rw_H, rw_gain;             // H_in and H_out (2 x m x 9), W before and after (m x 2); mh_reweight_homographies_auto: then the
                                               //   scales (m x 2); mh_label_residual_quantile: the labels, H, d2_out in rw_gain, info
+    DevBuf<int> me_labels, me_pairs, me_status;   // mh_merge_deltas / mh_labeling_energy: the labels (n), the pairs (npairs x 2), their status,
+    DevBuf<double> me_H;                      // the unions' fits (npairs x 9),
+    DevBuf<long long> me_out;                 // per pair |S|, data_old, data_new, cut, delta; mh_labeling_energy: data, smooth
     DevBuf<double> moments, min_eig;
     DevBuf<double> cp_pts, cp_H, cp_out;     // mh_compat_trial_stats staging
     DevBuf<int> cp_begin, cp_tri;

@@ -571,4 +571,71 @@ int mh_labeling_step(mh_engine* e, int warm, int* labeling, double* energy, int*
     });
 }
 
+static_assert(MH_MERGE_OK == MERGE_OK && MH_MERGE_EMPTY == MERGE_EMPTY && MH_MERGE_NO_FIT == MERGE_NO_FIT, "status codes of merge_energy.hip");
+
+// Writes the me_ staging buffers and nothing else of the engine (the definition: include/multih_hip.h).
+int mh_merge_deltas(mh_engine* e, const int* labels, const int* pairs, int npairs, double* H_out, long long* delta, long long* parts,
+                    int* status)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (npairs < 0 || npairs > MH_MERGE_MAX_PAIRS) return fail(MH_ERR_INVALID, "npairs outside [0, 2^20]");
+    if (npairs > 0 && (!labels || !pairs || !delta || !status)) return fail(MH_ERR_INVALID, "null argument");
+    int rc = require_models(e);
+    if (rc) return rc;
+    if (!e->have_graph) return fail(MH_ERR_NOT_SET, "neighbour graph is not set");
+    if (npairs == 0) return MH_OK;
+    for (int k = 0; k < npairs; ++k) {
+        const int a = pairs[2 * k], b = pairs[2 * k + 1];
+        if (a < 0 || b >= e->m || a >= b) return fail(MH_ERR_INVALID, "a pair is not 0 <= a < b < Nh");
+    }
+    const size_t np = (size_t)npairs;
+    HIPCHK(e->me_labels.reserve(e->n)); HIPCHK(e->me_pairs.reserve(2 * np)); HIPCHK(e->me_status.reserve(np));
+    HIPCHK(e->me_H.reserve(9 * np)); HIPCHK(e->me_out.reserve(5 * np));
+    HIPCHK(hipMemcpyAsync(e->me_labels.p, labels, sizeof(int) * e->n, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->me_pairs.p, pairs, sizeof(int) * 2 * np, hipMemcpyHostToDevice, e->stream));
+    const Graph g{ e->d_rowptr.p, e->d_col.p, e->d_w.p, e->d_rev.p, e->n, e->g_nnz, e->d_order.p, e->d_wsum.p };
+    HIPCHK(launch_merge_pairs(e->pts(), e->me_labels.p, e->H.p, e->me_pairs.p, npairs, g, e->lambda, e->thr_H * e->thr_H, e->me_H.p,
+                              e->me_out.p, e->me_status.p, e->stream, e->data_term == MH_DATA_TERM_RISING, e->route_symmetric()));
+    std::vector<double> h_H(H_out ? 9 * np : 0);
+    std::vector<long long> h_out(5 * np);
+    HIPCHK(hipMemcpyAsync(status, e->me_status.p, sizeof(int) * np, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(h_out.data(), e->me_out.p, sizeof(long long) * 5 * np, hipMemcpyDeviceToHost, e->stream));
+    if (H_out) HIPCHK(hipMemcpyAsync(h_H.data(), e->me_H.p, sizeof(double) * 9 * np, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (size_t k = 0; k < np; ++k) {            // a pair that is not OK leaves its rows of H_out and parts as they were
+        if (status[k] != MH_MERGE_OK) { delta[k] = 0x7fffffffffffffffll; continue; }
+        delta[k] = h_out[5 * k + 4];
+        if (parts) std::memcpy(parts + 4 * k, &h_out[5 * k], sizeof(long long) * 4);
+        if (H_out) std::memcpy(H_out + 9 * k, &h_H[9 * k], sizeof(double) * 9);
+    }
+    return MH_OK;
+    });
+}
+
+int mh_labeling_energy(mh_engine* e, const int* labels, long long* energy, long long* parts)
+{
+    return guarded([&]() -> int {
+    int rc = require_models(e);
+    if (rc) return rc;
+    if (!e->have_graph) return fail(MH_ERR_NOT_SET, "neighbour graph is not set");
+    if (!labels || !energy) return fail(MH_ERR_INVALID, "null argument");
+    for (int i = 0; i < e->n; ++i)
+        if (labels[i] < -1 || labels[i] >= e->m) return fail(MH_ERR_INVALID, "label out of range -1..Nh-1");
+    HIPCHK(e->me_labels.reserve(e->n)); HIPCHK(e->me_out.reserve(2));
+    HIPCHK(hipMemcpyAsync(e->me_labels.p, labels, sizeof(int) * e->n, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(e->me_out.p, 0, sizeof(long long) * 2, e->stream));
+    const Graph g{ e->d_rowptr.p, e->d_col.p, e->d_w.p, e->d_rev.p, e->n, e->g_nnz, e->d_order.p, e->d_wsum.p };
+    HIPCHK(launch_labeling_energy(e->pts(), e->me_labels.p, e->H.p, g, e->lambda, e->thr_H * e->thr_H,
+                                  reinterpret_cast<unsigned long long*>(e->me_out.p), e->stream, e->data_term == MH_DATA_TERM_RISING,
+                                  e->route_symmetric()));
+    long long out[2] = { 0, 0 };
+    HIPCHK(hipMemcpyAsync(out, e->me_out.p, sizeof(long long) * 2, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    *energy = out[0] + out[1];
+    if (parts) { parts[0] = out[0]; parts[1] = out[1]; }
+    return MH_OK;
+    });
+}
+
 } // extern "C"

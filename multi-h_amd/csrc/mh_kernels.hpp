@@ -283,6 +283,17 @@ struct Graph {              // symmetric weighted CSR in HBM
     const int* wsum;        // n    sum of w over the site's row: bounds every n-link total of the site (expand.hip, k_move_setup)
 };
 
+// --- merge_energy.hip: the energy of a labeling, the energy change of joining two labels (mh_labeling_energy, mh_merge_deltas) ---
+constexpr int MERGE_OK = 0, MERGE_EMPTY = 1, MERGE_NO_FIT = 2;       // MH_MERGE_*
+// per pair: status; for an OK pair H_out (9 doubles) and out = { |S|, data_old, data_new, cut, delta }.  labels: n ints, any
+// value; pairs: 0 <= a < b < Nh (the caller's check: they index H)
+hipError_t launch_merge_pairs(const Points& p, const int* labels, const double* H, const int* pairs, int npairs, const Graph& g,
+                              double lambda, double thr2, double* H_out, long long* out /* npairs x 5 */, int* status, hipStream_t s,
+                              int rising, int symmetric);
+// out[0] += data, out[1] += smooth (cleared by the caller).  labels: n ints in -1..Nh-1 (the caller's check: they index H)
+hipError_t launch_labeling_energy(const Points& p, const int* labels, const double* H, const Graph& g, double lambda, double thr2,
+                                  unsigned long long* out, hipStream_t s, int rising, int symmetric);
+
 constexpr int EXPAND_MAX_CTX = 16;
 constexpr int EXPAND_FLAG_WORDS = 896;     // device control block (expand_ctl.hpp)
 constexpr int EXPAND_HOST_WORDS = 32;      // its head, mirrored to the host

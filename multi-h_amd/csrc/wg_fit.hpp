@@ -1,5 +1,5 @@
 // wg_fit.hpp — what the per-model fit kernels share: k_fund_refit, k_moments, k_haf_reestimate, k_3pt_reestimate, k_refit_h,
-// k_polish_h, k_dlt_reestimate, k_reweight_h and k_autoscale_reweight_h (k_label_quantile: the member loop).  One 256-thread workgroup per model, strided passes over the points, thread 0 solves.
+// k_polish_h, k_dlt_reestimate, k_reweight_h and k_autoscale_reweight_h (k_label_quantile: the member loop; k_merge_pair: a pair of labels per workgroup).  One 256-thread workgroup per model, strided passes over the points, thread 0 solves.
 //
 // The order of every FP64 sum, stated here once: thread t adds its members t, t + 256, ... in ascending index from 0.0, then
 // the binary tree v[t] += v[t + s], s = 128 .. 1, over the workgroup's LDS buffer (wg_tree).  The twins (oracle/mh_oracle.cpp
@@ -72,6 +72,33 @@ __device__ __forceinline__ void for_label_members(const int* __restrict__ labels
             const int j = __builtin_ctz(match);
             match &= match - 1u;
             f((int)(n0 + (Index)256 * j));
+        }
+    }
+}
+
+// The two-label form (k_merge_pair): the members of label a OR label b, the same trips and the same ascending order; f gets the
+// point and whether it carries b.
+template <int BATCH, class Index, class Fn>
+__device__ __forceinline__ void for_pair_members(const int* __restrict__ labels, int N, int a, int b, int t, Fn&& f)
+{
+    for (Index n0 = t; n0 < N; n0 += (Index)256 * BATCH) {
+        int lb[BATCH];
+#pragma unroll
+        for (int j = 0; j < BATCH; ++j) {
+            const Index i = n0 + (Index)256 * j;
+            lb[j] = labels[i < N ? i : 0];
+        }
+        unsigned match = 0, is_b = 0;            // bit j: point n0 + 256 j carries a or b / carries b
+#pragma unroll
+        for (int j = 0; j < BATCH; ++j) {
+            const bool in = n0 + (Index)256 * j < N;
+            match |= (in && (lb[j] == a || lb[j] == b)) ? 1u << j : 0u;
+            is_b |= (in && lb[j] == b) ? 1u << j : 0u;
+        }
+        while (match) {                          // ascending j = ascending point index
+            const int j = __builtin_ctz(match);
+            match &= match - 1u;
+            f((int)(n0 + (Index)256 * j), (is_b >> j & 1u) != 0u);
         }
     }
 }

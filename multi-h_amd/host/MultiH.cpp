@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
 #include <mutex>
 
@@ -54,6 +55,9 @@
 #pragma weak mh_propose_3pt
 // ... and for the compatibility check without F (SetCompatibilityFit(COMPAT_FIT_DLT)): without its entry point that mode fails with a message.
 #pragma weak mh_compat_dlt_medians
+// ... and for the energy-tested merge (SetMergeMode(MERGE_ENERGY)): the same.
+#pragma weak mh_merge_deltas
+#pragma weak mh_labeling_energy
 
 namespace {
 
@@ -378,6 +382,14 @@ bool MultiH::Run(bool points_only)
             return false;
         }
     } else if (!Check(mh_set_estimator(engine, est), "mh_set_estimator")) {
+        return false;
+    }
+    if (merge_mode != MERGE_MEAN_SHIFT && merge_mode != MERGE_ENERGY) {
+        std::cerr << "Error: unknown merge mode (SetMergeMode)\n";
+        return false;
+    }
+    if (merge_mode == MERGE_ENERGY && (!mh_merge_deltas || !mh_labeling_energy)) {
+        std::cerr << "Error: the engine library has no energy-tested merge (mh_merge_deltas, mh_labeling_energy)\n";
         return false;
     }
     // the data term of the labeling (sticky on the engine, and engines are reused)
@@ -1093,6 +1105,9 @@ void MultiH::ClusterMergingAndLabeling()
     double lastEnergy = INT_MAX;
     int not_changed_number = 0;
     labeling_steps_run = 0;
+    labeling_is_current = false;
+    merge_log_open = false;
+    merge_log.clear();
 
     const bool timing = std::getenv("MULTIH_TIMING") != nullptr;                        // diagnostic: where the loop's time goes
     double merge_s = 0.0, label_s = 0.0;
@@ -1101,6 +1116,7 @@ void MultiH::ClusterMergingAndLabeling()
     };
     while (iteration_number++ < MAX_ITERATION_NUMBER) {                                 // :267
         bool changed = false;
+        loop_iteration = iteration_number;
         const auto t_merge = std::chrono::system_clock::now();
         const bool merged = MergingStep(changed);
         merge_s += seconds_since(t_merge);
@@ -1221,6 +1237,7 @@ int mhh_merging_step(mh_engine* engine, const double* H, int nh, const double* F
 
 bool MultiH::MergingStep(bool& changed)
 {
+    if (merge_mode == MERGE_ENERGY) return MergingStepEnergy(changed);
     const int nh = static_cast<int>(cluster_homographies.size());
     changed = false;
     if (nh == 0) return true;
@@ -1241,13 +1258,83 @@ bool MultiH::MergingStep(bool& changed)
     return true;
 }
 
+// MergingStep under MERGE_ENERGY (MultiH.h, SetMergeMode): the collinearity filter of MergingStepOnEngine on the models as they
+// stand, and — once a labeling exists — in front of it the joins that lower the labeling's energy.
+bool MultiH::MergingStepEnergy(bool& changed)
+{
+    const int nh = static_cast<int>(cluster_homographies.size());
+    const int N = static_cast<int>(labeling.size());
+    changed = false;
+    if (nh == 0) return true;
+    std::vector<double> H(9 * (size_t)nh);
+    for (int i = 0; i < nh; ++i) {
+        const double* p = reinterpret_cast<const double*>(cluster_homographies[i].data);
+        for (int k = 0; k < 9; ++k) H[9 * (size_t)i + k] = p[k];
+    }
+    int count = nh;
+    MergeLogRecord rec;
+    const bool evaluate = labeling_is_current;
+    if (!Check(mh_set_models(engine, H.data(), nh), "MergingStep (mh_set_models)")) return false;
+    if (evaluate) {
+        rec.iteration = loop_iteration;
+        rec.models_before = nh;
+        const std::vector<int> pairs = multih::MergePairList(H.data(), nh);
+        const int npairs = static_cast<int>(pairs.size() / 2);
+        rec.pairs = npairs;
+        if (!Check(mh_labeling_energy(engine, labeling.data(), &rec.E_before, nullptr), "MergingStep (mh_labeling_energy)")) return false;
+        std::vector<double> H_ab(9 * (size_t)npairs);
+        std::vector<long long> delta(npairs);
+        std::vector<int> status(npairs);
+        if (!Check(mh_merge_deltas(engine, labeling.data(), pairs.data(), npairs, H_ab.data(), delta.data(), nullptr, status.data()),
+                   "MergingStep (mh_merge_deltas)"))
+            return false;
+        const std::vector<int> accepted = multih::SelectMerges(pairs.data(), delta.data(), status.data(), npairs, nh);
+        for (int k : accepted) rec.sum_delta += delta[k];
+        rec.merges_accepted = static_cast<long long>(accepted.size());
+        count = multih::ApplyMerges(pairs.data(), H_ab.data(), accepted, N, labeling.data(), H.data(), nh);
+        if (count != nh && !Check(mh_set_models(engine, H.data(), count), "MergingStep (mh_set_models)")) return false;
+    }
+    // the collinearity filter (M/MultiH.cpp:446-463) on the models as they stand
+    std::vector<double> mom(6 * (size_t)count), mineig(count);
+    if (!Check(mh_inlier_moments(engine, threshold_homography * threshold_homography, mom.data(), mineig.data()), "MergingStep (mh_inlier_moments)"))
+        return false;
+    std::vector<char> remove(count, 0);
+    int filtered = 0;
+    for (int i = 0; i < count; ++i)
+        if (mineig[i] < straightness_threshold || static_cast<int>(mom[6 * (size_t)i]) < 3) { remove[i] = 1; ++filtered; }
+    if (filtered) count = multih::RemoveModels(remove, N, labeling.data(), H.data(), count);
+    if (evaluate) {
+        rec.models_filtered = filtered;
+        rec.E_start = rec.E_before + rec.sum_delta;
+        if (count > 0 && (filtered || count != nh)) {
+            if (!Check(mh_set_models(engine, H.data(), count), "MergingStep (mh_set_models)")) return false;
+            if (!Check(mh_labeling_energy(engine, labeling.data(), &rec.E_start, nullptr), "MergingStep (mh_labeling_energy)")) return false;
+        }
+        merge_log.push_back(rec);
+        merge_log_open = true;
+    }
+    changed = count != nh;
+    if (changed || evaluate) {
+        cluster_homographies.clear();
+        for (int i = 0; i < count; ++i) cluster_homographies.push_back(MatFrom9(&H[9 * (size_t)i]));
+    }
+    return true;
+}
+
 bool MultiH::LabelingStep(double& energy, bool changed)
 {
     energy = 0;
     if (!UploadModels()) return false;
     int cycles = 0;
-    if (!Check(mh_labeling_step(engine, changed ? 0 : 1, labeling.data(), &energy, &cycles), "mh_labeling_step"))
+    // under MERGE_ENERGY the merges keep the labeling valid for the models: warm whenever there is one
+    const int warm = (merge_mode == MERGE_ENERGY && labeling_is_current) ? 1 : (changed ? 0 : 1);
+    if (!Check(mh_labeling_step(engine, warm, labeling.data(), &energy, &cycles), "mh_labeling_step"))
         return false;
+    labeling_is_current = true;
+    if (merge_log_open) {
+        merge_log.back().E_expansion = static_cast<long long>(energy);
+        merge_log_open = false;
+    }
     return DownloadModels(static_cast<int>(cluster_homographies.size()));
 }
 
@@ -1411,6 +1498,21 @@ void mhh_set_fundamental_estimator(int mode, int max_samples, double confidence)
 {
     g_fund_estimator = mode; g_fund_max_samples = max_samples; g_fund_confidence = confidence;
 }
+// MultiH::SetMergeMode for the next mhh_run_process calls (< 0: the class default), and the merge log of the last one
+static int g_merge_mode = -1;
+static std::vector<MultiH::MergeLogRecord> g_merge_log;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_merge_mode(int mode) { g_merge_mode = mode; }
+// records_out: capacity x 9 long long (iteration, models before, pairs, merges accepted, models filtered, E_before, sum_delta,
+// E_start, E_expansion), nullable; returns the number of records of the last mhh_run_process
+extern "C" __attribute__((visibility("default")))
+int mhh_get_merge_log(long long* records_out, int capacity)
+{
+    static_assert(sizeof(MultiH::MergeLogRecord) == 9 * sizeof(long long), "a record travels as 9 long long");
+    for (int i = 0; records_out && i < capacity && i < (int)g_merge_log.size(); ++i)
+        std::memcpy(records_out + 9 * (size_t)i, &g_merge_log[i], sizeof(MultiH::MergeLogRecord));
+    return (int)g_merge_log.size();
+}
 // MultiH::SetDataTerm for the next mhh_run_process calls (< 0: the class default)
 static int g_data_term = -1;
 extern "C" __attribute__((visibility("default")))
@@ -1554,6 +1656,8 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     if (g_proposal_source != 0) mh.SetProposalSource(g_proposal_source, g_proposal_haf_members, g_proposal_haf_stride);
     if (g_fund_metric >= 0) mh.SetFundamentalMetric(g_fund_metric);
     if (g_data_term >= 0) mh.SetDataTerm(g_data_term);
+    if (g_merge_mode >= 0) mh.SetMergeMode(g_merge_mode);
+    g_merge_log.clear();
     if (g_residual >= 0) mh.SetResidual(g_residual);
     if (g_tail_score >= 0) mh.SetTailScore(g_tail_score);
     if (g_tail_refit >= 0) mh.SetTailRefit(g_tail_refit);
@@ -1597,5 +1701,6 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     if (energy) *energy = mh.GetEnergy();
     if (loop_seconds) *loop_seconds = mh.GetLastLoopSeconds();
     g_labeling_steps = mh.GetLabelingStepsRun();
+    g_merge_log = mh.GetMergeLog();
     return k;
 }

@@ -305,6 +305,27 @@ public:
     {
         compat_fit = mode; compat_trials = trials; compat_limit_scale = limit_scale;
     }
+    // How MergingStep decides.  MERGE_MEAN_SHIFT (default): the reference's rule — mean shift over the models' 6-D features, a
+    // rebuilt model per mode, the collinearity filter (M/MultiH.cpp:352-471); nothing changes anywhere.  MERGE_ENERGY: the PEARL
+    // merge move.  While no LabelingStep has run in this Process() the models only pass the collinearity filter; afterwards the
+    // step evaluates pairs of labels (all while there are at most 64 models, else each label's 8 nearest in the feature space)
+    // with mh_merge_deltas, joins those whose union — with its own N-point DLT refit — LOWERS the labeling's energy
+    // (multih::SelectMerges / ApplyMerges: best first, no label twice per step), runs the same filter (a filtered model's
+    // members become outliers) and sets `changed` iff the model count changed.  The LabelingStep that follows starts warm from
+    // that labeling.  Needs no F: it runs on the route with F and under SetEpipolarFree alike, replicated on every rank of a
+    // sharded run.  Limits: the union's model is the N-point DLT whatever SetEstimator says (the next LabelingStep re-estimates
+    // with the route's estimator); no label cost; no joins of three labels at once.  Any other value makes Process() fail.
+    enum { MERGE_MEAN_SHIFT = 0, MERGE_ENERGY = 1 };
+    void SetMergeMode(int m) { merge_mode = m; }
+    // One record per MergingStep that evaluated merges in the last Process() (empty under MERGE_MEAN_SHIFT): E_before =
+    // mh_labeling_energy in front of the merges, sum_delta the accepted deltas' sum, E_start = mh_labeling_energy of what the
+    // LabelingStep starts from (= E_before + sum_delta when nothing was filtered), E_expansion the energy that step returned
+    // (-1 when none followed).
+    struct MergeLogRecord {
+        long long iteration = 0, models_before = 0, pairs = 0, merges_accepted = 0, models_filtered = 0;
+        long long E_before = 0, sum_delta = 0, E_start = 0, E_expansion = -1;
+    };
+    const std::vector<MergeLogRecord>& GetMergeLog() const { return merge_log; }
     void SetDevice(int d) { device = d; }
     // schedule knob of the engine (mh_set_tuning; results never depend on it), applied when the engine is created
     void SetEngineTuning(int key, int value) { engine_tuning.emplace_back(key, value); }
@@ -400,6 +421,12 @@ protected:
                        std::vector<unsigned char>& mask);
     void ClusterMergingAndLabeling();     // M/MultiH.cpp:224-312
     bool MergingStep(bool& changed);      // :352-471
+    bool MergingStepEnergy(bool& changed);             // SetMergeMode(MERGE_ENERGY)
+    int merge_mode = MERGE_MEAN_SHIFT;
+    std::vector<MergeLogRecord> merge_log;
+    bool labeling_is_current = false;     // a LabelingStep has run in this Process() and `labeling` is valid for cluster_homographies
+    bool merge_log_open = false;          // the last record waits for its LabelingStep's energy
+    int loop_iteration = 0;
     bool LabelingStep(double& energy, bool changed);   // :513-602
     void ComputeInliersOfHomography(int idx);          // :743-768
     void HandleDegenerateCase();                       // :719-741 (single best DLT model)

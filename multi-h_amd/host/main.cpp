@@ -32,6 +32,10 @@
 //                                measured 256); "Compatibility check (4-point trials) .. clusters removed" reports it
 //                  [--data-term reference|rising]   the data term of the labeling (MultiH::SetDataTerm): reference, the default, is
 //                                the reference's dataEnergy (the cost falls as the fit gets worse); rising drops its `1.0 -`
+//                  [--merge meanshift|energy]   how MergingStep decides (MultiH::SetMergeMode): meanshift, the default, is the
+//                                reference's rule; energy joins two labels only where the union with its own N-point refit lowers
+//                                the labeling's energy (mh_merge_deltas), and the LabelingStep behind it starts warm; "Energy merges:"
+//                                reports the steps' totals
 //                  [--residual forward|symmetric]   the error of the whole route (MultiH::SetResidual): forward, the default, is the
 //                                reference's one-way transfer error; symmetric adds the backward term through adj(H) — proposals
 //                                are scored and selected, clusters merged, points labelled and the tail finished by it at thrH,
@@ -144,7 +148,7 @@ int main(int argc, char** argv)
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
                      "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] [--f-estimator ls8|minimal] "
-                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--compat-fit dlt[:trials[:limit_scale]]] [--data-term reference|rising] [--residual forward|symmetric] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--reweight n[:scale]] [--estimator-reweight n[:scale]] [--reweight-auto n[:kappa]] [--estimator-reweight-auto n[:kappa]] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
+                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--compat-fit dlt[:trials[:limit_scale]]] [--data-term reference|rising] [--merge meanshift|energy] [--residual forward|symmetric] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--reweight n[:scale]] [--estimator-reweight n[:scale]] [--reweight-auto n[:kappa]] [--estimator-reweight-auto n[:kappa]] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
         return 2;
     }
     double thrF = 2.6, thrH = 2.2, locality = 0.005, lambda = 0.5;     // M/main.cpp:55-59
@@ -159,6 +163,7 @@ int main(int argc, char** argv)
     int estimator = MultiH::ESTIMATOR_HAF;
     int data_term = MultiH::DATA_TERM_REFERENCE;
     int residual = MultiH::RESIDUAL_FORWARD;
+    int merge_mode = MultiH::MERGE_MEAN_SHIFT;
     int tail_score = MultiH::TAIL_SCORE_COUNT;
     int tail_refit = 0, tail_polish = 0, model_polish = 0;
     int compat_fit = MultiH::COMPAT_FIT_3PT, compat_trials = 501;
@@ -187,6 +192,11 @@ int main(int argc, char** argv)
             if (std::string(v) == "reference") data_term = MultiH::DATA_TERM_REFERENCE;
             else if (std::string(v) == "rising") data_term = MultiH::DATA_TERM_RISING;
             else { std::cerr << "--data-term: reference or rising\n"; return 2; }
+        }
+        else if (k == "--merge") {
+            if (std::string(v) == "meanshift") merge_mode = MultiH::MERGE_MEAN_SHIFT;
+            else if (std::string(v) == "energy") merge_mode = MultiH::MERGE_ENERGY;
+            else { std::cerr << "--merge: meanshift or energy\n"; return 2; }
         }
         else if (k == "--residual") {
             if (std::string(v) == "forward") residual = MultiH::RESIDUAL_FORWARD;
@@ -482,6 +492,7 @@ int main(int argc, char** argv)
     multiH->SetEpipolarFree(no_epipolar);
     multiH->SetCompatibilityFit(compat_fit, compat_trials, compat_limit_scale);
     multiH->SetDataTerm(data_term);
+    multiH->SetMergeMode(merge_mode);
     multiH->SetResidual(residual);
     multiH->SetTailScore(tail_score);
     multiH->SetTailRefit(tail_refit);
@@ -527,6 +538,14 @@ int main(int argc, char** argv)
     }
     printf("[Multi-H] %d clusters, %d iterations, energy %.0f\n", multiH->GetClusterNumber(), iterationNum,
            multiH->GetEnergy());
+    if (merge_mode == MultiH::MERGE_ENERGY) {
+        long long pairs = 0, accepted = 0, filtered = 0, sum_delta = 0;
+        for (const MultiH::MergeLogRecord& r : multiH->GetMergeLog()) {
+            pairs += r.pairs; accepted += r.merges_accepted; filtered += r.models_filtered; sum_delta += r.sum_delta;
+        }
+        printf("[Multi-H] Energy merges: %d steps, %lld pairs evaluated, %lld joined, %lld models filtered, sum of deltas %lld\n",
+               (int)multiH->GetMergeLog().size(), pairs, accepted, filtered, sum_delta);
+    }
 
     std::vector<cv::Point2d> src_points, dst_points;
     std::vector<cv::Mat> affinities;

@@ -877,10 +877,106 @@ int MergeCandidatesMedoid(const double* H, int nh, double thr_h, uint64_t seed, 
     return static_cast<int>(cand.size() / 9);
 }
 
+// ---- the energy-tested merge (MultiH::SetMergeMode(MERGE_ENERGY)) ----
+
+std::vector<int> SelectMerges(const int* pairs, const long long* delta, const int* status, int npairs, int nh)
+{
+    std::vector<int> order;
+    for (int k = 0; k < npairs; ++k)
+        if (status[k] == 0 && delta[k] < 0) order.push_back(k);
+    std::sort(order.begin(), order.end(), [&](int x, int y) {
+        if (delta[x] != delta[y]) return delta[x] < delta[y];
+        if (pairs[2 * x] != pairs[2 * y]) return pairs[2 * x] < pairs[2 * y];
+        if (pairs[2 * x + 1] != pairs[2 * y + 1]) return pairs[2 * x + 1] < pairs[2 * y + 1];
+        return x < y;
+    });
+    std::vector<char> used(nh > 0 ? nh : 0, 0);
+    std::vector<int> accepted;
+    for (int k : order) {
+        const int a = pairs[2 * k], b = pairs[2 * k + 1];
+        if (a < 0 || b >= nh || a >= b || used[a] || used[b]) continue;
+        used[a] = used[b] = 1;
+        accepted.push_back(k);
+    }
+    return accepted;
+}
+
+int ApplyMerges(const int* pairs, const double* H_ab, const std::vector<int>& accepted, int n, int* labels, double* H, int nh)
+{
+    std::vector<char> remove(nh, 0);
+    std::vector<int> into(nh);
+    for (int l = 0; l < nh; ++l) into[l] = l;
+    for (int k : accepted) {
+        const int a = pairs[2 * k], b = pairs[2 * k + 1];
+        into[b] = a;
+        remove[b] = 1;
+        std::memcpy(H + 9 * (size_t)a, H_ab + 9 * (size_t)k, 9 * sizeof(double));
+    }
+    for (int j = 0; j < n; ++j)
+        if (labels[j] >= 0 && labels[j] < nh) labels[j] = into[labels[j]];
+    return RemoveClusters(remove, n, labels, H, nh);
+}
+
+int RemoveModels(const std::vector<char>& remove, int n, int* labels, double* H, int nh) { return RemoveClusters(remove, n, labels, H, nh); }
+
+std::vector<int> MergePairList(const double* H, int nh, int all_up_to, int nearest)
+{
+    std::vector<int> pairs;
+    if (nh <= all_up_to) {
+        for (int a = 0; a < nh; ++a)
+            for (int b = a + 1; b < nh; ++b) { pairs.push_back(a); pairs.push_back(b); }
+        return pairs;
+    }
+    std::vector<double> feat(6 * (size_t)nh);
+    HomographyFeatures(H, nh, feat.data());
+    std::vector<std::pair<int, int>> found;
+    std::vector<std::pair<double, int>> d(nh);
+    for (int a = 0; a < nh; ++a) {
+        for (int b = 0; b < nh; ++b) {
+            double s = 0.0;
+            for (int k = 0; k < 6; ++k) { const double t = feat[6 * (size_t)a + k] - feat[6 * (size_t)b + k]; s += t * t; }
+            d[b] = { b == a || !(s == s) ? std::numeric_limits<double>::infinity() : s, b };       // itself and a NaN distance come last
+        }
+        const int take = std::min(nearest, nh - 1);
+        std::partial_sort(d.begin(), d.begin() + take, d.end());
+        for (int q = 0; q < take; ++q)
+            if (d[q].second != a) found.emplace_back(std::min(a, d[q].second), std::max(a, d[q].second));
+    }
+    std::sort(found.begin(), found.end());
+    found.erase(std::unique(found.begin(), found.end()), found.end());
+    for (const auto& p : found) { pairs.push_back(p.first); pairs.push_back(p.second); }
+    return pairs;
+}
+
 } // namespace multih
 
 // ---- C hooks for the CPU-side tests (no GPU needed) ----------------------------
 extern "C" {
+
+// SelectMerges for tests: accepted_out (capacity npairs) receives the accepted pairs' positions in acceptance order; returns their number
+__attribute__((visibility("default")))
+int mhh_select_merges(const int* pairs, const long long* delta, const int* status, int npairs, int nh, int* accepted_out)
+{
+    const std::vector<int> acc = multih::SelectMerges(pairs, delta, status, npairs, nh);
+    std::copy(acc.begin(), acc.end(), accepted_out);
+    return (int)acc.size();
+}
+
+// ApplyMerges for tests: labels (n) and H (nh x 9) in place; returns the new model count
+__attribute__((visibility("default")))
+int mhh_apply_merges(const int* pairs, const double* H_ab, const int* accepted, int n_accepted, int n, int* labels, double* H, int nh)
+{
+    return multih::ApplyMerges(pairs, H_ab, std::vector<int>(accepted, accepted + n_accepted), n, labels, H, nh);
+}
+
+// MergePairList for tests: pairs_out has capacity for nh * min(nearest, nh - 1) (or nh (nh - 1) / 2) pairs; returns their number
+__attribute__((visibility("default")))
+int mhh_merge_pair_list(const double* H, int nh, int all_up_to, int nearest, int* pairs_out)
+{
+    const std::vector<int> p = multih::MergePairList(H, nh, all_up_to, nearest);
+    std::copy(p.begin(), p.end(), pairs_out);
+    return (int)(p.size() / 2);
+}
 
 // MergeCandidatesMedoid for tests: mhh_merge_candidates' arguments without F
 __attribute__((visibility("default")))

@@ -62,6 +62,21 @@ int MergeCandidatesMedoid(const double* H /* nh x 9 */, int nh, double thr_h, ui
                           std::vector<double>* modes, std::vector<double>& cand, std::vector<int>* cand_mode = nullptr,
                           uint64_t* draws = nullptr);
 
+// ---- the energy-tested merge (MultiH::SetMergeMode(MERGE_ENERGY); the deltas: mh_merge_deltas, include/multih_hip.h) ----
+// Which of the evaluated pairs are joined in one step: the pairs with status 0 (MH_MERGE_OK) sorted by (delta, a, b) ascending, a
+// pair accepted while delta < 0 and neither of its labels has been used in this step (the deltas of pairs that share no label
+// add).  Returns the accepted pairs' positions in `pairs`, in acceptance order.
+std::vector<int> SelectMerges(const int* pairs /* npairs x 2, a < b */, const long long* delta, const int* status, int npairs, int nh);
+// The accepted joins applied: the members of b take label a, model a takes the pair's H_ab (row k of H_ab for pair k), the
+// removed models are compacted from the highest index down and the labels renumbered to match (-1 stays).  Returns the new count.
+int ApplyMerges(const int* pairs, const double* H_ab /* npairs x 9 */, const std::vector<int>& accepted, int n, int* labels,
+                double* H /* nh x 9, compacted in place */, int nh);
+// Models taken out with their members becoming -1 (the collinearity filter's verdicts), compaction as above.  Returns the new count.
+int RemoveModels(const std::vector<char>& remove, int n, int* labels, double* H, int nh);
+// The pairs a step evaluates: all of them while nh <= all_up_to, else per label its `nearest` nearest labels by squared distance
+// in the 6-D feature space (HomographyFeatures), as (a < b), sorted and without duplicates.
+std::vector<int> MergePairList(const double* H, int nh, int all_up_to = 64, int nearest = 8);
+
 // HomographyCompatibilityCheck (M/MultiH.cpp:100-222): per cluster 501 trials of {3 random cluster
 // points -> GetHomography3PT without refinement -> median squared transfer error of the remaining
 // points}; a cluster whose median-of-medians exceeds thr^2*81/16, or that has fewer than
