@@ -855,6 +855,44 @@ MH_API int mh_merge_deltas(mh_engine* e, const int* labels /* n */, const int* p
                            long long* parts /* npairs x 4, nullable */, int* status /* npairs */);
 MH_API int mh_labeling_energy(mh_engine* e, const int* labels /* n */, long long* energy, long long* parts /* 2, nullable */);
 
+/* ---- every site's best alternative label, and what dropping a label would do to the energy (csrc/label_cost.hip) ----
+ * The notation above: lam, T, potts, cost(i, H) in the arithmetic of mh_data_cost, w_pq; cost(i, -1) = round(lam * T), the
+ * outlier cost.  The graph has no self arcs and both directions carry the same w.  All sums are int64.  labels in -1..Nh-1.
+ *
+ * Used labels: U = { k in 0..Nh-1 : some labels[i] == k }.
+ *
+ * mh_best_alternative: per site i, with C_i = ({-1} u U) \ {labels[i]}:
+ *     alt[i]      = the first minimum of cost(i, l) over l in C_i in the order -1, 0, 1, ... (the outlier first, then the lowest
+ *                   index)
+ *     alt_cost[i] = that minimum;   own_cost[i] = cost(i, labels[i])
+ * C_i empty (the site is an outlier and no label is used): alt[i] = -1, alt_cost[i] = round(lam * T).
+ * The N x Nh table is never written: alt and alt_cost are the arg-min over the rows of mh_data_cost's table, restricted to C_i.
+ *
+ * mh_drop_deltas: the arg-min once, then per candidate label k with members S_k = { i : labels[i] == k } and
+ * labels' = labels with alt[i] in place of k on S_k:
+ *     data_old   = sum_{S_k} cost(i, H[k])                  data_new   = sum_{S_k} alt_cost[i]
+ *     smooth_old = potts * sum w_pq [labels[p] != labels[q]]    smooth_new = potts * sum w_pq [labels'[p] != labels'[q]]
+ *                  both over the undirected pairs with at least one end in S_k, each pair once
+ *     delta      = data_new - data_old + smooth_new - smooth_old
+ *     parts (nullable) = { |S_k|, data_old, data_new, smooth_old, smooth_new } per candidate
+ * status: MH_DROP_OK or MH_DROP_EMPTY (no member); not OK: delta = LLONG_MAX, the candidate's parts row stays as the caller
+ * passed it.  alt_out (nullable): the n best alternatives the deltas were computed with.
+ * The contract: with the models as they stand, mh_labeling_energy(labels') - mh_labeling_energy(labels) == delta, exactly.
+ * With a cost beta >= 0 per used label, E_beta = mh_labeling_energy + beta |U|, a drop — like a join of mh_merge_deltas —
+ * removes one used label: it lowers E_beta iff delta - beta < 0.
+ * Both calls need correspondences and models (mh_drop_deltas: and the neighbour graph), no F and no affinities, and change
+ * nothing in the engine: models, data-cost freshness, labels, counts and mode words stay.
+ * MH_ERR_INVALID: null engine; null labels / alt; null cand / delta / status with ncand > 0; a label outside -1..Nh-1; a
+ * candidate outside [0, Nh); ncand outside [0, Nh].  MH_ERR_NOT_SET without correspondences, models or (mh_drop_deltas) a
+ * neighbour graph.  ncand == 0: MH_OK, nothing is launched. */
+#define MH_DROP_OK     0
+#define MH_DROP_EMPTY  1
+MH_API int mh_best_alternative(mh_engine* e, const int* labels /* n */, int* alt /* n */, int* alt_cost /* n, nullable */,
+                               int* own_cost /* n, nullable */);
+MH_API int mh_drop_deltas(mh_engine* e, const int* labels /* n */, const int* cand /* ncand labels */, int ncand,
+                          long long* delta /* ncand */, long long* parts /* ncand x 5, nullable */, int* status /* ncand */,
+                          int* alt_out /* n, nullable */);
+
 /* ---- device-side access (bench / multi-GPU plumbing) --------------------- */
 enum { MH_BUF_COUNTS = 0, MH_BUF_MODELS = 1, MH_BUF_RESIDUALS = 2, MH_BUF_LABELS = 3, MH_BUF_COST = 4, MH_BUF_GATHERED_SCORES = 5,
        MH_BUF_LABEL_COUNTS = 6 /* per label, its member count in the last re-estimation (mh_reestimate / mh_labeling_step) */,

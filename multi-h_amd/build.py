@@ -28,7 +28,7 @@ ARCH = "gfx950"
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
              "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 KERNEL_SOURCES = ["residual.hip", "dlt4.hip", "datacost.hip", "reestimate.hip", "reestimate3pt.hip", "reestimate_dlt.hip", "expand.hip", "expand_solve.hip",
-                  "knn.hip", "graph.hip", "haf_propose.hip", "propose3pt.hip", "fund.hip", "refit_h.hip", "polish_h.hip", "reweight_h.hip", "label_scale.hip", "meanshift.hip", "refine.hip", "select.hip", "score32.hip", "msac32.hip", "compat.hip", "merge_energy.hip",
+                  "knn.hip", "graph.hip", "haf_propose.hip", "propose3pt.hip", "fund.hip", "refit_h.hip", "polish_h.hip", "reweight_h.hip", "label_scale.hip", "meanshift.hip", "refine.hip", "select.hip", "score32.hip", "msac32.hip", "compat.hip", "merge_energy.hip", "label_cost.hip",
                   "capi.hip", "capi_front.hip", "capi_score.hip", "capi_propose.hip", "capi_select.hip", "capi_label.hip"]
 
 

@@ -24,6 +24,9 @@ RESIDUAL_SCOPES = {"score": 0, "route": 1}      # MH_RESIDUAL_SCOPE_SCORE, MH_RE
 DATA_TERMS = {"reference": 0, "rising": 1}      # MH_DATA_TERM_REFERENCE, MH_DATA_TERM_RISING
 MERGE_OK, MERGE_EMPTY, MERGE_NO_FIT = 0, 1, 2   # MH_MERGE_*
 MERGE_NO_DELTA = 2**63 - 1                      # LLONG_MAX: the delta of a pair that is not OK
+DROP_OK, DROP_EMPTY = 0, 1                      # MH_DROP_*
+DROP_NO_DELTA = 2**63 - 1                       # LLONG_MAX: the delta of a candidate that is not OK
+BEST_ALT_TILE = 64                              # models per LDS tile of k_best_alternative (csrc/mh_kernels.hpp)
 K_DLT4, K_RESIDUAL, K_SCORE, K_DATACOST, K_EXPAND, K_REESTIMATE, K_COSTMATRIX = 0, 1, 2, 3, 4, 5, 6
 
 # every symbol include/multih_hip.h declares (tests check the export table against this)
@@ -35,7 +38,7 @@ SYMBOLS = [
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
     "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_propose_haf", "mh_get_haf_support", "mh_propose_3pt", "mh_set_residual_mode", "mh_set_residual_scope", "mh_score", "mh_score_msac", "mh_select_best_msac",
     "mh_residual_matrix", "mh_cost_matrix", "mh_get_residual_rows", "mh_set_transport", "mh_select_greedy", "mh_select_greedy_msac", "mh_get_score_stats", "mh_prefetch_dlt4", "mh_adopt_prefetched", "mh_select_best", "mh_get_copy_stats", "mh_inliers_of_model", "mh_inliers_of_homography", "mh_refit_homography", "mh_polish_homographies", "mh_reweight_homographies", "mh_label_residual_quantile", "mh_reweight_homographies_auto", "mh_compat_trial_stats", "mh_compat_trial_stats_fit", "mh_compat_dlt_medians", "mh_inlier_moments", "mh_set_data_term", "mh_data_cost", "mh_expand",
-    "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_set_estimator_reweighting", "mh_set_estimator_reweighting_auto", "mh_reestimate", "mh_labeling_step", "mh_merge_deltas", "mh_labeling_energy", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
+    "mh_get_expand_stats", "mh_get_expand_batch_stats", "mh_get_expand_trace", "mh_get_core_components", "mh_set_estimator", "mh_set_estimator_reweighting", "mh_set_estimator_reweighting_auto", "mh_reestimate", "mh_labeling_step", "mh_merge_deltas", "mh_labeling_energy", "mh_best_alternative", "mh_drop_deltas", "mh_device_buffer", "mh_profile_enable", "mh_profile_reset",
     "mh_profile_get", "mh_set_tuning",
 ]
 
@@ -723,6 +726,32 @@ class Engine:
         energy, parts = C.c_longlong(0), (C.c_longlong * 2)()
         self._check(self.lib.mh_labeling_energy(self._h, _p(labels, C.c_int), C.byref(energy), parts))
         return int(energy.value), int(parts[0]), int(parts[1])
+
+    def best_alternative(self, labels):
+        """mh_best_alternative: per point the cheapest label other than its own among the outlier label and the used labels
+        (the outlier first, then the lowest index), that cost and the cost under its own label.  Returns (alt, alt_cost,
+        own_cost), int32 each."""
+        labels = _i32(labels)
+        alt, alt_cost, own_cost = (np.zeros(labels.size, dtype=np.int32) for _ in range(3))
+        self._check(self.lib.mh_best_alternative(self._h, _p(labels, C.c_int), _p(alt, C.c_int), _p(alt_cost, C.c_int),
+                                                 _p(own_cost, C.c_int)))
+        return alt, alt_cost, own_cost
+
+    def drop_deltas(self, labels, cand):
+        """mh_drop_deltas: per candidate label k the energy change `delta` of giving each of its members its best alternative,
+        parts = (|S_k|, data_old, data_new, smooth_old, smooth_new) and status (DROP_OK / DROP_EMPTY).  A candidate that is not
+        OK has delta = DROP_NO_DELTA and a zero row of parts.  Returns (delta int64, parts int64 [ncand, 5], status int32, alt
+        int32 [n])."""
+        labels = _i32(labels)
+        cand = _i32(cand).reshape(-1)
+        ncand = cand.size
+        delta = np.zeros(ncand, dtype=np.int64)
+        parts = np.zeros((ncand, 5), dtype=np.int64)
+        status = np.zeros(ncand, dtype=np.int32)
+        alt = np.zeros(labels.size, dtype=np.int32)
+        self._check(self.lib.mh_drop_deltas(self._h, _p(labels, C.c_int), _p(cand, C.c_int), ncand, _p(delta, C.c_longlong),
+                                            _p(parts, C.c_longlong), _p(status, C.c_int), _p(alt, C.c_int)))
+        return delta, parts, status, alt
 
     # -- device access / profiling -----------------------------------------
     def device_buffer(self, which: int):

@@ -224,6 +224,8 @@ struct mh_engine : ResidentBatch {                    // (e->m, e->origin, e->ha
     DevBuf<int> me_labels, me_pairs, me_status;   // mh_merge_deltas / mh_labeling_energy: the labels (n), the pairs (npairs x 2), their status,
     DevBuf<double> me_H;                      // the unions' fits (npairs x 9),
     DevBuf<long long> me_out;                 // per pair |S|, data_old, data_new, cut, delta; mh_labeling_energy: data, smooth
+    DevBuf<int> lc_used, lc_cand, lc_alt, lc_cost;    // mh_best_alternative / mh_drop_deltas (labels in me_labels, status in me_status, sums in
+                                              //   me_out): the used flags (m), the candidates, alt (n), alt_cost | own_cost (2 n)
     DevBuf<double> moments, min_eig;
     DevBuf<double> cp_pts, cp_H, cp_out;     // mh_compat_trial_stats staging
     DevBuf<int> cp_begin, cp_tri;

@@ -638,4 +638,81 @@ int mh_labeling_energy(mh_engine* e, const int* labels, long long* energy, long 
     });
 }
 
+static_assert(MH_DROP_OK == DROP_OK && MH_DROP_EMPTY == DROP_EMPTY, "status codes of label_cost.hip");
+
+// The labels checked against -1..Nh-1 and the used flags counted in the same walk; both uploaded (me_labels, lc_used), and the
+// arg-min launched into lc_alt / lc_cost (alt_cost, then own_cost).  Writes staging buffers and nothing else of the engine.
+static int best_alternative_on_device(mh_engine* e, const int* labels)
+{
+    std::vector<int> used(e->m, 0);
+    for (int i = 0; i < e->n; ++i) {
+        if (labels[i] < -1 || labels[i] >= e->m) return fail(MH_ERR_INVALID, "label out of range -1..Nh-1");
+        if (labels[i] >= 0) used[labels[i]] = 1;
+    }
+    const size_t n = (size_t)e->n;
+    HIPCHK(e->me_labels.reserve(n)); HIPCHK(e->lc_used.reserve(e->m)); HIPCHK(e->lc_alt.reserve(n)); HIPCHK(e->lc_cost.reserve(2 * n));
+    HIPCHK(hipMemcpyAsync(e->me_labels.p, labels, sizeof(int) * n, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->lc_used.p, used.data(), sizeof(int) * e->m, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(launch_best_alternative(e->pts(), e->me_labels.p, e->H.p, e->m, e->lc_used.p, e->lambda, e->thr_H * e->thr_H, e->lc_alt.p,
+                                   e->lc_cost.p, e->lc_cost.p + n, e->stream, e->data_term == MH_DATA_TERM_RISING, e->route_symmetric()));
+    HIPCHK(hipStreamSynchronize(e->stream));     // `used` is pageable host memory of this frame
+    return MH_OK;
+}
+
+int mh_best_alternative(mh_engine* e, const int* labels, int* alt, int* alt_cost, int* own_cost)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (!labels || !alt) return fail(MH_ERR_INVALID, "null argument");
+    int rc = require_models(e);
+    if (rc) return rc;
+    rc = best_alternative_on_device(e, labels);
+    if (rc) return rc;
+    const size_t n = (size_t)e->n;
+    HIPCHK(hipMemcpyAsync(alt, e->lc_alt.p, sizeof(int) * n, hipMemcpyDeviceToHost, e->stream));
+    if (alt_cost) HIPCHK(hipMemcpyAsync(alt_cost, e->lc_cost.p, sizeof(int) * n, hipMemcpyDeviceToHost, e->stream));
+    if (own_cost) HIPCHK(hipMemcpyAsync(own_cost, e->lc_cost.p + n, sizeof(int) * n, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MH_OK;
+    });
+}
+
+int mh_drop_deltas(mh_engine* e, const int* labels, const int* cand, int ncand, long long* delta, long long* parts, int* status,
+                   int* alt_out)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (ncand < 0) return fail(MH_ERR_INVALID, "ncand outside [0, Nh]");
+    if (ncand > 0 && (!labels || !cand || !delta || !status)) return fail(MH_ERR_INVALID, "null argument");
+    int rc = require_models(e);
+    if (rc) return rc;
+    if (!e->have_graph) return fail(MH_ERR_NOT_SET, "neighbour graph is not set");
+    if (ncand > e->m) return fail(MH_ERR_INVALID, "ncand outside [0, Nh]");
+    if (ncand == 0) return MH_OK;
+    for (int k = 0; k < ncand; ++k)
+        if (cand[k] < 0 || cand[k] >= e->m) return fail(MH_ERR_INVALID, "a candidate is outside [0, Nh)");
+    rc = best_alternative_on_device(e, labels);
+    if (rc) return rc;
+    const size_t nc = (size_t)ncand, n = (size_t)e->n;
+    HIPCHK(e->lc_cand.reserve(nc)); HIPCHK(e->me_status.reserve(nc)); HIPCHK(e->me_out.reserve(5 * nc));
+    HIPCHK(hipMemcpyAsync(e->lc_cand.p, cand, sizeof(int) * nc, hipMemcpyHostToDevice, e->stream));
+    const Graph g{ e->d_rowptr.p, e->d_col.p, e->d_w.p, e->d_rev.p, e->n, e->g_nnz, e->d_order.p, e->d_wsum.p };
+    HIPCHK(launch_drop_labels(e->pts(), e->me_labels.p, e->H.p, e->lc_cand.p, ncand, e->lc_alt.p, e->lc_cost.p, g, e->lambda,
+                              e->thr_H * e->thr_H, e->me_out.p, e->me_status.p, e->stream, e->data_term == MH_DATA_TERM_RISING,
+                              e->route_symmetric()));
+    std::vector<long long> h_out(5 * nc);
+    HIPCHK(hipMemcpyAsync(status, e->me_status.p, sizeof(int) * nc, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(h_out.data(), e->me_out.p, sizeof(long long) * 5 * nc, hipMemcpyDeviceToHost, e->stream));
+    if (alt_out) HIPCHK(hipMemcpyAsync(alt_out, e->lc_alt.p, sizeof(int) * n, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (size_t k = 0; k < nc; ++k) {            // a candidate that is not OK leaves its row of parts as it was
+        if (status[k] != MH_DROP_OK) { delta[k] = 0x7fffffffffffffffll; continue; }
+        const long long* o = &h_out[5 * k];
+        delta[k] = o[2] - o[1] + o[4] - o[3];
+        if (parts) std::memcpy(parts + 5 * k, o, sizeof(long long) * 5);
+    }
+    return MH_OK;
+    });
+}
+
 } // extern "C"

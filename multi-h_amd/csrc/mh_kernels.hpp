@@ -294,6 +294,19 @@ hipError_t launch_merge_pairs(const Points& p, const int* labels, const double* 
 hipError_t launch_labeling_energy(const Points& p, const int* labels, const double* H, const Graph& g, double lambda, double thr2,
                                   unsigned long long* out, hipStream_t s, int rising, int symmetric);
 
+// --- label_cost.hip: every site's best alternative label, the energy change of dropping a label (mh_best_alternative, mh_drop_deltas) ---
+constexpr int DROP_OK = 0, DROP_EMPTY = 1;       // MH_DROP_*
+constexpr int BEST_ALT_TILE = 64;                // models per LDS tile of k_best_alternative
+// per site: alt, alt_cost (nullable), own_cost (nullable).  labels: n ints in -1..Nh-1, used: Nh flags, used[labels[i]] != 0
+// (the caller's check and count)
+hipError_t launch_best_alternative(const Points& p, const int* labels, const double* H, int Nh, const int* used, double lambda,
+                                   double thr2, int* alt, int* alt_cost, int* own_cost, hipStream_t s, int rising, int symmetric);
+// per candidate: status; for an OK one out = { |S_k|, data_old, data_new, smooth_old, smooth_new }.  cand: labels in [0, Nh) (the
+// caller's check: they index H); alt, alt_cost: launch_best_alternative's on the same labels
+hipError_t launch_drop_labels(const Points& p, const int* labels, const double* H, const int* cand, int ncand, const int* alt,
+                              const int* alt_cost, const Graph& g, double lambda, double thr2, long long* out /* ncand x 5 */,
+                              int* status, hipStream_t s, int rising, int symmetric);
+
 constexpr int EXPAND_MAX_CTX = 16;
 constexpr int EXPAND_FLAG_WORDS = 896;     // device control block (expand_ctl.hpp)
 constexpr int EXPAND_HOST_WORDS = 32;      // its head, mirrored to the host

@@ -58,6 +58,8 @@
 // ... and for the energy-tested merge (SetMergeMode(MERGE_ENERGY)): the same.
 #pragma weak mh_merge_deltas
 #pragma weak mh_labeling_energy
+// ... and for the label cost (SetLabelCost): the same.
+#pragma weak mh_drop_deltas
 
 namespace {
 
@@ -391,6 +393,28 @@ bool MultiH::Run(bool points_only)
     if (merge_mode == MERGE_ENERGY && (!mh_merge_deltas || !mh_labeling_energy)) {
         std::cerr << "Error: the engine library has no energy-tested merge (mh_merge_deltas, mh_labeling_energy)\n";
         return false;
+    }
+    if (!(label_cost_points >= 0.0) || !std::isfinite(label_cost_points)) {
+        std::cerr << "Error: the label cost must be finite and not negative (SetLabelCost)\n";
+        return false;
+    }
+    if (label_cost_points > 0.0 && merge_mode != MERGE_ENERGY) {
+        std::cerr << "Error: a label cost needs the energy-tested merge (SetLabelCost with SetMergeMode(MERGE_ENERGY))\n";
+        return false;
+    }
+    if (label_cost_points > 0.0 && !mh_drop_deltas) {
+        std::cerr << "Error: the engine library has no label-drop evaluation (mh_drop_deltas)\n";
+        return false;
+    }
+    {
+        // beta in energy units: `points` outliers' worth, round(lam * T) each (mh_data_cost's outlier cost)
+        const double outlier = std::round((100.0 / energy_lambda) * (threshold_homography * threshold_homography * 81.0 / 16.0));
+        const double beta = label_cost_points * outlier;
+        if (!(beta < 9.0e18)) {
+            std::cerr << "Error: the label cost is too large (SetLabelCost)\n";
+            return false;
+        }
+        label_cost_beta = std::llround(beta);
     }
     // the data term of the labeling (sticky on the engine, and engines are reused)
     if (!mh_set_data_term) {
@@ -1108,6 +1132,7 @@ void MultiH::ClusterMergingAndLabeling()
     labeling_is_current = false;
     merge_log_open = false;
     merge_log.clear();
+    drop_log.clear();
 
     const bool timing = std::getenv("MULTIH_TIMING") != nullptr;                        // diagnostic: where the loop's time goes
     double merge_s = 0.0, label_s = 0.0;
@@ -1288,15 +1313,61 @@ bool MultiH::MergingStepEnergy(bool& changed)
         if (!Check(mh_merge_deltas(engine, labeling.data(), pairs.data(), npairs, H_ab.data(), delta.data(), nullptr, status.data()),
                    "MergingStep (mh_merge_deltas)"))
             return false;
-        const std::vector<int> accepted = multih::SelectMerges(pairs.data(), delta.data(), status.data(), npairs, nh);
+        const std::vector<int> accepted = multih::SelectMergesWithLabelCost(pairs.data(), delta.data(), status.data(), npairs, nh, label_cost_beta);
         for (int k : accepted) rec.sum_delta += delta[k];
         rec.merges_accepted = static_cast<long long>(accepted.size());
         count = multih::ApplyMerges(pairs.data(), H_ab.data(), accepted, N, labeling.data(), H.data(), nh);
         if (count != nh && !Check(mh_set_models(engine, H.data(), count), "MergingStep (mh_set_models)")) return false;
+        // the drop move, on the labeling and models the joins left: at most one label per step
+        if (label_cost_beta > 0 && count > 0) {
+            DropLogRecord drop;
+            drop.iteration = loop_iteration;
+            drop.beta = label_cost_beta;
+            std::vector<char> in_use(count, 0);
+            for (int j = 0; j < N; ++j)
+                if (labeling[j] >= 0 && labeling[j] < count) in_use[labeling[j]] = 1;
+            std::vector<int> cand;
+            for (int l = 0; l < count; ++l)
+                if (in_use[l]) cand.push_back(l);
+            const int ncand = static_cast<int>(cand.size());
+            drop.candidates = ncand;
+            drop.E_before = rec.E_before + rec.sum_delta;
+            if (!accepted.empty() &&
+                !Check(mh_labeling_energy(engine, labeling.data(), &drop.E_before, nullptr), "MergingStep (mh_labeling_energy)"))
+                return false;
+            drop.E_after = drop.E_before;
+            if (ncand > 0) {
+                std::vector<long long> d_delta(ncand), d_parts(5 * (size_t)ncand);
+                std::vector<int> d_status(ncand), alt(N);
+                if (!Check(mh_drop_deltas(engine, labeling.data(), cand.data(), ncand, d_delta.data(), d_parts.data(), d_status.data(),
+                                          alt.data()),
+                           "MergingStep (mh_drop_deltas)"))
+                    return false;
+                const int pick = multih::SelectDrop(cand.data(), d_delta.data(), d_status.data(), ncand, label_cost_beta);
+                if (pick >= 0) {
+                    int to_outlier = 0;
+                    drop.dropped = cand[pick];
+                    drop.members = d_parts[5 * (size_t)pick];
+                    drop.delta = d_delta[pick];
+                    count = multih::ApplyDrop(cand[pick], alt.data(), N, labeling.data(), H.data(), count, &to_outlier);
+                    drop.to_outlier = to_outlier;
+                    if (count > 0) {
+                        if (!Check(mh_set_models(engine, H.data(), count), "MergingStep (mh_set_models)")) return false;
+                        if (!Check(mh_labeling_energy(engine, labeling.data(), &drop.E_after, nullptr), "MergingStep (mh_labeling_energy)"))
+                            return false;
+                    } else {
+                        drop.E_after = drop.E_before + drop.delta;       // no model is left to ask: every site is an outlier
+                    }
+                    rec.sum_delta += drop.delta;
+                }
+            }
+            drop_log.push_back(drop);
+        }
     }
     // the collinearity filter (M/MultiH.cpp:446-463) on the models as they stand
     std::vector<double> mom(6 * (size_t)count), mineig(count);
-    if (!Check(mh_inlier_moments(engine, threshold_homography * threshold_homography, mom.data(), mineig.data()), "MergingStep (mh_inlier_moments)"))
+    if (count > 0 &&                                 // (0: the drop took the last label, the engine's models are stale)
+        !Check(mh_inlier_moments(engine, threshold_homography * threshold_homography, mom.data(), mineig.data()), "MergingStep (mh_inlier_moments)"))
         return false;
     std::vector<char> remove(count, 0);
     int filtered = 0;
@@ -1513,6 +1584,22 @@ int mhh_get_merge_log(long long* records_out, int capacity)
         std::memcpy(records_out + 9 * (size_t)i, &g_merge_log[i], sizeof(MultiH::MergeLogRecord));
     return (int)g_merge_log.size();
 }
+// MultiH::SetLabelCost for the next mhh_run_process calls (the class default is 0; any value is handed on, so that a bad one
+// fails in Process()), and the drop log of the last one
+static double g_label_cost = 0.0;
+static std::vector<MultiH::DropLogRecord> g_drop_log;
+extern "C" __attribute__((visibility("default")))
+void mhh_set_label_cost(double points) { g_label_cost = points; }
+// records_out: capacity x 9 long long (iteration, candidates, dropped label or -1, members, members to the outlier label, delta,
+// beta, E_before, E_after), nullable; returns the number of records of the last mhh_run_process
+extern "C" __attribute__((visibility("default")))
+int mhh_get_drop_log(long long* records_out, int capacity)
+{
+    static_assert(sizeof(MultiH::DropLogRecord) == 9 * sizeof(long long), "a record travels as 9 long long");
+    for (int i = 0; records_out && i < capacity && i < (int)g_drop_log.size(); ++i)
+        std::memcpy(records_out + 9 * (size_t)i, &g_drop_log[i], sizeof(MultiH::DropLogRecord));
+    return (int)g_drop_log.size();
+}
 // MultiH::SetDataTerm for the next mhh_run_process calls (< 0: the class default)
 static int g_data_term = -1;
 extern "C" __attribute__((visibility("default")))
@@ -1658,6 +1745,8 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     if (g_data_term >= 0) mh.SetDataTerm(g_data_term);
     if (g_merge_mode >= 0) mh.SetMergeMode(g_merge_mode);
     g_merge_log.clear();
+    if (g_label_cost != 0.0) mh.SetLabelCost(g_label_cost);
+    g_drop_log.clear();
     if (g_residual >= 0) mh.SetResidual(g_residual);
     if (g_tail_score >= 0) mh.SetTailScore(g_tail_score);
     if (g_tail_refit >= 0) mh.SetTailRefit(g_tail_refit);
@@ -1702,5 +1791,6 @@ int mhh_run_process(const double* src_xy, const double* dst_xy, const double* af
     if (loop_seconds) *loop_seconds = mh.GetLastLoopSeconds();
     g_labeling_steps = mh.GetLabelingStepsRun();
     g_merge_log = mh.GetMergeLog();
+    g_drop_log = mh.GetDropLog();
     return k;
 }

@@ -314,18 +314,36 @@ public:
     // members become outliers) and sets `changed` iff the model count changed.  The LabelingStep that follows starts warm from
     // that labeling.  Needs no F: it runs on the route with F and under SetEpipolarFree alike, replicated on every rank of a
     // sharded run.  Limits: the union's model is the N-point DLT whatever SetEstimator says (the next LabelingStep re-estimates
-    // with the route's estimator); no label cost; no joins of three labels at once.  Any other value makes Process() fail.
+    // with the route's estimator); no joins of three labels at once; a cost per label only through SetLabelCost (default 0).  Any other value makes Process() fail.
     enum { MERGE_MEAN_SHIFT = 0, MERGE_ENERGY = 1 };
     void SetMergeMode(int m) { merge_mode = m; }
     // One record per MergingStep that evaluated merges in the last Process() (empty under MERGE_MEAN_SHIFT): E_before =
     // mh_labeling_energy in front of the merges, sum_delta the accepted deltas' sum, E_start = mh_labeling_energy of what the
     // LabelingStep starts from (= E_before + sum_delta when nothing was filtered), E_expansion the energy that step returned
-    // (-1 when none followed).
+    // (-1 when none followed).  Under SetLabelCost an accepted drop's delta is part of sum_delta (its details: GetDropLog).
     struct MergeLogRecord {
         long long iteration = 0, models_before = 0, pairs = 0, merges_accepted = 0, models_filtered = 0;
         long long E_before = 0, sum_delta = 0, E_start = 0, E_expansion = -1;
     };
     const std::vector<MergeLogRecord>& GetMergeLog() const { return merge_log; }
+    // The cost of a label in use, for the moves of MergingStep under MERGE_ENERGY (PEARL's third term, beside data and
+    // smoothness): beta = llround(points * round(lam * T)) energy units, i.e. stated in outliers' worth — a label must explain
+    // about `points` correspondences better than the outlier label does to pay for itself.  Default 0: nothing changes.  With
+    // beta > 0 a join is taken iff delta - beta < 0 (multih::SelectMergesWithLabelCost), and behind the joins, on the labeling and
+    // models that result, mh_drop_deltas evaluates for every used label the move "give each member its best alternative among
+    // the other used labels and the outlier label"; at most one drop per step, the one with the smallest (delta, label), iff
+    // delta - beta < 0 (multih::SelectDrop / ApplyDrop).  The alpha-expansion itself stays without label costs.  A negative or
+    // non-finite value, or a positive one without MERGE_ENERGY, makes Process() fail with a message.
+    void SetLabelCost(double points) { label_cost_points = points; }
+    // One record per MergingStep that evaluated drops in the last Process() (empty while the label cost is 0): the dropped
+    // label in the numbering behind the joins (-1: none), its members and how many of them became outliers, delta and beta,
+    // E_before = mh_labeling_energy in front of the drop, E_after a second mh_labeling_energy call behind it (= E_before + delta;
+    // E_before when nothing was dropped).
+    struct DropLogRecord {
+        long long iteration = 0, candidates = 0, dropped = -1, members = 0, to_outlier = 0;
+        long long delta = 0, beta = 0, E_before = 0, E_after = 0;
+    };
+    const std::vector<DropLogRecord>& GetDropLog() const { return drop_log; }
     void SetDevice(int d) { device = d; }
     // schedule knob of the engine (mh_set_tuning; results never depend on it), applied when the engine is created
     void SetEngineTuning(int key, int value) { engine_tuning.emplace_back(key, value); }
@@ -424,6 +442,9 @@ protected:
     bool MergingStepEnergy(bool& changed);             // SetMergeMode(MERGE_ENERGY)
     int merge_mode = MERGE_MEAN_SHIFT;
     std::vector<MergeLogRecord> merge_log;
+    double label_cost_points = 0.0;       // SetLabelCost
+    long long label_cost_beta = 0;        // ... in energy units, set by Run()
+    std::vector<DropLogRecord> drop_log;
     bool labeling_is_current = false;     // a LabelingStep has run in this Process() and `labeling` is valid for cluster_homographies
     bool merge_log_open = false;          // the last record waits for its LabelingStep's energy
     int loop_iteration = 0;

@@ -36,6 +36,10 @@
 //                                reference's rule; energy joins two labels only where the union with its own N-point refit lowers
 //                                the labeling's energy (mh_merge_deltas), and the LabelingStep behind it starts warm; "Energy merges:"
 //                                reports the steps' totals
+//                  [--label-cost P]   the cost of a label in use, in outliers' worth (MultiH::SetLabelCost; needs --merge energy):
+//                                joins are taken iff delta - beta < 0, and behind them at most one label per step is dropped
+//                                (mh_drop_deltas) where that lowers the energy with the cost; default 0; "Label cost:" reports
+//                                the drops
 //                  [--residual forward|symmetric]   the error of the whole route (MultiH::SetResidual): forward, the default, is the
 //                                reference's one-way transfer error; symmetric adds the backward term through adj(H) — proposals
 //                                are scored and selected, clusters merged, points labelled and the tail finished by it at thrH,
@@ -148,7 +152,7 @@ int main(int argc, char** argv)
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
                      "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] [--f-estimator ls8|minimal] "
-                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--compat-fit dlt[:trials[:limit_scale]]] [--data-term reference|rising] [--merge meanshift|energy] [--residual forward|symmetric] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--reweight n[:scale]] [--estimator-reweight n[:scale]] [--reweight-auto n[:kappa]] [--estimator-reweight-auto n[:kappa]] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
+                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--compat-fit dlt[:trials[:limit_scale]]] [--data-term reference|rising] [--merge meanshift|energy] [--label-cost P] [--residual forward|symmetric] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--reweight n[:scale]] [--estimator-reweight n[:scale]] [--reweight-auto n[:kappa]] [--estimator-reweight-auto n[:kappa]] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
         return 2;
     }
     double thrF = 2.6, thrH = 2.2, locality = 0.005, lambda = 0.5;     // M/main.cpp:55-59
@@ -164,6 +168,7 @@ int main(int argc, char** argv)
     int data_term = MultiH::DATA_TERM_REFERENCE;
     int residual = MultiH::RESIDUAL_FORWARD;
     int merge_mode = MultiH::MERGE_MEAN_SHIFT;
+    double label_cost = 0.0;
     int tail_score = MultiH::TAIL_SCORE_COUNT;
     int tail_refit = 0, tail_polish = 0, model_polish = 0;
     int compat_fit = MultiH::COMPAT_FIT_3PT, compat_trials = 501;
@@ -198,6 +203,7 @@ int main(int argc, char** argv)
             else if (std::string(v) == "energy") merge_mode = MultiH::MERGE_ENERGY;
             else { std::cerr << "--merge: meanshift or energy\n"; return 2; }
         }
+        else if (k == "--label-cost") label_cost = std::atof(v);
         else if (k == "--residual") {
             if (std::string(v) == "forward") residual = MultiH::RESIDUAL_FORWARD;
             else if (std::string(v) == "symmetric") residual = MultiH::RESIDUAL_SYMMETRIC;
@@ -493,6 +499,7 @@ int main(int argc, char** argv)
     multiH->SetCompatibilityFit(compat_fit, compat_trials, compat_limit_scale);
     multiH->SetDataTerm(data_term);
     multiH->SetMergeMode(merge_mode);
+    multiH->SetLabelCost(label_cost);
     multiH->SetResidual(residual);
     multiH->SetTailScore(tail_score);
     multiH->SetTailRefit(tail_refit);
@@ -545,6 +552,15 @@ int main(int argc, char** argv)
         }
         printf("[Multi-H] Energy merges: %d steps, %lld pairs evaluated, %lld joined, %lld models filtered, sum of deltas %lld\n",
                (int)multiH->GetMergeLog().size(), pairs, accepted, filtered, sum_delta);
+    }
+    if (label_cost > 0.0) {
+        long long candidates = 0, dropped = 0, members = 0, to_outlier = 0, beta = 0;
+        for (const MultiH::DropLogRecord& r : multiH->GetDropLog()) {
+            candidates += r.candidates; beta = r.beta;
+            if (r.dropped >= 0) { ++dropped; members += r.members; to_outlier += r.to_outlier; }
+        }
+        printf("[Multi-H] Label cost: beta %lld, %d steps, %lld candidates evaluated, %lld labels dropped (%lld members, %lld to the outlier label)\n",
+               beta, (int)multiH->GetDropLog().size(), candidates, dropped, members, to_outlier);
     }
 
     std::vector<cv::Point2d> src_points, dst_points;

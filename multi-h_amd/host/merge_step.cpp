@@ -881,9 +881,14 @@ int MergeCandidatesMedoid(const double* H, int nh, double thr_h, uint64_t seed, 
 
 std::vector<int> SelectMerges(const int* pairs, const long long* delta, const int* status, int npairs, int nh)
 {
+    return SelectMergesWithLabelCost(pairs, delta, status, npairs, nh, 0);
+}
+
+std::vector<int> SelectMergesWithLabelCost(const int* pairs, const long long* delta, const int* status, int npairs, int nh, long long beta)
+{
     std::vector<int> order;
     for (int k = 0; k < npairs; ++k)
-        if (status[k] == 0 && delta[k] < 0) order.push_back(k);
+        if (status[k] == 0 && delta[k] < beta) order.push_back(k);                       // delta - beta < 0, without the subtraction
     std::sort(order.begin(), order.end(), [&](int x, int y) {
         if (delta[x] != delta[y]) return delta[x] < delta[y];
         if (pairs[2 * x] != pairs[2 * y]) return pairs[2 * x] < pairs[2 * y];
@@ -919,6 +924,31 @@ int ApplyMerges(const int* pairs, const double* H_ab, const std::vector<int>& ac
 
 int RemoveModels(const std::vector<char>& remove, int n, int* labels, double* H, int nh) { return RemoveClusters(remove, n, labels, H, nh); }
 
+int SelectDrop(const int* cand, const long long* delta, const int* status, int ncand, long long beta)
+{
+    int best = -1;
+    for (int c = 0; c < ncand; ++c) {
+        if (status[c] != 0) continue;
+        if (best < 0 || delta[c] < delta[best] || (delta[c] == delta[best] && cand[c] < cand[best])) best = c;
+    }
+    return best >= 0 && delta[best] < beta ? best : -1;
+}
+
+int ApplyDrop(int k, const int* alt, int n, int* labels, double* H, int nh, int* to_outlier)
+{
+    int gone = 0;
+    if (k < 0 || k >= nh) { if (to_outlier) *to_outlier = 0; return nh; }
+    for (int j = 0; j < n; ++j)
+        if (labels[j] == k) {
+            labels[j] = alt[j] >= 0 && alt[j] < nh && alt[j] != k ? alt[j] : -1;
+            gone += labels[j] < 0 ? 1 : 0;
+        }
+    if (to_outlier) *to_outlier = gone;
+    std::vector<char> remove(nh, 0);
+    remove[k] = 1;
+    return RemoveClusters(remove, n, labels, H, nh);
+}
+
 std::vector<int> MergePairList(const double* H, int nh, int all_up_to, int nearest)
 {
     std::vector<int> pairs;
@@ -952,6 +982,30 @@ std::vector<int> MergePairList(const double* H, int nh, int all_up_to, int neare
 
 // ---- C hooks for the CPU-side tests (no GPU needed) ----------------------------
 extern "C" {
+
+// SelectMergesWithLabelCost for tests: mhh_select_merges with the cost per label
+__attribute__((visibility("default")))
+int mhh_select_merges_label_cost(const int* pairs, const long long* delta, const int* status, int npairs, int nh, long long beta,
+                                 int* accepted_out)
+{
+    const std::vector<int> acc = multih::SelectMergesWithLabelCost(pairs, delta, status, npairs, nh, beta);
+    std::copy(acc.begin(), acc.end(), accepted_out);
+    return (int)acc.size();
+}
+
+// SelectDrop for tests: the chosen candidate's position, or -1
+__attribute__((visibility("default")))
+int mhh_select_drop(const int* cand, const long long* delta, const int* status, int ncand, long long beta)
+{
+    return multih::SelectDrop(cand, delta, status, ncand, beta);
+}
+
+// ApplyDrop for tests: labels (n) and H (nh x 9) in place; returns the new model count, *to_outlier the members that became -1
+__attribute__((visibility("default")))
+int mhh_apply_drop(int k, const int* alt, int n, int* labels, double* H, int nh, int* to_outlier)
+{
+    return multih::ApplyDrop(k, alt, n, labels, H, nh, to_outlier);
+}
 
 // SelectMerges for tests: accepted_out (capacity npairs) receives the accepted pairs' positions in acceptance order; returns their number
 __attribute__((visibility("default")))

@@ -73,6 +73,17 @@ int ApplyMerges(const int* pairs, const double* H_ab /* npairs x 9 */, const std
                 double* H /* nh x 9, compacted in place */, int nh);
 // Models taken out with their members becoming -1 (the collinearity filter's verdicts), compaction as above.  Returns the new count.
 int RemoveModels(const std::vector<char>& remove, int n, int* labels, double* H, int nh);
+// ---- the label cost (MultiH::SetLabelCost; the deltas: mh_merge_deltas, mh_drop_deltas) ----
+// With a cost beta >= 0 per used label a join or a drop removes one used label: a move is taken iff delta - beta < 0.
+// SelectMerges' rule — the same order, no label twice — with that threshold; beta = 0 is SelectMerges.
+std::vector<int> SelectMergesWithLabelCost(const int* pairs, const long long* delta, const int* status, int npairs, int nh, long long beta);
+// Which label is dropped in one step: among the candidates with status 0 (MH_DROP_OK) the one with the smallest (delta, label),
+// taken iff delta - beta < 0.  Returns its position in `cand`, or -1.
+int SelectDrop(const int* cand, const long long* delta, const int* status, int ncand, long long beta);
+// The drop applied: the members of k take their alt (mh_drop_deltas' alt_out, in the old numbering), model k goes and the labels
+// are compacted as ApplyMerges compacts them.  Returns the new count; *to_outlier (nullable): the members that became -1.
+int ApplyDrop(int k, const int* alt /* n */, int n, int* labels, double* H /* nh x 9, compacted in place */, int nh,
+              int* to_outlier = nullptr);
 // The pairs a step evaluates: all of them while nh <= all_up_to, else per label its `nearest` nearest labels by squared distance
 // in the 6-D feature space (HomographyFeatures), as (a < b), sorted and without duplicates.
 std::vector<int> MergePairList(const double* H, int nh, int all_up_to = 64, int nearest = 8);
