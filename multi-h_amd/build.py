@@ -30,6 +30,8 @@ HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contr
 KERNEL_SOURCES = ["residual.hip", "dlt4.hip", "datacost.hip", "reestimate.hip", "reestimate3pt.hip", "reestimate_dlt.hip", "expand.hip", "expand_solve.hip",
                   "knn.hip", "graph.hip", "haf_propose.hip", "propose3pt.hip", "fund.hip", "refit_h.hip", "polish_h.hip", "reweight_h.hip", "label_scale.hip", "meanshift.hip", "refine.hip", "select.hip", "score32.hip", "msac32.hip", "compat.hip", "merge_energy.hip", "label_cost.hip",
                   "capi.hip", "capi_front.hip", "capi_score.hip", "capi_propose.hip", "capi_select.hip", "capi_label.hip"]
+# the sources of libmultih_host.so (the CPU tests that compile the host layer themselves take the list from here)
+HOST_SOURCES = [os.path.join(HOST, f) for f in ("MultiH.cpp", "hooks.cpp", "merge_step.cpp", "approx_neighbours.cpp")]
 
 
 def _newer(target: str, deps: list[str]) -> bool:
@@ -70,7 +72,7 @@ def build_engine(force: bool = False, verbose: bool = False) -> str:
 
 def build_host(force: bool = False, verbose: bool = False) -> str:
     """C++ host mirror of the reference class (no HIP in these files; g++)."""
-    srcs = [os.path.join(HOST, f) for f in ("MultiH.cpp", "merge_step.cpp", "approx_neighbours.cpp")]
+    srcs = HOST_SOURCES
     hdrs = [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith(".h")]
     hdrs.append(os.path.join(ROOT, "include", "multih_hip.h"))
     hdrs.append(os.path.join(ROOT, "include", "multih_rccl.h"))
@@ -125,7 +127,7 @@ def build_tuning(force: bool = False, verbose: bool = False) -> str:
 
 def build_all(force: bool = False, verbose: bool = False) -> None:
     build_engine(force, verbose)
-    if os.path.exists(os.path.join(HOST, "MultiH.cpp")):
+    if all(os.path.exists(s) for s in HOST_SOURCES):
         build_host(force, verbose)
 
 

@@ -14,52 +14,16 @@
 #include <cstring>
 #include <iostream>
 #include <mutex>
+#include <sstream>
 
 #include "merge_step.h"
-#include "multih_hip.h"
+#include "multih_internal.h"
 
-// The entry points of the point-only route are referenced weakly because the class is also linked against the suite's
-// stand-in engine (tests/fake_engine.cpp, the host-boundary test under AddressSanitizer), which defines the ABI up to
-// mh_set_tuning and not these two.  Against libmultih_hip.so they always resolve; where they do not, the HAF route runs
-// unchanged and the point-only route fails with a message instead of a link error.  The same holds for the minimal-sample
-// F estimator (SetFundamentalEstimator): without its entry point that mode fails with a message, the default runs unchanged.
-#pragma weak mh_set_estimator
-#pragma weak mh_refine_points
-#pragma weak mh_estimate_fundamental_minimal
-// ... and for the proposal sampler (SetProposalSampler): without its entry points the local sampler fails with a message.
-#pragma weak mh_set_sampler
-#pragma weak mh_build_sample_neighbours
-// ... and for the data term (SetDataTerm): without its entry point the rising term fails with a message.
-#pragma weak mh_set_data_term
-// ... and for the error of the route (SetResidual): without its entry points the symmetric error fails with a message.
-#pragma weak mh_set_residual_mode
-#pragma weak mh_set_residual_scope
-// ... and for the MSAC tail (SetTailScore): without its entry points that tail fails with a message.
-#pragma weak mh_score_msac
-#pragma weak mh_select_best_msac
-#pragma weak mh_get_model
-// ... and for the refit of the tail's winner (SetTailRefit): without its entry point that mode fails with a message.
-#pragma weak mh_refit_homography
-// ... and for the LM polish of the results (SetTailPolish, SetModelPolish): without its entry point those modes fail with a message.
-#pragma weak mh_polish_homographies
-// ... and for the reweighted refits (SetModelReweight, SetEstimatorReweight): the same.
-#pragma weak mh_reweight_homographies
-#pragma weak mh_set_estimator_reweighting
-#pragma weak mh_reweight_homographies_auto
-#pragma weak mh_set_estimator_reweighting_auto
-// ... and for the selection ranked by weight (SetSelectionScore): without its entry point that mode fails with a message.
-#pragma weak mh_select_greedy_msac
-// ... and for the HAF proposals (SetProposalSource): without its entry point that source fails with a message.
-#pragma weak mh_propose_haf
-// ... and for the 3-point proposals (PROPOSAL_SOURCE_3PT): the same.
-#pragma weak mh_propose_3pt
-// ... and for the compatibility check without F (SetCompatibilityFit(COMPAT_FIT_DLT)): without its entry point that mode fails with a message.
-#pragma weak mh_compat_dlt_medians
-// ... and for the energy-tested merge (SetMergeMode(MERGE_ENERGY)): the same.
-#pragma weak mh_merge_deltas
-#pragma weak mh_labeling_energy
-// ... and for the label cost (SetLabelCost): the same.
-#pragma weak mh_drop_deltas
+using multih::detail::BorrowEngine;
+using multih::detail::Check;
+using multih::detail::MatFrom9;
+using multih::detail::MergingStepOnEngine;
+using multih::detail::ReturnEngine;
 
 namespace {
 
@@ -73,16 +37,64 @@ cv::Mat OwnedMat(int rows, int cols, const double* v)
     return m;
 }
 
-cv::Mat MatFrom9(const double* h) { return OwnedMat(3, 3, h); }
+// Points — and, given `aff`, their 2 x 2 affinities row by row — as the flat arrays the engine takes.
+struct PackedPoints {
+    std::vector<double> s, d, a;
+    const double* affinities() const { return a.empty() ? nullptr : a.data(); }
+};
+PackedPoints PackPoints(const std::vector<cv::Point2d>& src, const std::vector<cv::Point2d>& dst, const std::vector<cv::Mat>* aff = nullptr)
+{
+    const size_t n = src.size();
+    PackedPoints p;
+    p.s.resize(2 * n); p.d.resize(2 * n);
+    if (aff) p.a.resize(4 * n);
+    for (size_t i = 0; i < n; ++i) {
+        p.s[2 * i] = src[i].x; p.s[2 * i + 1] = src[i].y;
+        p.d[2 * i] = dst[i].x; p.d[2 * i + 1] = dst[i].y;
+        if (!aff) continue;
+        const cv::Mat& A = (*aff)[i];
+        p.a[4 * i] = A.at<double>(0, 0); p.a[4 * i + 1] = A.at<double>(0, 1);
+        p.a[4 * i + 2] = A.at<double>(1, 0); p.a[4 * i + 3] = A.at<double>(1, 1);
+    }
+    return p;
+}
 
-bool Check(int rc, const char* what)
+} // namespace
+
+cv::Mat multih::detail::MatFrom9(const double* h) { return OwnedMat(3, 3, h); }
+
+bool multih::detail::Check(int rc, const char* what)
 {
     if (rc == MH_OK) return true;
     std::cerr << "[Multi-H] engine error in " << what << ": " << mh_last_error() << "\n";
     return false;
 }
 
-} // namespace
+MultiH::EngineCaps multih::detail::LinkedEngineCaps()
+{
+    MultiH::EngineCaps c;
+    c.point_only = mh_set_estimator && mh_refine_points;
+    c.fundamental_minimal = mh_estimate_fundamental_minimal;
+    c.set_sampler = mh_set_sampler;
+    c.sample_neighbours = mh_build_sample_neighbours;
+    c.data_term = mh_set_data_term;
+    c.residual_route = mh_set_residual_mode && mh_set_residual_scope;
+    c.msac_scores = mh_score_msac && mh_select_best_msac;
+    c.get_model = mh_get_model;
+    c.refit = mh_refit_homography;
+    c.polish = mh_polish_homographies;
+    c.reweight = mh_reweight_homographies;
+    c.estimator_reweighting = mh_set_estimator_reweighting;
+    c.reweight_auto = mh_reweight_homographies_auto;
+    c.estimator_reweighting_auto = mh_set_estimator_reweighting_auto;
+    c.select_greedy_msac = mh_select_greedy_msac;
+    c.propose_haf = mh_propose_haf;
+    c.propose_3pt = mh_propose_3pt;
+    c.compat_dlt = mh_compat_dlt_medians;
+    c.energy_merge = mh_merge_deltas && mh_labeling_energy;
+    c.drop_deltas = mh_drop_deltas;
+    return c;
+}
 
 MultiH::MultiH(double _thr_fund_mat, double _thr_hom, double _locality, double _lambda,
                int _minimum_inlier_number)
@@ -219,9 +231,7 @@ bool MultiH::EnsureEngine()
                  "mh_set_params");
 }
 
-namespace {
-// an engine for a helper outside any MultiH object: from the pool when one is idle on `device`
-mh_engine* BorrowEngine(int device)
+mh_engine* multih::detail::BorrowEngine(int device)
 {
     if (engine_pool_enabled()) {
         EnginePool& p = engine_pool();
@@ -232,7 +242,7 @@ mh_engine* BorrowEngine(int device)
     mh_engine* e = nullptr;
     return Check(mh_create(&e, device), "mh_create") ? e : nullptr;
 }
-void ReturnEngine(int device, mh_engine* e)
+void multih::detail::ReturnEngine(int device, mh_engine* e)
 {
     if (!e) return;
     if (engine_pool_enabled() && mh_synchronize(e) == MH_OK) {
@@ -242,7 +252,6 @@ void ReturnEngine(int device, mh_engine* e)
     }
     mh_destroy(e);
 }
-} // namespace
 
 bool multih::FilterCorrespondencesByEpipolarGeometry(std::vector<cv::Point2d>& srcPoints, std::vector<cv::Point2d>& dstPoints,
                                                      std::vector<cv::Mat>& affines, double threshold, uint64_t seed,
@@ -257,22 +266,18 @@ bool multih::FilterCorrespondencesByEpipolarGeometry(std::vector<cv::Point2d>& s
         return false;
     }
     const bool minimal = estimator.mode == MultiH::FUND_ESTIMATOR_MINIMAL7;
-    if (minimal && !mh_estimate_fundamental_minimal) {
+    if (minimal && !multih::detail::LinkedEngineCaps().fundamental_minimal) {
         std::cerr << "Error: the engine library has no minimal-sample F estimator (mh_estimate_fundamental_minimal)\n";
         return false;
     }
     mh_engine* e = BorrowEngine(device);
     if (!e) return false;
-    std::vector<double> s(2 * n), d(2 * n);
-    for (size_t i = 0; i < n; ++i) {
-        s[2 * i] = srcPoints[i].x; s[2 * i + 1] = srcPoints[i].y;
-        d[2 * i] = dstPoints[i].x; d[2 * i + 1] = dstPoints[i].y;
-    }
+    const PackedPoints p = PackPoints(srcPoints, dstPoints);
     std::vector<unsigned char> mask(n, 0);
     double F[9], e2[2];
     int inl = 0;
     const bool ok = Check(mh_set_fundamental_metric(e, metric), "mh_set_fundamental_metric") &&
-                    Check(mh_set_correspondences(e, s.data(), d.data(), nullptr, (int)n), "mh_set_correspondences") &&
+                    Check(mh_set_correspondences(e, p.s.data(), p.d.data(), nullptr, (int)n), "mh_set_correspondences") &&
                     (minimal ? Check(mh_estimate_fundamental_minimal(e, seed, estimator.max_samples, estimator.confidence, threshold, F, e2,
                                                                      mask.data(), &inl, nullptr), "mh_estimate_fundamental_minimal")
                              : Check(mh_estimate_fundamental(e, seed, hypotheses, threshold, F, e2, mask.data(), &inl), "mh_estimate_fundamental"));
@@ -290,398 +295,355 @@ bool multih::FilterCorrespondencesByEpipolarGeometry(std::vector<cv::Point2d>& s
     return true;
 }
 
+// diagnostic: where Process() spends its time
+struct MultiH::StageClock {
+    const bool on = std::getenv("MULTIH_TIMING") != nullptr;
+    const std::chrono::system_clock::time_point began = std::chrono::system_clock::now();
+    void operator()(const char* what) const
+    {
+        if (on) printf("[Multi-H] %s done %.1f ms after Process() began\n", what,
+                       std::chrono::duration<double, std::milli>(std::chrono::system_clock::now() - began).count());
+    }
+};
+
 bool MultiH::Run(bool points_only)
 {
-    if (src_points_original.size() < 8 || dst_points_original.size() != src_points_original.size() ||
-        (!points_only && affinities_original.size() != src_points_original.size())) {
-        std::cerr << "Error: Features are not set!\n";                       // M/MultiH.cpp:48
+    std::string error;
+    caps = multih::detail::LinkedEngineCaps();
+    if (!PlanRun(points_only, caps, plan, error)) {
+        std::cerr << error;
         return false;
     }
-    if (points_only && initial_homographies.empty() && init_mode == INIT_STABLE_SETS) {
-        std::cerr << "Error: the stable point sets (INIT_STABLE_SETS) need affinities; the point-only Process() cannot use them\n";
-        return false;
-    }
-    if (estimator != ESTIMATOR_HAF && estimator != ESTIMATOR_3PT && estimator != ESTIMATOR_DLT) {
-        std::cerr << "Error: unknown estimator " << estimator << " (ESTIMATOR_HAF, ESTIMATOR_3PT or ESTIMATOR_DLT)\n";
-        return false;
-    }
-    if (epipolar_free) {      // what needs F cannot run without one
-        if (init_mode == INIT_STABLE_SETS) {
-            std::cerr << "Error: the stable point sets (INIT_STABLE_SETS) need the fundamental matrix; the epipolar-free route (SetEpipolarFree) cannot use them\n";
-            return false;
-        }
-        if (proposal_source == PROPOSAL_SOURCE_HAF || proposal_source == PROPOSAL_SOURCE_3PT) {
-            std::cerr << "Error: " << (proposal_source == PROPOSAL_SOURCE_HAF ? "HAF proposals (PROPOSAL_SOURCE_HAF)" : "3-point proposals (PROPOSAL_SOURCE_3PT)")
-                      << " need the fundamental matrix; the epipolar-free route (SetEpipolarFree) cannot use them\n";
-            return false;
-        }
-    }
-    if (compat_fit != COMPAT_FIT_3PT && compat_fit != COMPAT_FIT_DLT) {
-        std::cerr << "Error: unknown compatibility fit " << compat_fit << " (COMPAT_FIT_3PT or COMPAT_FIT_DLT)\n";
-        return false;
-    }
-    if (compat_fit == COMPAT_FIT_DLT && run_compatibility_check) {
-        if (!mh_compat_dlt_medians) {
-            std::cerr << "Error: the engine library has no compatibility check with 4-point trials (mh_compat_dlt_medians)\n";
-            return false;
-        }
-        if (compat_trials < 1 || compat_trials > MH_COMPAT_DLT_MAX_TRIALS || !(compat_limit_scale >= 0.0) || std::isinf(compat_limit_scale)) {
-            std::cerr << "Error: SetCompatibilityFit: trials outside [1, " << MH_COMPAT_DLT_MAX_TRIALS << "] or a limit scale that is negative or not finite\n";
-            return false;
-        }
-    }
-    // where the initial batch comes from (looked at only where a batch is proposed)
-    proposal_haf_run = false;
-    proposal_3pt_run = false;
-    if (initial_homographies.empty() && init_mode != INIT_STABLE_SETS) {
-        if (proposal_source == PROPOSAL_SOURCE_3PT) {      // points and F are all it needs: the point-only Process() may use it
-            if (!mh_propose_3pt) {
-                std::cerr << "Error: the engine library has no 3-point proposals (mh_propose_3pt)\n";
-                return false;
-            }
-            proposal_3pt_run = true;
-        } else if (proposal_source != PROPOSAL_SOURCE_DLT && proposal_source != PROPOSAL_SOURCE_HAF) {
-            std::cerr << "Error: unknown proposal source " << proposal_source << " (PROPOSAL_SOURCE_DLT or PROPOSAL_SOURCE_HAF)\n";
-            return false;
-        }
-        if (proposal_source == PROPOSAL_SOURCE_HAF) {
-            if (points_only) {
-                std::cerr << "Error: HAF proposals (PROPOSAL_SOURCE_HAF) need affinities; the point-only Process() cannot use them\n";
-                return false;
-            }
-            if (!mh_propose_haf) {
-                std::cerr << "Error: the engine library has no HAF proposals (mh_propose_haf)\n";
-                return false;
-            }
-            if (proposal_haf_stride < 1 || proposal_haf_members < 0 || proposal_haf_members == 1 || proposal_haf_members == 2 ||
-                proposal_haf_members > 32) {
-                std::cerr << "Error: SetProposalSource: members = " << proposal_haf_members << ", stride = " << proposal_haf_stride
-                          << " (members 0 or in [3, 32], stride >= 1)\n";
-                return false;
-            }
-            if (proposal_sampler == PROPOSAL_LOCAL && proposal_haf_members > proposal_sampler_k) {
-                std::cerr << "Error: SetProposalSource: members = " << proposal_haf_members << " exceeds k = " << proposal_sampler_k
-                          << " of the local sampler, whose table the HAF proposals share\n";
-                return false;
-            }
-            proposal_haf_run = true;
-        }
-    }
-    point_only_run = points_only;
-    const bool timing = std::getenv("MULTIH_TIMING") != nullptr;          // diagnostic: where Process() spends its time
-    const auto t_process = std::chrono::system_clock::now();
-    auto stage = [&](const char* what) {
-        if (timing) printf("[Multi-H] %s done %.1f ms after Process() began\n", what,
-                           std::chrono::duration<double, std::milli>(std::chrono::system_clock::now() - t_process).count());
-    };
-    if (!EnsureEngine()) return false;
-    // the re-estimator of the loop and of the proposal refit (sticky on the engine, and engines are reused)
-    // (the epipolar-free route: the N-point DLT, which reads no F; the point-only route: the 3-point fit unless the DLT is asked for)
-    const int est = epipolar_free || estimator == ESTIMATOR_DLT ? MH_ESTIMATOR_DLT : points_only ? MH_ESTIMATOR_3PT : estimator;
-    if (!mh_set_estimator || !mh_refine_points) {
-        if (est != MH_ESTIMATOR_HAF) {
-            std::cerr << "Error: the engine library has no point-only entry points (mh_set_estimator, mh_refine_points)\n";
-            return false;
-        }
-    } else if (!Check(mh_set_estimator(engine, est), "mh_set_estimator")) {
-        return false;
-    }
-    if (merge_mode != MERGE_MEAN_SHIFT && merge_mode != MERGE_ENERGY) {
-        std::cerr << "Error: unknown merge mode (SetMergeMode)\n";
-        return false;
-    }
-    if (merge_mode == MERGE_ENERGY && (!mh_merge_deltas || !mh_labeling_energy)) {
-        std::cerr << "Error: the engine library has no energy-tested merge (mh_merge_deltas, mh_labeling_energy)\n";
-        return false;
-    }
-    if (!(label_cost_points >= 0.0) || !std::isfinite(label_cost_points)) {
-        std::cerr << "Error: the label cost must be finite and not negative (SetLabelCost)\n";
-        return false;
-    }
-    if (label_cost_points > 0.0 && merge_mode != MERGE_ENERGY) {
-        std::cerr << "Error: a label cost needs the energy-tested merge (SetLabelCost with SetMergeMode(MERGE_ENERGY))\n";
-        return false;
-    }
-    if (label_cost_points > 0.0 && !mh_drop_deltas) {
-        std::cerr << "Error: the engine library has no label-drop evaluation (mh_drop_deltas)\n";
-        return false;
-    }
-    {
-        // beta in energy units: `points` outliers' worth, round(lam * T) each (mh_data_cost's outlier cost)
-        const double outlier = std::round((100.0 / energy_lambda) * (threshold_homography * threshold_homography * 81.0 / 16.0));
-        const double beta = label_cost_points * outlier;
-        if (!(beta < 9.0e18)) {
-            std::cerr << "Error: the label cost is too large (SetLabelCost)\n";
-            return false;
-        }
-        label_cost_beta = std::llround(beta);
-    }
-    // the data term of the labeling (sticky on the engine, and engines are reused)
-    if (!mh_set_data_term) {
-        if (data_term != DATA_TERM_REFERENCE) {
-            std::cerr << "Error: the engine library has no selectable data term (mh_set_data_term)\n";
-            return false;
-        }
-    } else if (!Check(mh_set_data_term(engine, data_term), "mh_set_data_term")) {
-        return false;
-    }
-    // the error of the whole route (sticky on the engine, and engines are reused: set both ways)
-    if (residual != RESIDUAL_FORWARD && residual != RESIDUAL_SYMMETRIC) {
-        std::cerr << "Error: unknown residual " << residual << " (RESIDUAL_FORWARD or RESIDUAL_SYMMETRIC)\n";
-        return false;
-    }
-    if (residual == RESIDUAL_SYMMETRIC && (tail_score == TAIL_SCORE_MSAC || (init_mode != INIT_STABLE_SETS && selection_score == SELECTION_SCORE_MSAC))) {
-        std::cerr << "Error: the MSAC weights (TAIL_SCORE_MSAC, SELECTION_SCORE_MSAC) measure the forward error only; they do not combine with RESIDUAL_SYMMETRIC\n";
-        return false;
-    }
-    if (!mh_set_residual_mode || !mh_set_residual_scope) {
-        if (residual != RESIDUAL_FORWARD) {
-            std::cerr << "Error: the engine library has no symmetric route (mh_set_residual_mode, mh_set_residual_scope)\n";
-            return false;
-        }
-    } else if (!Check(mh_set_residual_mode(engine, residual == RESIDUAL_SYMMETRIC ? MH_RESIDUAL_SYMMETRIC : MH_RESIDUAL_FORWARD), "mh_set_residual_mode") ||
-               !Check(mh_set_residual_scope(engine, residual == RESIDUAL_SYMMETRIC ? MH_RESIDUAL_SCOPE_ROUTE : MH_RESIDUAL_SCOPE_SCORE), "mh_set_residual_scope")) {
-        return false;
-    }
-    // how the degenerate tail ranks its hypotheses
-    if (tail_score != TAIL_SCORE_COUNT && tail_score != TAIL_SCORE_MSAC) {
-        std::cerr << "Error: unknown tail score " << tail_score << " (TAIL_SCORE_COUNT or TAIL_SCORE_MSAC)\n";
-        return false;
-    }
-    if (tail_score == TAIL_SCORE_MSAC && (!mh_score_msac || !mh_select_best_msac || !mh_get_model)) {
-        std::cerr << "Error: the engine library has no MSAC scores (mh_score_msac, mh_select_best_msac, mh_get_model)\n";
-        return false;
-    }
-    // whether the degenerate tail refits its winner
-    if (tail_refit < 0 || tail_refit > 16) {
-        std::cerr << "Error: tail refit iterations " << tail_refit << " outside [0, 16]\n";
-        return false;
-    }
-    if (tail_refit > 0 && (!mh_refit_homography || !mh_get_model)) {
-        std::cerr << "Error: the engine library has no homography refit (mh_refit_homography, mh_get_model)\n";
-        return false;
-    }
-    // whether the tail's result and the final models are polished
-    if (tail_polish < 0 || tail_polish > 32) {
-        std::cerr << "Error: tail polish iterations " << tail_polish << " outside [0, 32]\n";
-        return false;
-    }
-    if (model_polish < 0 || model_polish > 32) {
-        std::cerr << "Error: model polish iterations " << model_polish << " outside [0, 32]\n";
-        return false;
-    }
-    if ((tail_polish > 0 || model_polish > 0) && !mh_polish_homographies) {
-        std::cerr << "Error: the engine library has no homography polish (mh_polish_homographies)\n";
-        return false;
-    }
-    if (tail_polish > 0 && !mh_get_model) {
-        std::cerr << "Error: the engine library has no single-model read-back for the tail's polish (mh_get_model)\n";
-        return false;
-    }
-    // whether the final models and the loop's DLT re-estimator run reweighted rounds
-    if (model_reweight < 0 || model_reweight > 16 || estimator_reweight < 0 || estimator_reweight > 16) {
-        std::cerr << "Error: reweighting rounds " << model_reweight << " (final) / " << estimator_reweight << " (estimator) outside [0, 16]\n";
-        return false;
-    }
-    if (!(model_reweight_scale >= 0.0) || !(estimator_reweight_scale >= 0.0) || std::isinf(model_reweight_scale) ||
-        std::isinf(estimator_reweight_scale)) {
-        std::cerr << "Error: reweighting scale " << model_reweight_scale << " (final) / " << estimator_reweight_scale
-                  << " (estimator) is not a finite number >= 0\n";
-        return false;
-    }
-    if (model_reweight > 0 && !mh_reweight_homographies) {
-        std::cerr << "Error: the engine library has no reweighted refit (mh_reweight_homographies)\n";
-        return false;
-    }
-    {
-        // sticky on the engine, and engines are reused: set on every call, off unless the DLT estimator runs with rounds
-        const int rw = est == MH_ESTIMATOR_DLT ? estimator_reweight : 0;
-        const double px = estimator_reweight_scale > 0.0 ? estimator_reweight_scale : threshold_homography;
-        if (!mh_set_estimator_reweighting) {
-            if (rw > 0) {
-                std::cerr << "Error: the engine library has no reweighted estimator (mh_set_estimator_reweighting)\n";
-                return false;
-            }
-        } else if (!Check(mh_set_estimator_reweighting(engine, rw, px * px), "mh_set_estimator_reweighting")) {
-            return false;
-        }
-    }
-    // ... or reweighted rounds whose scale follows each label's own residuals (SetModelReweightAuto, SetEstimatorReweightAuto)
-    if (model_reweight_auto < 0 || model_reweight_auto > 16 || estimator_reweight_auto < 0 || estimator_reweight_auto > 16) {
-        std::cerr << "Error: self-scaled reweighting rounds " << model_reweight_auto << " (final) / " << estimator_reweight_auto
-                  << " (estimator) outside [0, 16]\n";
-        return false;
-    }
-    if (!(model_reweight_kappa >= 0.0) || !(estimator_reweight_kappa >= 0.0) || model_reweight_kappa > 1e150 ||
-        estimator_reweight_kappa > 1e150) {
-        std::cerr << "Error: self-scaled reweighting kappa " << model_reweight_kappa << " (final) / " << estimator_reweight_kappa
-                  << " (estimator) is not a finite number >= 0\n";
-        return false;
-    }
-    if ((model_reweight > 0 && model_reweight_auto > 0) || (estimator_reweight > 0 && estimator_reweight_auto > 0)) {
-        std::cerr << "Error: both the fixed and the self-scaled reweighting are set for the "
-                  << (model_reweight > 0 && model_reweight_auto > 0 ? "final refit" : "estimator") << "; choose one\n";
-        return false;
-    }
-    if (model_reweight_auto > 0 && !mh_reweight_homographies_auto) {
-        std::cerr << "Error: the engine library has no self-scaled reweighted refit (mh_reweight_homographies_auto)\n";
-        return false;
-    }
-    {
-        // set behind the fixed setting, and only with rounds: of the engine's two setters the last call decides
-        const int rw = est == MH_ESTIMATOR_DLT ? estimator_reweight_auto : 0;
-        if (rw > 0) {
-            if (!mh_set_estimator_reweighting_auto) {
-                std::cerr << "Error: the engine library has no self-scaled reweighted estimator (mh_set_estimator_reweighting_auto)\n";
-                return false;
-            }
-            if (!Check(mh_set_estimator_reweighting_auto(engine, rw, 1, 2, AutoKappa2(estimator_reweight_kappa), DBL_MIN, AutoScaleMax()),
-                       "mh_set_estimator_reweighting_auto"))
-                return false;
-        }
-    }
-    // how ProposeModels ranks a batch (INIT_STABLE_SETS proposes nothing: the mode is not looked at)
-    if (init_mode != INIT_STABLE_SETS) {
-        if (selection_score != SELECTION_SCORE_COUNT && selection_score != SELECTION_SCORE_MSAC) {
-            std::cerr << "Error: unknown selection score " << selection_score << " (SELECTION_SCORE_COUNT or SELECTION_SCORE_MSAC)\n";
-            return false;
-        }
-        if (selection_score == SELECTION_SCORE_MSAC && !mh_select_greedy_msac) {
-            std::cerr << "Error: the engine library has no selection ranked by MSAC weight (mh_select_greedy_msac)\n";
-            return false;
-        }
-    }
+    const StageClock stage;
+    if (!EnsureEngine() || !ConfigureEngine(plan)) return false;
     stage("engine");
 
     // GetFundamentalMatrixAndRefineData (M/MultiH.cpp:52, :770-848; §8(f) row 4): with
     // SetEpipolarGeometry the caller's F / e2 are used and the points are taken as already
-    // filtered; otherwise F is estimated on the GPU below.
+    // filtered; otherwise F is estimated on the GPU (FrontHalf).
     src_points = src_points_original;
     dst_points = dst_points_original;
     affinities = affinities_original;
     degenerate_case = false;
     cluster_homographies.clear();
     labeling.clear();
-
-    const int N = static_cast<int>(src_points.size());
     front_stages = FrontStages();
-    front_stages.input = front_stages.in_ransac_mask = front_stages.triangulated = front_stages.affine_consistent = N;
-    std::vector<double> s(2 * (size_t)N), d(2 * (size_t)N), a(4 * (size_t)N);
-    for (int i = 0; i < N; ++i) {
-        s[2 * i] = src_points[i].x; s[2 * i + 1] = src_points[i].y;
-        d[2 * i] = dst_points[i].x; d[2 * i + 1] = dst_points[i].y;
-        if (points_only) continue;
-        const cv::Mat& A = affinities[i];
-        a[4 * i] = A.at<double>(0, 0); a[4 * i + 1] = A.at<double>(0, 1);
-        a[4 * i + 2] = A.at<double>(1, 0); a[4 * i + 3] = A.at<double>(1, 1);
-    }
-    if (!Check(mh_set_correspondences(engine, s.data(), d.data(), points_only ? nullptr : a.data(), N), "mh_set_correspondences"))
-        return false;
+    front_stages.input = front_stages.in_ransac_mask = front_stages.triangulated = front_stages.affine_consistent =
+        static_cast<int>(src_points.size());
+    if (!UploadCorrespondences(src_points, dst_points, affinities)) return false;
     stage("correspondences on the device");
 
-    if (epipolar_free) {
-        // no F is estimated, no correspondence refined or dropped: the stage table keeps the input count four times
-        if (have_epipolar) printf("[Multi-H] Epipolar-free route: the epipolar geometry given by SetEpipolarGeometry is ignored.\n");
-    } else if (!have_epipolar) {
-        // GetFundamentalMatrixAndRefineData (M/MultiH.cpp:770-848) on the GPU: RANSAC over normalised
-        // 8-point hypotheses with Sampson scoring, LS refit, epipoles from F^T F / F F^T, then the
-        // per-correspondence refinement of :807-838.
-        std::vector<unsigned char> mask(N, 0);
-        int inl = 0;
-        if (fundamental_estimator.mode != FUND_ESTIMATOR_LS8 && fundamental_estimator.mode != FUND_ESTIMATOR_MINIMAL7) {
-            std::cerr << "Error: unknown F estimator " << fundamental_estimator.mode << " (FUND_ESTIMATOR_LS8 or FUND_ESTIMATOR_MINIMAL7)\n";
-            return false;
-        }
-        const bool minimal = fundamental_estimator.mode == FUND_ESTIMATOR_MINIMAL7;
-        if (minimal && !mh_estimate_fundamental_minimal) {
-            std::cerr << "Error: the engine library has no minimal-sample F estimator (mh_estimate_fundamental_minimal)\n";
-            return false;
-        }
-        const bool ok = minimal ? Check(mh_estimate_fundamental_minimal(engine, proposal_seed ^ 0xf00dull, fundamental_estimator.max_samples,
-                                                                        fundamental_estimator.confidence, threshold_fundamental_matrix,
-                                                                        fundamental_matrix, epipole_2, mask.data(), &inl, nullptr),
-                                        "mh_estimate_fundamental_minimal")
-                                : Check(mh_estimate_fundamental(engine, proposal_seed ^ 0xf00dull, fundamental_hypotheses,
-                                                                threshold_fundamental_matrix, fundamental_matrix, epipole_2,
-                                                                mask.data(), &inl),
-                                        "mh_estimate_fundamental");
-        double nrm = 0.0;
-        for (double f : fundamental_matrix) nrm += f * f;
-        degenerate_case = !ok || !(std::sqrt(nrm) >= 1e-5) || !std::isfinite(epipole_2[0]) ||
-                          !std::isfinite(epipole_2[1]);                             // :779
-        if (degenerate_case) {
-            printf("[Multi-H] Degenerate case, the fundamental matrix cannot be estimated.\n");
-        } else {
-            // :807-838 on the GPU: Hartley-Sturm correction, affine consistency filter, optimal affinity (the point-only
-            // route: the correction alone, mh_refine_points)
-            double e1[2];
-            std::vector<unsigned char> keep(N, 0);
-            const int stride = points_only ? 4 : 8;
-            std::vector<double> refined(stride * (size_t)N);
-            if (!Check(mh_epipoles(engine, fundamental_matrix, e1, epipole_2), "mh_epipoles"))
-                return false;
-            if (points_only ? !Check(mh_refine_points(engine, fundamental_matrix, e1, epipole_2, mask.data(), keep.data(), refined.data()),
-                                     "mh_refine_points")
-                            : !Check(mh_refine_correspondences(engine, fundamental_matrix, e1, epipole_2, mask.data(), keep.data(),
-                                                               refined.data()),
-                                     "mh_refine_correspondences"))
-                return false;
-            std::vector<unsigned char> reason(N, 0);
-            if (!Check(mh_get_refine_reasons(engine, reason.data(), N), "mh_get_refine_reasons")) return false;
-            front_stages.in_ransac_mask = front_stages.triangulated = front_stages.affine_consistent = 0;
-            for (int i = 0; i < N; ++i) {
-                if (reason[i] != MH_REFINE_NOT_IN_MASK) ++front_stages.in_ransac_mask;
-                if (reason[i] == MH_REFINE_KEPT || reason[i] == MH_REFINE_AFFINE_TEST) ++front_stages.triangulated;
-                if (reason[i] == MH_REFINE_KEPT) ++front_stages.affine_consistent;
-            }
-            std::vector<cv::Point2d> s2, d2;
-            std::vector<cv::Mat> a2;
-            for (int i = 0; i < N; ++i)
-                if (keep[i]) {
-                    const double* r = &refined[stride * (size_t)i];
-                    s2.push_back(cv::Point2d(r[0], r[1]));
-                    d2.push_back(cv::Point2d(r[2], r[3]));
-                    if (!points_only) a2.push_back(OwnedMat(2, 2, r + 4));
-                }
-            printf("[Multi-H] %d points kept from the initial %d after filtering.\n", (int)s2.size(), N);   // :840
-            if (log_to_console)
-                printf("[Multi-H]   stages: %d in the RANSAC mask at %.2f px, %d after OptimalTriangulation, %d after distanceError <= 1\n",
-                       front_stages.in_ransac_mask, threshold_fundamental_matrix, front_stages.triangulated, front_stages.affine_consistent);
-            if (s2.size() < 8) {
-                degenerate_case = true;
-                printf("[Multi-H] Degenerate case, not enough points remained.\n");                         // :845
-            } else {
-                src_points.swap(s2); dst_points.swap(d2); affinities.swap(a2);
-                const int K = static_cast<int>(src_points.size());
-                std::vector<double> ss(2 * (size_t)K), dd(2 * (size_t)K), aa(4 * (size_t)K);
-                for (int i = 0; i < K; ++i) {
-                    ss[2 * i] = src_points[i].x; ss[2 * i + 1] = src_points[i].y;
-                    dd[2 * i] = dst_points[i].x; dd[2 * i + 1] = dst_points[i].y;
-                    if (points_only) continue;
-                    const cv::Mat& A = affinities[i];
-                    aa[4 * i] = A.at<double>(0, 0); aa[4 * i + 1] = A.at<double>(0, 1);
-                    aa[4 * i + 2] = A.at<double>(1, 0); aa[4 * i + 3] = A.at<double>(1, 1);
-                }
-                if (!Check(mh_set_correspondences(engine, ss.data(), dd.data(), points_only ? nullptr : aa.data(), K), "mh_set_correspondences"))
-                    return false;
-            }
-        }
-    }
-
+    if (!FrontHalf()) return false;
     if (degenerate_case) {
         HandleDegenerateCase();
         return true;
     }
     if (!epipolar_free && !Check(mh_set_epipolar(engine, fundamental_matrix, epipole_2), "mh_set_epipolar")) return false;
+    if (!BuildProposalTables(stage) || !InitialModels()) return false;
+    stage("initial models");
+    ClusterMergingAndLabeling();
+    stage("neighbourhood + alternation");
+    return PostFilter() && Finish();
+}
 
-    // The proposal sampler: its three arguments are checked here, once; then the local sampler's table, once, on the
-    // correspondences the proposer samples (the refined ones).
+namespace {
+// A refusal of PlanRun: `return Refuse(error) << text << value;` leaves what was streamed in `error` and returns false.
+struct Refuse {
+    explicit Refuse(std::string& e) : error(e) {}
+    ~Refuse() { error = text.str(); }
+    template <class T> Refuse& operator<<(const T& v) { text << v; return *this; }
+    operator bool() const { return false; }
+    std::string& error;
+    std::ostringstream text;
+};
+// The idiom of every optional mode — no entry point: fine while the setting is at its default, an error otherwise.
+bool Offers(bool have, bool wanted, const char* message, std::string& error)
+{
+    return have || !wanted || (Refuse(error) << message);
+}
+} // namespace
+
+// Every check of Process() that depends on nothing but the settings and on what the engine library offers, in the order the
+// checks have always had, and what the run derives from the settings.  Touches no engine and prints nothing: Run() prints
+// `error`.  All of these checks precede the creation of the engine and the engine's own setters, so where two settings are
+// wrong at once — or no device can be opened — the message can be that of a check which once came behind an engine call;
+// with one wrong setting the message and the return value are what they were.  The checks behind the front half
+// (FrontHalf: the F estimator; BuildProposalTables: the sampler and the HAF table) stay there, because a degenerate front
+// half returns true ahead of them, and what the engine validates (the data term, the fundamental metric) the engine refuses.
+bool MultiH::PlanRun(bool points_only, const EngineCaps& have, RunPlan& out, std::string& error) const
+{
+    out = RunPlan();
+    out.points_only = points_only;
+    if (src_points_original.size() < 8 || dst_points_original.size() != src_points_original.size() ||
+        (!points_only && affinities_original.size() != src_points_original.size()))
+        return Refuse(error) << "Error: Features are not set!\n";                       // M/MultiH.cpp:48
+    if (points_only && initial_homographies.empty() && init_mode == INIT_STABLE_SETS)
+        return Refuse(error) << "Error: the stable point sets (INIT_STABLE_SETS) need affinities; the point-only Process() cannot use them\n";
+    if (estimator != ESTIMATOR_HAF && estimator != ESTIMATOR_3PT && estimator != ESTIMATOR_DLT)
+        return Refuse(error) << "Error: unknown estimator " << estimator << " (ESTIMATOR_HAF, ESTIMATOR_3PT or ESTIMATOR_DLT)\n";
+    if (epipolar_free) {      // what needs F cannot run without one
+        if (init_mode == INIT_STABLE_SETS)
+            return Refuse(error) << "Error: the stable point sets (INIT_STABLE_SETS) need the fundamental matrix; the epipolar-free route (SetEpipolarFree) cannot use them\n";
+        if (proposal_source == PROPOSAL_SOURCE_HAF || proposal_source == PROPOSAL_SOURCE_3PT)
+            return Refuse(error) << "Error: " << (proposal_source == PROPOSAL_SOURCE_HAF ? "HAF proposals (PROPOSAL_SOURCE_HAF)" : "3-point proposals (PROPOSAL_SOURCE_3PT)")
+                                 << " need the fundamental matrix; the epipolar-free route (SetEpipolarFree) cannot use them\n";
+    }
+    if (compat_fit != COMPAT_FIT_3PT && compat_fit != COMPAT_FIT_DLT)
+        return Refuse(error) << "Error: unknown compatibility fit " << compat_fit << " (COMPAT_FIT_3PT or COMPAT_FIT_DLT)\n";
+    if (compat_fit == COMPAT_FIT_DLT && run_compatibility_check) {
+        if (!Offers(have.compat_dlt, true, "Error: the engine library has no compatibility check with 4-point trials (mh_compat_dlt_medians)\n", error))
+            return false;
+        if (compat_trials < 1 || compat_trials > MH_COMPAT_DLT_MAX_TRIALS || !(compat_limit_scale >= 0.0) || std::isinf(compat_limit_scale))
+            return Refuse(error) << "Error: SetCompatibilityFit: trials outside [1, " << MH_COMPAT_DLT_MAX_TRIALS << "] or a limit scale that is negative or not finite\n";
+    }
+    // where the batches come from (looked at only where a batch is proposed)
+    if (initial_homographies.empty() && init_mode != INIT_STABLE_SETS) {
+        if (proposal_source == PROPOSAL_SOURCE_3PT) {      // points and F are all it needs: the point-only Process() may use it
+            if (!Offers(have.propose_3pt, true, "Error: the engine library has no 3-point proposals (mh_propose_3pt)\n", error)) return false;
+            out.initial_source = out.iterative_source = PROPOSAL_SOURCE_3PT;
+        } else if (proposal_source != PROPOSAL_SOURCE_DLT && proposal_source != PROPOSAL_SOURCE_HAF) {
+            return Refuse(error) << "Error: unknown proposal source " << proposal_source << " (PROPOSAL_SOURCE_DLT or PROPOSAL_SOURCE_HAF)\n";
+        }
+        if (proposal_source == PROPOSAL_SOURCE_HAF) {
+            if (points_only)
+                return Refuse(error) << "Error: HAF proposals (PROPOSAL_SOURCE_HAF) need affinities; the point-only Process() cannot use them\n";
+            if (!Offers(have.propose_haf, true, "Error: the engine library has no HAF proposals (mh_propose_haf)\n", error)) return false;
+            if (proposal_haf_stride < 1 || proposal_haf_members < 0 || proposal_haf_members == 1 || proposal_haf_members == 2 ||
+                proposal_haf_members > 32)
+                return Refuse(error) << "Error: SetProposalSource: members = " << proposal_haf_members << ", stride = " << proposal_haf_stride
+                                     << " (members 0 or in [3, 32], stride >= 1)\n";
+            if (proposal_sampler == PROPOSAL_LOCAL && proposal_haf_members > proposal_sampler_k)
+                return Refuse(error) << "Error: SetProposalSource: members = " << proposal_haf_members << " exceeds k = " << proposal_sampler_k
+                                     << " of the local sampler, whose table the HAF proposals share\n";
+            out.initial_source = PROPOSAL_SOURCE_HAF;      // (the iterative batches stay DLT)
+        }
+    }
+    // the re-estimator of the loop and of the proposal refit
+    // (the epipolar-free route: the N-point DLT, which reads no F; the point-only route: the 3-point fit unless the DLT is asked for)
+    out.est = epipolar_free || estimator == ESTIMATOR_DLT ? MH_ESTIMATOR_DLT : points_only ? MH_ESTIMATOR_3PT : estimator;
+    if (!Offers(have.point_only, out.est != MH_ESTIMATOR_HAF,
+                "Error: the engine library has no point-only entry points (mh_set_estimator, mh_refine_points)\n", error))
+        return false;
+    if (merge_mode != MERGE_MEAN_SHIFT && merge_mode != MERGE_ENERGY) return Refuse(error) << "Error: unknown merge mode (SetMergeMode)\n";
+    if (!Offers(have.energy_merge, merge_mode == MERGE_ENERGY,
+                "Error: the engine library has no energy-tested merge (mh_merge_deltas, mh_labeling_energy)\n", error))
+        return false;
+    if (!(label_cost_points >= 0.0) || !std::isfinite(label_cost_points))
+        return Refuse(error) << "Error: the label cost must be finite and not negative (SetLabelCost)\n";
+    if (label_cost_points > 0.0 && merge_mode != MERGE_ENERGY)
+        return Refuse(error) << "Error: a label cost needs the energy-tested merge (SetLabelCost with SetMergeMode(MERGE_ENERGY))\n";
+    if (!Offers(have.drop_deltas, label_cost_points > 0.0, "Error: the engine library has no label-drop evaluation (mh_drop_deltas)\n", error))
+        return false;
+    // beta in energy units: `points` outliers' worth, round(lam * T) each (mh_data_cost's outlier cost)
+    const double outlier = std::round((100.0 / energy_lambda) * (threshold_homography * threshold_homography * 81.0 / 16.0));
+    const double beta = label_cost_points * outlier;
+    if (!(beta < 9.0e18)) return Refuse(error) << "Error: the label cost is too large (SetLabelCost)\n";
+    out.label_cost_beta = std::llround(beta);
+    // the data term of the labeling (an unknown value is the engine's to refuse)
+    if (!Offers(have.data_term, data_term != DATA_TERM_REFERENCE, "Error: the engine library has no selectable data term (mh_set_data_term)\n", error))
+        return false;
+    // the error of the whole route
+    if (residual != RESIDUAL_FORWARD && residual != RESIDUAL_SYMMETRIC)
+        return Refuse(error) << "Error: unknown residual " << residual << " (RESIDUAL_FORWARD or RESIDUAL_SYMMETRIC)\n";
+    if (residual == RESIDUAL_SYMMETRIC && (tail_score == TAIL_SCORE_MSAC || (init_mode != INIT_STABLE_SETS && selection_score == SELECTION_SCORE_MSAC)))
+        return Refuse(error) << "Error: the MSAC weights (TAIL_SCORE_MSAC, SELECTION_SCORE_MSAC) measure the forward error only; they do not combine with RESIDUAL_SYMMETRIC\n";
+    if (!Offers(have.residual_route, residual != RESIDUAL_FORWARD,
+                "Error: the engine library has no symmetric route (mh_set_residual_mode, mh_set_residual_scope)\n", error))
+        return false;
+    out.residual_mode = residual == RESIDUAL_SYMMETRIC ? MH_RESIDUAL_SYMMETRIC : MH_RESIDUAL_FORWARD;
+    out.residual_scope = residual == RESIDUAL_SYMMETRIC ? MH_RESIDUAL_SCOPE_ROUTE : MH_RESIDUAL_SCOPE_SCORE;
+    return PlanFinishModes(have, out, error);
+}
+
+// ... continued: the degenerate tail, the refits of the results and of the loop's estimator, the selection.
+bool MultiH::PlanFinishModes(const EngineCaps& have, RunPlan& out, std::string& error) const
+{
+    // how the degenerate tail ranks its hypotheses
+    if (tail_score != TAIL_SCORE_COUNT && tail_score != TAIL_SCORE_MSAC)
+        return Refuse(error) << "Error: unknown tail score " << tail_score << " (TAIL_SCORE_COUNT or TAIL_SCORE_MSAC)\n";
+    if (!Offers(have.msac_scores && have.get_model, tail_score == TAIL_SCORE_MSAC,
+                "Error: the engine library has no MSAC scores (mh_score_msac, mh_select_best_msac, mh_get_model)\n", error))
+        return false;
+    // whether the degenerate tail refits its winner
+    if (tail_refit < 0 || tail_refit > 16) return Refuse(error) << "Error: tail refit iterations " << tail_refit << " outside [0, 16]\n";
+    if (!Offers(have.refit && have.get_model, tail_refit > 0,
+                "Error: the engine library has no homography refit (mh_refit_homography, mh_get_model)\n", error))
+        return false;
+    // whether the tail's result and the final models are polished
+    if (tail_polish < 0 || tail_polish > 32) return Refuse(error) << "Error: tail polish iterations " << tail_polish << " outside [0, 32]\n";
+    if (model_polish < 0 || model_polish > 32) return Refuse(error) << "Error: model polish iterations " << model_polish << " outside [0, 32]\n";
+    if (!Offers(have.polish, tail_polish > 0 || model_polish > 0, "Error: the engine library has no homography polish (mh_polish_homographies)\n", error))
+        return false;
+    if (!Offers(have.get_model, tail_polish > 0, "Error: the engine library has no single-model read-back for the tail's polish (mh_get_model)\n", error))
+        return false;
+    // whether the final models and the loop's DLT re-estimator run reweighted rounds
+    if (model_reweight < 0 || model_reweight > 16 || estimator_reweight < 0 || estimator_reweight > 16)
+        return Refuse(error) << "Error: reweighting rounds " << model_reweight << " (final) / " << estimator_reweight << " (estimator) outside [0, 16]\n";
+    if (!(model_reweight_scale >= 0.0) || !(estimator_reweight_scale >= 0.0) || std::isinf(model_reweight_scale) ||
+        std::isinf(estimator_reweight_scale))
+        return Refuse(error) << "Error: reweighting scale " << model_reweight_scale << " (final) / " << estimator_reweight_scale
+                             << " (estimator) is not a finite number >= 0\n";
+    if (!Offers(have.reweight, model_reweight > 0, "Error: the engine library has no reweighted refit (mh_reweight_homographies)\n", error))
+        return false;
+    const bool dlt = out.est == MH_ESTIMATOR_DLT;      // the estimator's rounds are off unless the DLT estimator runs
+    if (!Offers(have.estimator_reweighting, dlt && estimator_reweight > 0,
+                "Error: the engine library has no reweighted estimator (mh_set_estimator_reweighting)\n", error))
+        return false;
+    // ... or reweighted rounds whose scale follows each label's own residuals (SetModelReweightAuto, SetEstimatorReweightAuto)
+    if (model_reweight_auto < 0 || model_reweight_auto > 16 || estimator_reweight_auto < 0 || estimator_reweight_auto > 16)
+        return Refuse(error) << "Error: self-scaled reweighting rounds " << model_reweight_auto << " (final) / " << estimator_reweight_auto
+                             << " (estimator) outside [0, 16]\n";
+    if (!(model_reweight_kappa >= 0.0) || !(estimator_reweight_kappa >= 0.0) || model_reweight_kappa > 1e150 ||
+        estimator_reweight_kappa > 1e150)
+        return Refuse(error) << "Error: self-scaled reweighting kappa " << model_reweight_kappa << " (final) / " << estimator_reweight_kappa
+                             << " (estimator) is not a finite number >= 0\n";
+    if ((model_reweight > 0 && model_reweight_auto > 0) || (estimator_reweight > 0 && estimator_reweight_auto > 0))
+        return Refuse(error) << "Error: both the fixed and the self-scaled reweighting are set for the "
+                             << (model_reweight > 0 && model_reweight_auto > 0 ? "final refit" : "estimator") << "; choose one\n";
+    if (!Offers(have.reweight_auto, model_reweight_auto > 0,
+                "Error: the engine library has no self-scaled reweighted refit (mh_reweight_homographies_auto)\n", error))
+        return false;
+    if (!Offers(have.estimator_reweighting_auto, dlt && estimator_reweight_auto > 0,
+                "Error: the engine library has no self-scaled reweighted estimator (mh_set_estimator_reweighting_auto)\n", error))
+        return false;
+    const double px = estimator_reweight_scale > 0.0 ? estimator_reweight_scale : threshold_homography;
+    out.estimator_reweight_auto = dlt && estimator_reweight_auto > 0;
+    out.estimator_reweight_rounds = !dlt ? 0 : out.estimator_reweight_auto ? estimator_reweight_auto : estimator_reweight;
+    out.estimator_reweight_c2 = px * px;
+    // how ProposeModels ranks a batch (INIT_STABLE_SETS proposes nothing: the mode is not looked at)
+    if (init_mode == INIT_STABLE_SETS) return true;
+    if (selection_score != SELECTION_SCORE_COUNT && selection_score != SELECTION_SCORE_MSAC)
+        return Refuse(error) << "Error: unknown selection score " << selection_score << " (SELECTION_SCORE_COUNT or SELECTION_SCORE_MSAC)\n";
+    return Offers(have.select_greedy_msac, selection_score == SELECTION_SCORE_MSAC,
+                  "Error: the engine library has no selection ranked by MSAC weight (mh_select_greedy_msac)\n", error);
+}
+
+// The engine's sticky settings, every one on every call because engines are reused.  A setter the library lacks is skipped:
+// PlanRun has made sure that the setting is then at its default.
+bool MultiH::ConfigureEngine(const RunPlan& p)
+{
+    if (caps.point_only && !Check(mh_set_estimator(engine, p.est), "mh_set_estimator")) return false;
+    if (caps.data_term && !Check(mh_set_data_term(engine, data_term), "mh_set_data_term")) return false;
+    if (caps.residual_route && (!Check(mh_set_residual_mode(engine, p.residual_mode), "mh_set_residual_mode") ||
+                                !Check(mh_set_residual_scope(engine, p.residual_scope), "mh_set_residual_scope")))
+        return false;
+    if (caps.estimator_reweighting &&
+        !Check(mh_set_estimator_reweighting(engine, p.estimator_reweight_auto ? 0 : p.estimator_reweight_rounds, p.estimator_reweight_c2),
+               "mh_set_estimator_reweighting"))
+        return false;
+    // set behind the fixed setting, and only with rounds: of the engine's two setters the last call decides
+    return !p.estimator_reweight_auto ||
+           Check(mh_set_estimator_reweighting_auto(engine, p.estimator_reweight_rounds, 1, 2, AutoKappa2(estimator_reweight_kappa), DBL_MIN,
+                                                   AutoScaleMax()),
+                 "mh_set_estimator_reweighting_auto");
+}
+
+bool MultiH::UploadCorrespondences(const std::vector<cv::Point2d>& src, const std::vector<cv::Point2d>& dst, const std::vector<cv::Mat>& aff)
+{
+    const PackedPoints p = PackPoints(src, dst, plan.points_only ? nullptr : &aff);
+    return Check(mh_set_correspondences(engine, p.s.data(), p.d.data(), p.affinities(), static_cast<int>(src.size())), "mh_set_correspondences");
+}
+
+// GetFundamentalMatrixAndRefineData (M/MultiH.cpp:770-848) on the GPU: RANSAC over normalised 8-point hypotheses with
+// Sampson scoring, LS refit, epipoles from F^T F / F F^T, then the per-correspondence refinement of :807-838 (RefineData).
+// Nothing to do with the caller's F or on the route without one.  Leaves degenerate_case set where no F can be had.
+bool MultiH::FrontHalf()
+{
+    if (epipolar_free) {
+        // no F is estimated, no correspondence refined or dropped: the stage table keeps the input count four times
+        if (have_epipolar) printf("[Multi-H] Epipolar-free route: the epipolar geometry given by SetEpipolarGeometry is ignored.\n");
+        return true;
+    }
+    if (have_epipolar) return true;
+    std::vector<unsigned char> mask(src_points.size(), 0);
+    int inl = 0;
+    if (fundamental_estimator.mode != FUND_ESTIMATOR_LS8 && fundamental_estimator.mode != FUND_ESTIMATOR_MINIMAL7) {
+        std::cerr << "Error: unknown F estimator " << fundamental_estimator.mode << " (FUND_ESTIMATOR_LS8 or FUND_ESTIMATOR_MINIMAL7)\n";
+        return false;
+    }
+    const bool minimal = fundamental_estimator.mode == FUND_ESTIMATOR_MINIMAL7;
+    if (minimal && !caps.fundamental_minimal) {
+        std::cerr << "Error: the engine library has no minimal-sample F estimator (mh_estimate_fundamental_minimal)\n";
+        return false;
+    }
+    const bool ok = minimal ? Check(mh_estimate_fundamental_minimal(engine, proposal_seed ^ 0xf00dull, fundamental_estimator.max_samples,
+                                                                    fundamental_estimator.confidence, threshold_fundamental_matrix,
+                                                                    fundamental_matrix, epipole_2, mask.data(), &inl, nullptr),
+                                    "mh_estimate_fundamental_minimal")
+                            : Check(mh_estimate_fundamental(engine, proposal_seed ^ 0xf00dull, fundamental_hypotheses,
+                                                            threshold_fundamental_matrix, fundamental_matrix, epipole_2,
+                                                            mask.data(), &inl),
+                                    "mh_estimate_fundamental");
+    double nrm = 0.0;
+    for (double f : fundamental_matrix) nrm += f * f;
+    degenerate_case = !ok || !(std::sqrt(nrm) >= 1e-5) || !std::isfinite(epipole_2[0]) ||
+                      !std::isfinite(epipole_2[1]);                             // :779
+    if (degenerate_case) {
+        printf("[Multi-H] Degenerate case, the fundamental matrix cannot be estimated.\n");
+        return true;
+    }
+    return RefineData(mask);
+}
+
+// :807-838 on the GPU: Hartley-Sturm correction, affine consistency filter, optimal affinity (the point-only route: the
+// correction alone, mh_refine_points); what is kept replaces the correspondences here and on the engine.
+bool MultiH::RefineData(const std::vector<unsigned char>& mask)
+{
+    const int N = static_cast<int>(src_points.size());
+    const bool points_only = plan.points_only;
+    double e1[2];
+    std::vector<unsigned char> keep(N, 0);
+    const int stride = points_only ? 4 : 8;
+    std::vector<double> refined(stride * (size_t)N);
+    if (!Check(mh_epipoles(engine, fundamental_matrix, e1, epipole_2), "mh_epipoles"))
+        return false;
+    if (points_only ? !Check(mh_refine_points(engine, fundamental_matrix, e1, epipole_2, mask.data(), keep.data(), refined.data()),
+                             "mh_refine_points")
+                    : !Check(mh_refine_correspondences(engine, fundamental_matrix, e1, epipole_2, mask.data(), keep.data(),
+                                                       refined.data()),
+                             "mh_refine_correspondences"))
+        return false;
+    std::vector<unsigned char> reason(N, 0);
+    if (!Check(mh_get_refine_reasons(engine, reason.data(), N), "mh_get_refine_reasons")) return false;
+    front_stages.in_ransac_mask = front_stages.triangulated = front_stages.affine_consistent = 0;
+    for (int i = 0; i < N; ++i) {
+        if (reason[i] != MH_REFINE_NOT_IN_MASK) ++front_stages.in_ransac_mask;
+        if (reason[i] == MH_REFINE_KEPT || reason[i] == MH_REFINE_AFFINE_TEST) ++front_stages.triangulated;
+        if (reason[i] == MH_REFINE_KEPT) ++front_stages.affine_consistent;
+    }
+    std::vector<cv::Point2d> s2, d2;
+    std::vector<cv::Mat> a2;
+    for (int i = 0; i < N; ++i)
+        if (keep[i]) {
+            const double* r = &refined[stride * (size_t)i];
+            s2.push_back(cv::Point2d(r[0], r[1]));
+            d2.push_back(cv::Point2d(r[2], r[3]));
+            if (!points_only) a2.push_back(OwnedMat(2, 2, r + 4));
+        }
+    printf("[Multi-H] %d points kept from the initial %d after filtering.\n", (int)s2.size(), N);   // :840
+    if (log_to_console)
+        printf("[Multi-H]   stages: %d in the RANSAC mask at %.2f px, %d after OptimalTriangulation, %d after distanceError <= 1\n",
+               front_stages.in_ransac_mask, threshold_fundamental_matrix, front_stages.triangulated, front_stages.affine_consistent);
+    if (s2.size() < 8) {
+        degenerate_case = true;
+        printf("[Multi-H] Degenerate case, not enough points remained.\n");                         // :845
+        return true;
+    }
+    src_points.swap(s2); dst_points.swap(d2); affinities.swap(a2);
+    return UploadCorrespondences(src_points, dst_points, affinities);
+}
+
+// The proposal sampler: its three arguments are checked here, once; then the local sampler's table, once, on the
+// correspondences the proposer samples (the refined ones); then the HAF proposals' neighbour table.
+bool MultiH::BuildProposalTables(const StageClock& stage)
+{
+    const bool haf = plan.initial_source == PROPOSAL_SOURCE_HAF;
     if (proposal_sampler != PROPOSAL_UNIFORM && proposal_sampler != PROPOSAL_LOCAL) {
         std::cerr << "Error: unknown proposal sampler " << proposal_sampler << " (PROPOSAL_UNIFORM or PROPOSAL_LOCAL)\n";
         return false;
     }
-    proposal_local_run = proposal_sampler == PROPOSAL_LOCAL && init_mode != INIT_STABLE_SETS;
-    if (proposal_local_run) {
+    plan.proposal_local = proposal_sampler == PROPOSAL_LOCAL && init_mode != INIT_STABLE_SETS;
+    if (plan.proposal_local) {
         if (proposal_sampler_k < 3 || proposal_sampler_k > 32) {
             std::cerr << "Error: SetProposalSampler: k = " << proposal_sampler_k << " is outside [3, 32]\n";
             return false;
@@ -690,7 +652,7 @@ bool MultiH::Run(bool points_only)
             std::cerr << "Error: SetProposalSampler: uniform_per_16 = " << proposal_uniform_per_16 << " is outside [0, 16]\n";
             return false;
         }
-        if (!mh_set_sampler || !mh_build_sample_neighbours) {
+        if (!caps.set_sampler || !caps.sample_neighbours) {
             std::cerr << "Error: the engine library has no local proposal sampler (mh_set_sampler, mh_build_sample_neighbours)\n";
             return false;
         }
@@ -702,100 +664,102 @@ bool MultiH::Run(bool points_only)
         }
         if (!Check(mh_build_sample_neighbours(engine, k), "mh_build_sample_neighbours")) return false;
         stage("sampling table");
-        if (proposal_haf_run && proposal_haf_members > k) {
+        if (haf && proposal_haf_members > k) {
             std::cerr << "Error: SetProposalSource: members = " << proposal_haf_members << " exceeds k = " << k << " of the local sampler's table\n";
             return false;
         }
     }
     // The HAF proposals' neighbour table: the sampler's when there is one, else built here, once, with k = members.
-    haf_members_run = proposal_haf_run ? proposal_haf_members : 0;
-    if (proposal_haf_run && haf_members_run > 0 && !proposal_local_run) {
-        if (!mh_build_sample_neighbours) {
+    plan.haf_members = haf ? proposal_haf_members : 0;
+    if (haf && plan.haf_members > 0 && !plan.proposal_local) {
+        if (!caps.sample_neighbours) {
             std::cerr << "Error: the engine library has no neighbour table for the HAF proposals (mh_build_sample_neighbours)\n";
             return false;
         }
         const int points = static_cast<int>(src_points.size());          // (at least 8 here, so members stays >= 3)
-        if (haf_members_run > points - 1) {
-            haf_members_run = points - 1;
+        if (plan.haf_members > points - 1) {
+            plan.haf_members = points - 1;
             // (said whatever the verbosity, like the sampler's "k reduced": the caller's setting is not what runs)
-            printf("[Multi-H] HAF proposals: members reduced from %d to %d (%d correspondences)\n", proposal_haf_members, haf_members_run, points);
+            printf("[Multi-H] HAF proposals: members reduced from %d to %d (%d correspondences)\n", proposal_haf_members, plan.haf_members, points);
         }
-        if (!Check(mh_build_sample_neighbours(engine, haf_members_run), "mh_build_sample_neighbours")) return false;
+        if (!Check(mh_build_sample_neighbours(engine, plan.haf_members), "mh_build_sample_neighbours")) return false;
         stage("HAF neighbour table");
     }
+    return true;
+}
 
+bool MultiH::InitialModels()
+{
     if (!initial_homographies.empty()) {
         for (const cv::Mat& h : initial_homographies) cluster_homographies.push_back(h.clone());
-    } else if (init_mode == INIT_STABLE_SETS) {
-        auto t0 = std::chrono::system_clock::now();
-        if (!EstablishStablePointSets()) return false;
-        std::chrono::duration<double> el = std::chrono::system_clock::now() - t0;
-        printf("[Multi-H] Stable cluster estimation time = %f secs\n", el.count());          // :74
-    } else if (!ProposeInitialModels()) {
-        return false;
+        return true;
     }
+    if (init_mode != INIT_STABLE_SETS) return ProposeInitialModels();
+    auto t0 = std::chrono::system_clock::now();
+    if (!EstablishStablePointSets()) return false;
+    std::chrono::duration<double> el = std::chrono::system_clock::now() - t0;
+    printf("[Multi-H] Stable cluster estimation time = %f secs\n", el.count());          // :74
+    return true;
+}
 
-    stage("initial models");
-    ClusterMergingAndLabeling();
-    stage("neighbourhood + alternation");
-
-    if (cluster_homographies.size() > 1 && run_compatibility_check && compat_fit == COMPAT_FIT_DLT) {
-        const int before = static_cast<int>(cluster_homographies.size());
-        auto t0 = std::chrono::system_clock::now();
-        post_filter_failed = false;
+bool MultiH::PostFilter()
+{
+    if (cluster_homographies.size() <= 1 || !run_compatibility_check) return true;
+    const int before = static_cast<int>(cluster_homographies.size());
+    auto t0 = std::chrono::system_clock::now();
+    post_filter_failed = false;
+    if (compat_fit == COMPAT_FIT_DLT) {
         HomographyCompatibilityCheckDlt();
         if (post_filter_failed) return false;                                // the engine refused: no host fallback
         std::chrono::duration<double> el = std::chrono::system_clock::now() - t0;
         printf("[Multi-H] Compatibility check (4-point trials) time = %f secs (%d clusters removed from %d)\n", el.count(),
                before - (int)cluster_homographies.size(), before);
-    } else if (cluster_homographies.size() > 1 && run_compatibility_check && epipolar_free) {
+    } else if (epipolar_free) {
         printf("[Multi-H] Epipolar-free route: the compatibility check is skipped (its trials are 3-point fits with F).\n");
-    } else if (cluster_homographies.size() > 1 && run_compatibility_check) {        // :78-86
-        const int before = static_cast<int>(cluster_homographies.size());
-        auto t0 = std::chrono::system_clock::now();
-        post_filter_failed = false;
+    } else {                                                                 // :78-86
         HomographyCompatibilityCheck();
         if (post_filter_failed) return false;                                // the engine refused: no host fallback
         std::chrono::duration<double> el = std::chrono::system_clock::now() - t0;
         printf("[Multi-H] Compatibility check time = %f secs (%d clusters removed from %d)\n", el.count(),
                before - (int)cluster_homographies.size(), before);
     }
+    return true;
+}
 
-    if (cluster_homographies.size() <= 1) {                                  // :88-94
+// The one-cluster exit (:88-94), or every cluster's homography refitted (reweighted rounds, then the polish) over its
+// labelled (refined) correspondences: the engine still holds them.
+bool MultiH::Finish()
+{
+    if (cluster_homographies.size() <= 1) {
         labeling.clear();
         labeling.resize(src_points.size(), -1);
         cluster_homographies.resize(0);
         HandleDegenerateCase();
-    } else if (model_reweight > 0 || model_reweight_auto > 0 || model_polish > 0) {
-        // every cluster's homography refitted (reweighted rounds, then the polish) over its labelled (refined) correspondences:
-        // the engine still holds them
-        const int nh = static_cast<int>(cluster_homographies.size());
-        if (labeling.size() != src_points.size()) {
-            std::cerr << "Error: model refit: " << labeling.size() << " labels for " << src_points.size() << " correspondences\n";
-            return false;
-        }
-        std::vector<double> H(9 * (size_t)nh);
-        for (int i = 0; i < nh; ++i) {
-            const double* p = reinterpret_cast<const double*>(cluster_homographies[i].data);
-            for (int k = 0; k < 9; ++k) H[9 * (size_t)i + k] = p[k];
-        }
-        if (model_reweight > 0) {
-            const double px = model_reweight_scale > 0.0 ? model_reweight_scale : threshold_homography;
-            if (!Check(mh_reweight_homographies(engine, labeling.data(), H.data(), nh, px * px, model_reweight, H.data(), nullptr, nullptr),
-                       "mh_reweight_homographies"))
-                return false;
-        }
-        if (model_reweight_auto > 0 &&
-            !Check(mh_reweight_homographies_auto(engine, labeling.data(), H.data(), nh, 1, 2, AutoKappa2(model_reweight_kappa), DBL_MIN,
-                                                 AutoScaleMax(), model_reweight_auto, H.data(), nullptr, nullptr, nullptr),
-                   "mh_reweight_homographies_auto"))
-            return false;
-        if (model_polish > 0 &&
-            !Check(mh_polish_homographies(engine, labeling.data(), H.data(), nh, model_polish, H.data(), nullptr, nullptr),
-                   "mh_polish_homographies"))
-            return false;
-        for (int i = 0; i < nh; ++i) cluster_homographies[i] = MatFrom9(&H[9 * (size_t)i]);
+        return true;
     }
+    if (model_reweight <= 0 && model_reweight_auto <= 0 && model_polish <= 0) return true;
+    const int nh = static_cast<int>(cluster_homographies.size());
+    if (labeling.size() != src_points.size()) {
+        std::cerr << "Error: model refit: " << labeling.size() << " labels for " << src_points.size() << " correspondences\n";
+        return false;
+    }
+    std::vector<double> H = FlatModels();
+    if (model_reweight > 0) {
+        const double px = model_reweight_scale > 0.0 ? model_reweight_scale : threshold_homography;
+        if (!Check(mh_reweight_homographies(engine, labeling.data(), H.data(), nh, px * px, model_reweight, H.data(), nullptr, nullptr),
+                   "mh_reweight_homographies"))
+            return false;
+    }
+    if (model_reweight_auto > 0 &&
+        !Check(mh_reweight_homographies_auto(engine, labeling.data(), H.data(), nh, 1, 2, AutoKappa2(model_reweight_kappa), DBL_MIN,
+                                             AutoScaleMax(), model_reweight_auto, H.data(), nullptr, nullptr, nullptr),
+               "mh_reweight_homographies_auto"))
+        return false;
+    if (model_polish > 0 &&
+        !Check(mh_polish_homographies(engine, labeling.data(), H.data(), nh, model_polish, H.data(), nullptr, nullptr),
+               "mh_polish_homographies"))
+        return false;
+    for (int i = 0; i < nh; ++i) cluster_homographies[i] = MatFrom9(&H[9 * (size_t)i]);
     return true;
 }
 
@@ -811,15 +775,8 @@ void MultiH::HomographyCompatibilityCheck()
     const int N = static_cast<int>(src_points.size());
     const int nh = static_cast<int>(cluster_homographies.size());
     if (nh == 0 || (int)labeling.size() != N) return;
-    std::vector<double> s(2 * (size_t)N), d(2 * (size_t)N), H(9 * (size_t)nh);
-    for (int i = 0; i < N; ++i) {
-        s[2 * i] = src_points[i].x; s[2 * i + 1] = src_points[i].y;
-        d[2 * i] = dst_points[i].x; d[2 * i + 1] = dst_points[i].y;
-    }
-    for (int i = 0; i < nh; ++i) {
-        const double* p = reinterpret_cast<const double*>(cluster_homographies[i].data);
-        for (int k = 0; k < 9; ++k) H[9 * (size_t)i + k] = p[k];
-    }
+    const PackedPoints xy = PackPoints(src_points, dst_points);
+    std::vector<double> H = FlatModels();
     // the trials' 3-point fits (r06) and their order statistics come from the engine (csrc/compat.hip); the replay of the draws
     // and the reference's stale-buffer bookkeeping are host work (merge_step.cpp)
     multih::CompatStatsFn on_engine;
@@ -831,7 +788,7 @@ void MultiH::HomographyCompatibilityCheck()
             return Check(mh_compat_trial_stats(engine, pts, begin, clusters, tri, Ht, ok, trials, out), "mh_compat_trial_stats");
         };
     bool failed = false;
-    const int kept = multih::CompatibilityCheck(s.data(), d.data(), N, labeling.data(), H.data(), nh,
+    const int kept = multih::CompatibilityCheck(xy.s.data(), xy.d.data(), N, labeling.data(), H.data(), nh,
                                                 fundamental_matrix, sqr_threshold_homography,
                                                 minimum_inlier_number, proposal_seed ^ 0xc0117a7ull, nullptr,
                                                 engine ? &on_engine : nullptr, &failed, engine != nullptr);
@@ -845,15 +802,8 @@ void MultiH::HomographyCompatibilityCheckDlt()
     const int N = static_cast<int>(src_points.size());
     const int nh = static_cast<int>(cluster_homographies.size());
     if (nh == 0 || (int)labeling.size() != N) return;
-    std::vector<double> s(2 * (size_t)N), d(2 * (size_t)N), H(9 * (size_t)nh);
-    for (int i = 0; i < N; ++i) {
-        s[2 * i] = src_points[i].x; s[2 * i + 1] = src_points[i].y;
-        d[2 * i] = dst_points[i].x; d[2 * i + 1] = dst_points[i].y;
-    }
-    for (int i = 0; i < nh; ++i) {
-        const double* p = reinterpret_cast<const double*>(cluster_homographies[i].data);
-        for (int k = 0; k < 9; ++k) H[9 * (size_t)i + k] = p[k];
-    }
+    const PackedPoints xy = PackPoints(src_points, dst_points);
+    std::vector<double> H = FlatModels();
     const multih::CompatDltFn on_engine = [this](const double* pts, const int* begin, int clusters, uint64_t seed, int trials,
                                                  double* medians) {
         return Check(mh_compat_dlt_medians(engine, pts, begin, clusters, seed, 0, trials, medians, nullptr, nullptr, nullptr),
@@ -861,7 +811,7 @@ void MultiH::HomographyCompatibilityCheckDlt()
     };
     const double scale = compat_limit_scale > 0.0 ? compat_limit_scale : COMPAT_DLT_LIMIT_SCALE;
     bool failed = false;
-    const int kept = multih::CompatibilityCheckDlt(s.data(), d.data(), N, labeling.data(), H.data(), nh,
+    const int kept = multih::CompatibilityCheckDlt(xy.s.data(), xy.d.data(), N, labeling.data(), H.data(), nh,
                                                    scale * sqr_threshold_homography, minimum_inlier_number,
                                                    proposal_seed ^ 0xc0117a7ull, compat_trials, nullptr, &on_engine, &failed);
     if (failed) { post_filter_failed = true; return; }
@@ -906,15 +856,20 @@ void MultiH::DrawClusters(cv::Mat& img1, cv::Mat& img2, int size)
     }
 }
 
+std::vector<double> MultiH::FlatModels() const
+{
+    std::vector<double> H(9 * cluster_homographies.size());
+    for (size_t i = 0; i < cluster_homographies.size(); ++i) {
+        const double* p = reinterpret_cast<const double*>(cluster_homographies[i].data);
+        for (int k = 0; k < 9; ++k) H[9 * i + k] = p[k];
+    }
+    return H;
+}
+
 bool MultiH::UploadModels()
 {
-    const int nh = static_cast<int>(cluster_homographies.size());
-    std::vector<double> H(9 * (size_t)nh);
-    for (int i = 0; i < nh; ++i) {
-        const double* p = reinterpret_cast<const double*>(cluster_homographies[i].data);
-        for (int k = 0; k < 9; ++k) H[9 * (size_t)i + k] = p[k];
-    }
-    return Check(mh_set_models(engine, H.data(), nh), "mh_set_models");
+    const std::vector<double> H = FlatModels();
+    return Check(mh_set_models(engine, H.data(), static_cast<int>(cluster_homographies.size())), "mh_set_models");
 }
 
 bool MultiH::DownloadModels(int count)
@@ -955,13 +910,10 @@ bool MultiH::EstablishStablePointSets()
     for (int i = 0; i < N; ++i) if (assign[i] >= 0) members[assign[i]].push_back(i);
     {
         // one 3-point fit with LM per cluster of at least three points (:664-688), on the host's cores (r06), taken in cluster order
-        std::vector<double> sxy(2 * (size_t)N), dxy(2 * (size_t)N), Hc;
+        const PackedPoints xy = PackPoints(src_points, dst_points);
+        std::vector<double> Hc;
         std::vector<unsigned char> okc;
-        for (int i = 0; i < N; ++i) {
-            sxy[2 * (size_t)i] = src_points[i].x; sxy[2 * (size_t)i + 1] = src_points[i].y;
-            dxy[2 * (size_t)i] = dst_points[i].x; dxy[2 * (size_t)i + 1] = dst_points[i].y;
-        }
-        multih::Homography3PTClusters(sxy.data(), dxy.data(), members, fundamental_matrix, Hc, okc);
+        multih::Homography3PTClusters(xy.s.data(), xy.d.data(), members, fundamental_matrix, Hc, okc);
         for (int c = 0; c < k; ++c)
             if (okc[c]) cluster_homographies.push_back(MatFrom9(&Hc[9 * (size_t)c]));
     }
@@ -980,21 +932,19 @@ bool MultiH::EstablishStablePointSets()
 bool MultiH::ProposeInitialModels()
 {
     std::vector<unsigned char> mask(src_points.size(), 1);
-    if (proposal_haf_run) {
+    if (plan.initial_source == PROPOSAL_SOURCE_HAF) {
         // one hypothesis per stride-th refined correspondence: counters 0 .. M - 1, anchors c * stride
         const int M = (static_cast<int>(src_points.size()) + proposal_haf_stride - 1) / proposal_haf_stride;
         if (log_to_console || std::getenv("MULTIH_TIMING") != nullptr)      // (part of the stage log too)
-            printf("[Multi-H] HAF proposals: %d hypotheses (members %d, stride %d); SetProposal's count of %d is ignored\n", M, haf_members_run,
+            printf("[Multi-H] HAF proposals: %d hypotheses (members %d, stride %d); SetProposal's count of %d is ignored\n", M, plan.haf_members,
                    proposal_haf_stride, proposal_hypotheses);
-        haf_batch_now = true;
-        const bool ok = ProposeModels(proposal_seed, 0, M, proposal_max_models, mask);
-        haf_batch_now = false;
+        const bool ok = ProposeModels(PROPOSAL_SOURCE_HAF, proposal_seed, 0, M, proposal_max_models, mask);
         if (ok && log_to_console)
             printf("[Multi-H] Proposed %d models from %d HAF hypotheses\n", (int)cluster_homographies.size(), M);
         return ok;
     }
-    const bool ok = ProposeModels(proposal_seed, 0, proposal_hypotheses, proposal_max_models, mask);
-    if (ok && proposal_3pt_run && (log_to_console || std::getenv("MULTIH_TIMING") != nullptr))      // (part of the stage log too)
+    const bool ok = ProposeModels(plan.initial_source, proposal_seed, 0, proposal_hypotheses, proposal_max_models, mask);
+    if (ok && plan.initial_source == PROPOSAL_SOURCE_3PT && (log_to_console || std::getenv("MULTIH_TIMING") != nullptr))      // (part of the stage log too)
         printf("[Multi-H] Proposed %d models from %d 3PT hypotheses\n", (int)cluster_homographies.size(), proposal_hypotheses);
     else if (ok && log_to_console)
         printf("[Multi-H] Proposed %d models from %d DLT hypotheses\n", (int)cluster_homographies.size(),
@@ -1005,7 +955,7 @@ bool MultiH::ProposeInitialModels()
 // The engine's sampler for the coming batch.  An engine library without the entry point has the uniform sampler only.
 bool MultiH::ApplyProposalSampler(bool local)
 {
-    if (!mh_set_sampler) return !local;
+    if (!caps.set_sampler) return !local;
     return Check(mh_set_sampler(engine, local ? MH_SAMPLER_LOCAL : MH_SAMPLER_UNIFORM, local ? proposal_uniform_per_16 : 0), "mh_set_sampler");
 }
 
@@ -1015,18 +965,18 @@ bool MultiH::ApplyProposalSampler(bool local)
 // words.  Sharded (SetSharding): rank r owns counters [first + off_r, first + off_r + m_r); the ranks all-gather
 // their int32 score vectors and the H each offers through the caller's transport on DEVICE buffers, and the selection
 // order is the single-GPU one (highest score, lowest counter on ties), so world sizes 1..G give identical model lists.
-bool MultiH::ProposeModels(uint64_t seed, long long first, int M, int max_models, std::vector<unsigned char>& mask)
+bool MultiH::ProposeModels(int source, uint64_t seed, long long first, int M, int max_models, std::vector<unsigned char>& mask)
 {
     const int need = std::max(minimum_inlier_number, 8);
     if (M <= 0 || max_models <= 0) return true;
     const int W = std::max(shard_world, 1), base = M / W, rem = M % W;
     const int mine = base + (shard_rank < rem ? 1 : 0);
     const long long off = (long long)shard_rank * base + std::min(shard_rank, rem);
-    if (!ApplyProposalSampler(proposal_local_run)) return false;      // (sticky on the engine, and engines are reused)
-    if (haf_batch_now) {      // an empty shard too: mh_propose_haf(.., 0, ..) keeps the batch's record, which every rank's selection compares
-        if (!Check(mh_propose_haf(engine, first + off, mine, proposal_haf_stride, haf_members_run, sqr_threshold_homography), "mh_propose_haf"))
+    if (!ApplyProposalSampler(plan.proposal_local)) return false;      // (sticky on the engine, and engines are reused)
+    if (source == PROPOSAL_SOURCE_HAF) {      // an empty shard too: mh_propose_haf(.., 0, ..) keeps the batch's record, which every rank's selection compares
+        if (!Check(mh_propose_haf(engine, first + off, mine, proposal_haf_stride, plan.haf_members, sqr_threshold_homography), "mh_propose_haf"))
             return false;
-    } else if (proposal_3pt_run) {      // the initial and the iterative batches alike; an empty shard keeps the batch's record here too
+    } else if (source == PROPOSAL_SOURCE_3PT) {      // the initial and the iterative batches alike; an empty shard keeps the batch's record here too
         if (!Check(mh_propose_3pt(engine, seed, first + off, mine), "mh_propose_3pt")) return false;
     } else if (mine > 0) {
         if (!Check(mh_propose_dlt4(engine, seed, first + off, mine), "mh_propose_dlt4")) return false;
@@ -1069,13 +1019,11 @@ void MultiH::SetShardingStream(int rank, int world, StreamAllGatherFn fn, void* 
     shard_rank = rank; shard_world = world; shard_stream_allgather = fn; shard_ctx = ctx;      // world == 1: a one-rank communicator
 }
 
-void MultiH::ClusterMergingAndLabeling()
+// Neighbourhood (M/MultiH.cpp:233-253).  Given hits are used as they are; otherwise the engine builds them in the
+// same float32 (x1,y1,x2,y2) space (MultiH.h, SetNeighbourK / SetNeighbourRadius).
+bool MultiH::BuildNeighbourhood()
 {
-    auto start = std::chrono::system_clock::now();
     const int N = static_cast<int>(src_points.size());
-
-    // Neighbourhood (M/MultiH.cpp:233-253).  Given hits are used as they are; otherwise the engine builds them in the
-    // same float32 (x1,y1,x2,y2) space (MultiH.h, SetNeighbourK / SetNeighbourRadius).
     bool ok;
     if (!neighbours.empty()) {
         std::vector<int> rowptr(N + 1, 0), col;
@@ -1119,6 +1067,14 @@ void MultiH::ClusterMergingAndLabeling()
             if (ok && log_to_console) printf("[Multi-H] %lld neighbourhood hits within %.1f px\n", hits, neighbour_radius);
         }
     }
+    return ok;
+}
+
+void MultiH::ClusterMergingAndLabeling()
+{
+    auto start = std::chrono::system_clock::now();
+    const int N = static_cast<int>(src_points.size());
+    const bool ok = BuildNeighbourhood();
     std::chrono::duration<double> el = std::chrono::system_clock::now() - start;
     printf("[Multi-H] Adjacency-matrix calculation time = %f secs\n", el.count());      // :258
     if (!ok) { cluster_homographies.clear(); return; }
@@ -1151,7 +1107,7 @@ void MultiH::ClusterMergingAndLabeling()
             std::vector<unsigned char> mask(N);
             for (int i = 0; i < N; ++i) mask[i] = labeling[i] < 0 ? 1 : 0;
             const size_t before = cluster_homographies.size();
-            if (!ProposeModels(proposal_seed, (long long)iteration_number * iter_hypotheses + proposal_hypotheses,
+            if (!ProposeModels(plan.iterative_source, proposal_seed, (long long)iteration_number * iter_hypotheses + proposal_hypotheses,
                                iter_hypotheses, iter_max_new, mask))
                 break;
             if (cluster_homographies.size() != before) changed = true;
@@ -1218,13 +1174,9 @@ void MultiH::ClusterMergingAndLabeling()
 // Mode -> homography is GetHomography3PT with its LM refinement (:995-1055, multih::Homography3PT).
 // The N x modes scoring and the 3x3 scatter eigen test (:430-463) run on the GPU
 // (mh_inlier_moments).
-// MergingStep (M/MultiH.cpp:352-471) on a given engine: host candidates (merge_step.cpp MergeCandidates), then the N x
-// candidates scoring and the collinearity filter on the GPU (mh_inlier_moments; :430-463).  kept: the surviving
-// candidates, 9 doubles each.  Returns an MH_* status.  The correspondences must be resident in the engine; its model
-// set is replaced by the candidates.
-// F == nullptr: the epipolar-free route, whose candidate of a mode is its medoid (merge_step.cpp MergeCandidatesMedoid).
-static int MergingStepOnEngine(mh_engine* engine, const double* H, int nh, const double F[9], double thr_h, double straightness,
-                               uint64_t seed, std::vector<double>& kept, uint64_t* draws)
+// (multih_internal.h says what goes in and out)
+int multih::detail::MergingStepOnEngine(mh_engine* engine, const double* H, int nh, const double F[9], double thr_h, double straightness,
+                                        uint64_t seed, std::vector<double>& kept, uint64_t* draws)
 {
     kept.clear();
     std::vector<double> cand;
@@ -1244,33 +1196,13 @@ static int MergingStepOnEngine(mh_engine* engine, const double* H, int nh, const
     return MH_OK;
 }
 
-// test hook (tests/test_gpu_alternation.py): one MergingStep of the product on `engine`, to be compared bit for bit with
-// the oracle's mho_merging_step.  kept: capacity nh x 9; returns the number kept or a negative MH_* status.
-extern "C" __attribute__((visibility("default")))
-int mhh_merging_step(mh_engine* engine, const double* H, int nh, const double* F, double thr_h, double straightness,
-                     unsigned long long seed, double* kept_out, int* changed, unsigned long long* draws)
-{
-    std::vector<double> kept;
-    uint64_t d = 0;
-    const int rc = MergingStepOnEngine(engine, H, nh, F, thr_h, straightness, seed, kept, &d);
-    if (rc != MH_OK) return rc;
-    std::copy(kept.begin(), kept.end(), kept_out);
-    if (changed) *changed = (int)(kept.size() / 9) != nh;
-    if (draws) *draws = d;
-    return (int)(kept.size() / 9);
-}
-
 bool MultiH::MergingStep(bool& changed)
 {
     if (merge_mode == MERGE_ENERGY) return MergingStepEnergy(changed);
     const int nh = static_cast<int>(cluster_homographies.size());
     changed = false;
     if (nh == 0) return true;
-    std::vector<double> H(9 * (size_t)nh);
-    for (int i = 0; i < nh; ++i) {
-        const double* p = reinterpret_cast<const double*>(cluster_homographies[i].data);
-        for (int k = 0; k < 9; ++k) H[9 * (size_t)i + k] = p[k];
-    }
+    std::vector<double> H = FlatModels();
     std::vector<double> kept9;
     const int rc = MergingStepOnEngine(engine, H.data(), nh, epipolar_free ? nullptr : fundamental_matrix, threshold_homography, straightness_threshold,
                                        proposal_seed ^ 0x4d53u ^ (merge_rng_counter << 20), kept9, nullptr);
@@ -1291,11 +1223,7 @@ bool MultiH::MergingStepEnergy(bool& changed)
     const int N = static_cast<int>(labeling.size());
     changed = false;
     if (nh == 0) return true;
-    std::vector<double> H(9 * (size_t)nh);
-    for (int i = 0; i < nh; ++i) {
-        const double* p = reinterpret_cast<const double*>(cluster_homographies[i].data);
-        for (int k = 0; k < 9; ++k) H[9 * (size_t)i + k] = p[k];
-    }
+    std::vector<double> H = FlatModels();
     int count = nh;
     MergeLogRecord rec;
     const bool evaluate = labeling_is_current;
@@ -1313,16 +1241,16 @@ bool MultiH::MergingStepEnergy(bool& changed)
         if (!Check(mh_merge_deltas(engine, labeling.data(), pairs.data(), npairs, H_ab.data(), delta.data(), nullptr, status.data()),
                    "MergingStep (mh_merge_deltas)"))
             return false;
-        const std::vector<int> accepted = multih::SelectMergesWithLabelCost(pairs.data(), delta.data(), status.data(), npairs, nh, label_cost_beta);
+        const std::vector<int> accepted = multih::SelectMergesWithLabelCost(pairs.data(), delta.data(), status.data(), npairs, nh, plan.label_cost_beta);
         for (int k : accepted) rec.sum_delta += delta[k];
         rec.merges_accepted = static_cast<long long>(accepted.size());
         count = multih::ApplyMerges(pairs.data(), H_ab.data(), accepted, N, labeling.data(), H.data(), nh);
         if (count != nh && !Check(mh_set_models(engine, H.data(), count), "MergingStep (mh_set_models)")) return false;
         // the drop move, on the labeling and models the joins left: at most one label per step
-        if (label_cost_beta > 0 && count > 0) {
+        if (plan.label_cost_beta > 0 && count > 0) {
             DropLogRecord drop;
             drop.iteration = loop_iteration;
-            drop.beta = label_cost_beta;
+            drop.beta = plan.label_cost_beta;
             std::vector<char> in_use(count, 0);
             for (int j = 0; j < N; ++j)
                 if (labeling[j] >= 0 && labeling[j] < count) in_use[labeling[j]] = 1;
@@ -1343,7 +1271,7 @@ bool MultiH::MergingStepEnergy(bool& changed)
                                           alt.data()),
                            "MergingStep (mh_drop_deltas)"))
                     return false;
-                const int pick = multih::SelectDrop(cand.data(), d_delta.data(), d_status.data(), ncand, label_cost_beta);
+                const int pick = multih::SelectDrop(cand.data(), d_delta.data(), d_status.data(), ncand, plan.label_cost_beta);
                 if (pick >= 0) {
                     int to_outlier = 0;
                     drop.dropped = cand[pick];
@@ -1423,18 +1351,7 @@ void MultiH::HandleDegenerateCase()
     labeling.assign(N, -1);
     // The engine may still hold the FILTERED, refined correspondences (Process() re-uploads them after
     // GetFundamentalMatrixAndRefineData); the reference fits and labels the originals here (:725-739).
-    {
-        std::vector<double> s(2 * (size_t)N), d(2 * (size_t)N), a(4 * (size_t)N);
-        for (int i = 0; i < N; ++i) {
-            s[2 * i] = src_points_original[i].x; s[2 * i + 1] = src_points_original[i].y;
-            d[2 * i] = dst_points_original[i].x; d[2 * i + 1] = dst_points_original[i].y;
-            if (point_only_run) continue;                                      // (affinities_original is empty)
-            const cv::Mat& A = affinities_original[i];
-            a[4 * i] = A.at<double>(0, 0); a[4 * i + 1] = A.at<double>(0, 1);
-            a[4 * i + 2] = A.at<double>(1, 0); a[4 * i + 3] = A.at<double>(1, 1);
-        }
-        if (!Check(mh_set_correspondences(engine, s.data(), d.data(), point_only_run ? nullptr : a.data(), N), "mh_set_correspondences")) return;
-    }
+    if (!UploadCorrespondences(src_points_original, dst_points_original, affinities_original)) return;
     const int M = std::max(proposal_hypotheses, 1000);
     if (!ApplyProposalSampler(false)) return;          // this batch is uniform whatever SetProposalSampler says (the oracle's mho_handle_degenerate defines it)
     if (!Check(mh_propose_dlt4(engine, proposal_seed ^ 0xdeadull, 0, M), "mh_propose_dlt4")) return;
@@ -1476,321 +1393,4 @@ void MultiH::HandleDegenerateCase()
     if (!Check(mh_inliers_of_model(engine, (int)best, sqr_threshold_homography, 0, labeling.data()), "mh_inliers_of_model"))
         return;
     cluster_homographies.push_back(MatFrom9(&H[9 * (size_t)best]));
-}
-
-// Sharding for the next mhh_run_process call of this process (one process per GPU).
-static int g_shard_rank = 0, g_shard_world = 1;
-static MultiH::AllGatherFn g_shard_fn = nullptr;
-static MultiH::StreamAllGatherFn g_shard_stream_fn = nullptr;
-static void* g_shard_ctx = nullptr;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_sharding(int rank, int world, MultiH::AllGatherFn fn, void* ctx)
-{
-    g_shard_rank = rank; g_shard_world = world; g_shard_fn = fn; g_shard_stream_fn = nullptr; g_shard_ctx = ctx;
-}
-
-// Stream-ordered transport (RCCL: host/rccl_transport.cpp) for the next mhh_run_process calls; fn = NULL returns to
-// whatever mhh_set_sharding set.  world == 1 is allowed: the whole sharded protocol on a one-rank communicator.
-extern "C" __attribute__((visibility("default")))
-void mhh_set_sharding_stream(int rank, int world, MultiH::StreamAllGatherFn fn, void* ctx)
-{
-    g_shard_rank = rank; g_shard_world = world; g_shard_stream_fn = fn; g_shard_fn = nullptr; g_shard_ctx = ctx;
-}
-
-static int g_device = 0;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_device(int device) { g_device = device; }
-
-// Neighbourhood of the next mhh_run_process calls: radius > 0 selects the complete radius list, else k > 0 the k nearest
-// hits within 1 / locality; both 0: the class default (k = 16).
-static int g_knn = 0, g_post_filter = 1;
-static double g_radius = 0.0;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_post_filter(int on) { g_post_filter = on; }
-extern "C" __attribute__((visibility("default")))
-void mhh_set_neighbourhood(int knn_k, double radius) { g_knn = knn_k; g_radius = radius; }
-// MultiH::SetNeighbourApprox for the next mhh_run_process calls (trees <= 0 switches it off again)
-static int g_approx_trees = 0, g_approx_checks = 32;
-static unsigned long long g_approx_seed = 0;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_neighbourhood_approx(int trees, int checks, unsigned long long seed) { g_approx_trees = trees; g_approx_checks = checks; g_approx_seed = seed; }
-// bound on the hits of the complete radius list (MultiH::SetNeighbourRadius' max_hits); <= 0 restores the default
-static long long g_max_hits = 0;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_neighbour_max_hits(long long max_hits) { g_max_hits = max_hits; }
-// caller-supplied directed hit lists (MultiH::SetNeighbours) for the next mhh_run_process calls, CSR; n <= 0 clears them.
-// For tools/neighbourhood_sweep.py: which neighbourhood rule reproduces the reference's recorded barrsmith result.
-static std::vector<std::vector<int>> g_hits;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_neighbour_hits(const int* rowptr, const int* col, int n)
-{
-    g_hits.clear();
-    if (n <= 0 || !rowptr || !col) return;
-    g_hits.resize(n);
-    for (int i = 0; i < n; ++i) g_hits[i].assign(col + rowptr[i], col + rowptr[i + 1]);
-}
-// MultiH::SetProposalRefit for the next mhh_run_process calls (default 1)
-static int g_proposal_refit = 1;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_proposal_refit(int on) { g_proposal_refit = on; }
-// MultiH::SetProposalSampler for the next mhh_run_process calls (default: uniform)
-static int g_proposal_sampler = 0, g_proposal_sampler_k = 0, g_proposal_uniform_per_16 = 0;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_proposal_sampler(int mode, int k, int uniform_per_16)
-{
-    g_proposal_sampler = mode; g_proposal_sampler_k = k; g_proposal_uniform_per_16 = uniform_per_16;
-}
-// MultiH::SetProposalSource for the next mhh_run_process calls (default: DLT)
-static int g_proposal_source = 0, g_proposal_haf_members = 16, g_proposal_haf_stride = 1;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_proposal_source(int source, int members, int stride)
-{
-    g_proposal_source = source; g_proposal_haf_members = members; g_proposal_haf_stride = stride;
-}
-// schedule knobs (mh_set_tuning) for the engines of the next mhh_run_process calls; key < 0 clears the list
-static std::vector<std::pair<int, int>> g_tuning;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_engine_tuning(int key, int value) { if (key < 0) g_tuning.clear(); else g_tuning.emplace_back(key, value); }
-
-// LabelingSteps the last mhh_run_process ran (MultiH::GetLabelingStepsRun)
-static int g_labeling_steps = 0;
-extern "C" __attribute__((visibility("default")))
-int mhh_get_labeling_steps() { return g_labeling_steps; }
-// MultiH::SetFundamentalMetric for the next mhh_run_process calls (< 0: the class default), and the stage table of the last one
-static int g_fund_metric = -1;
-static int g_front_stages[4] = { 0, 0, 0, 0 };
-extern "C" __attribute__((visibility("default")))
-void mhh_set_fundamental_metric(int metric) { g_fund_metric = metric; }
-// MultiH::SetFundamentalEstimator for the next mhh_run_process and mhh_filter_correspondences calls (mode < 0: the class default)
-static int g_fund_estimator = -1, g_fund_max_samples = 1000;
-static double g_fund_confidence = 0.99;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_fundamental_estimator(int mode, int max_samples, double confidence)
-{
-    g_fund_estimator = mode; g_fund_max_samples = max_samples; g_fund_confidence = confidence;
-}
-// MultiH::SetMergeMode for the next mhh_run_process calls (< 0: the class default), and the merge log of the last one
-static int g_merge_mode = -1;
-static std::vector<MultiH::MergeLogRecord> g_merge_log;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_merge_mode(int mode) { g_merge_mode = mode; }
-// records_out: capacity x 9 long long (iteration, models before, pairs, merges accepted, models filtered, E_before, sum_delta,
-// E_start, E_expansion), nullable; returns the number of records of the last mhh_run_process
-extern "C" __attribute__((visibility("default")))
-int mhh_get_merge_log(long long* records_out, int capacity)
-{
-    static_assert(sizeof(MultiH::MergeLogRecord) == 9 * sizeof(long long), "a record travels as 9 long long");
-    for (int i = 0; records_out && i < capacity && i < (int)g_merge_log.size(); ++i)
-        std::memcpy(records_out + 9 * (size_t)i, &g_merge_log[i], sizeof(MultiH::MergeLogRecord));
-    return (int)g_merge_log.size();
-}
-// MultiH::SetLabelCost for the next mhh_run_process calls (the class default is 0; any value is handed on, so that a bad one
-// fails in Process()), and the drop log of the last one
-static double g_label_cost = 0.0;
-static std::vector<MultiH::DropLogRecord> g_drop_log;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_label_cost(double points) { g_label_cost = points; }
-// records_out: capacity x 9 long long (iteration, candidates, dropped label or -1, members, members to the outlier label, delta,
-// beta, E_before, E_after), nullable; returns the number of records of the last mhh_run_process
-extern "C" __attribute__((visibility("default")))
-int mhh_get_drop_log(long long* records_out, int capacity)
-{
-    static_assert(sizeof(MultiH::DropLogRecord) == 9 * sizeof(long long), "a record travels as 9 long long");
-    for (int i = 0; records_out && i < capacity && i < (int)g_drop_log.size(); ++i)
-        std::memcpy(records_out + 9 * (size_t)i, &g_drop_log[i], sizeof(MultiH::DropLogRecord));
-    return (int)g_drop_log.size();
-}
-// MultiH::SetDataTerm for the next mhh_run_process calls (< 0: the class default)
-static int g_data_term = -1;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_data_term(int term) { g_data_term = term; }
-// MultiH::SetResidual for the next mhh_run_process calls (< 0: the class default)
-static int g_residual = -1;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_residual(int residual) { g_residual = residual; }
-// MultiH::SetTailScore for the next mhh_run_process calls (< 0: the class default)
-static int g_tail_score = -1;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_tail_score(int score) { g_tail_score = score; }
-// MultiH::SetTailRefit for the next mhh_run_process calls (< 0: the class default)
-static int g_tail_refit = -1;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_tail_refit(int iterations) { g_tail_refit = iterations; }
-// MultiH::SetTailPolish and MultiH::SetModelPolish for the next mhh_run_process calls (< 0: the class default)
-static int g_tail_polish = -1, g_model_polish = -1;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_tail_polish(int iterations) { g_tail_polish = iterations; }
-extern "C" __attribute__((visibility("default")))
-void mhh_set_model_polish(int iterations) { g_model_polish = iterations; }
-// MultiH::SetModelReweight and MultiH::SetEstimatorReweight (scale: the class default, the homography threshold) for the next
-// mhh_run_process calls (< 0: the class default)
-static int g_model_reweight = -1, g_estimator_reweight = -1;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_model_reweight(int rounds) { g_model_reweight = rounds; }
-extern "C" __attribute__((visibility("default")))
-void mhh_set_estimator_reweight(int rounds) { g_estimator_reweight = rounds; }
-// MultiH::SetModelReweightAuto and MultiH::SetEstimatorReweightAuto (kappa: the class default) the same way
-static int g_model_reweight_auto = -1, g_estimator_reweight_auto = -1;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_model_reweight_auto(int rounds) { g_model_reweight_auto = rounds; }
-extern "C" __attribute__((visibility("default")))
-void mhh_set_estimator_reweight_auto(int rounds) { g_estimator_reweight_auto = rounds; }
-// MultiH::SetEstimator (-1: leave as is, the class default) and MultiH::SetEpipolarFree for the next mhh_run_process calls
-static int g_estimator = -1, g_epipolar_free = 0;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_estimator(int estimator) { g_estimator = estimator; }
-extern "C" __attribute__((visibility("default")))
-void mhh_set_epipolar_free(int on) { g_epipolar_free = on; }
-// MultiH::SetCompatibilityFit for mhh_run_process; the initial value (COMPAT_FIT_3PT, 501, 0) is the class's default
-static int g_compat_fit = 0, g_compat_trials = 501;
-static double g_compat_limit_scale = 0.0;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_compat_fit(int mode, int trials, double limit_scale) { g_compat_fit = mode; g_compat_trials = trials; g_compat_limit_scale = limit_scale; }
-// MultiH::SetSelectionScore for the next mhh_run_process calls (< 0: the class default)
-static int g_selection_score = -1;
-extern "C" __attribute__((visibility("default")))
-void mhh_set_selection_score(int score) { g_selection_score = score; }
-extern "C" __attribute__((visibility("default")))
-void mhh_get_front_stages(int out[4]) { for (int i = 0; i < 4; ++i) out[i] = g_front_stages[i]; }
-// multih::FilterCorrespondencesByEpipolarGeometry on plain arrays: mask (n flags) out; returns the number kept, -1 on failure
-extern "C" __attribute__((visibility("default")))
-int mhh_filter_correspondences(const double* src_xy, const double* dst_xy, int n, double threshold, unsigned long long seed,
-                               int hypotheses, int metric, int device, unsigned char* mask)
-{
-    std::vector<cv::Point2d> s(n), d(n);
-    std::vector<cv::Mat> a(n);
-    for (int i = 0; i < n; ++i) {
-        s[i] = cv::Point2d(src_xy[2 * i], src_xy[2 * i + 1]);
-        d[i] = cv::Point2d(dst_xy[2 * i], dst_xy[2 * i + 1]);
-    }
-    std::vector<unsigned char> m;
-    MultiH::FundEstimator est;
-    if (g_fund_estimator >= 0) { est.mode = g_fund_estimator; est.max_samples = g_fund_max_samples; est.confidence = g_fund_confidence; }
-    if (!multih::FilterCorrespondencesByEpipolarGeometry(s, d, a, threshold, seed, hypotheses, metric, device, &m, est)) return -1;
-    for (int i = 0; i < n; ++i) mask[i] = m[i];
-    return (int)s.size();
-}
-
-// multih::CompatibilityCheck with the trials' order statistics from an engine (mh_compat_trial_stats), as Process() runs
-// it, returning the per-cluster median-of-medians too; -1 if the engine fails.  For the GPU tests.
-static int g_compat_fits_on_engine = 1;           // mhh_compatibility_medians_on_engine: 1 = the fits on the device too (as Process() runs it since r06), 0 = on the host
-extern "C" __attribute__((visibility("default")))
-void mhh_set_compat_fits_on_engine(int on) { g_compat_fits_on_engine = on; }
-extern "C" __attribute__((visibility("default")))
-int mhh_compatibility_medians_on_engine(mh_engine* engine, const double* src_xy, const double* dst_xy, int n, int* labels, double* H,
-                                        int nh, const double* F, double sqr_thr, int min_inliers, unsigned long long seed,
-                                        double* medians)
-{
-    multih::CompatStatsFn fn = [engine, F](const double* pts, const int* begin, int clusters, const int* tri, const double* Ht,
-                                           const unsigned char* ok, int trials, double* out) {
-        if (!Ht) return mh_compat_trial_stats_fit(engine, pts, begin, clusters, tri, F, trials, out, nullptr, nullptr) == MH_OK;
-        return mh_compat_trial_stats(engine, pts, begin, clusters, tri, Ht, ok, trials, out) == MH_OK;
-    };
-    bool failed = false;
-    const int kept = multih::CompatibilityCheck(src_xy, dst_xy, n, labels, H, nh, F, sqr_thr, min_inliers, seed, medians, &fn, &failed,
-                                                g_compat_fits_on_engine != 0);
-    return failed ? -1 : kept;
-}
-
-// multih::CompatibilityCheckDlt with the statistics from an engine (mh_compat_dlt_medians), as Process() runs it under
-// COMPAT_FIT_DLT, returning the per-cluster medians too (NaN where a cluster got none); -1 if the engine fails.  For the GPU tests.
-extern "C" __attribute__((visibility("default")))
-int mhh_compatibility_dlt_on_engine(mh_engine* engine, const double* src_xy, const double* dst_xy, int n, int* labels, double* H,
-                                    int nh, double limit, int min_inliers, unsigned long long seed, int trials, double* medians)
-{
-    if (!mh_compat_dlt_medians) return -1;
-    const multih::CompatDltFn fn = [engine](const double* pts, const int* begin, int clusters, uint64_t sd, int tr, double* out) {
-        return mh_compat_dlt_medians(engine, pts, begin, clusters, sd, 0, tr, out, nullptr, nullptr, nullptr) == MH_OK;
-    };
-    bool failed = false;
-    const int kept = multih::CompatibilityCheckDlt(src_xy, dst_xy, n, labels, H, nh, limit, min_inliers, seed, trials, medians, &fn, &failed);
-    return failed ? -1 : kept;
-}
-
-// ---- C hook for the GPU-side integration test (ctypes; plain arrays in/out) ----------------
-extern "C" __attribute__((visibility("default")))
-int mhh_run_process(const double* src_xy, const double* dst_xy, const double* aff, int n,
-                    const double* F, const double* e2, double thr_F, double thr_H, double locality,
-                    double lambda, int min_inliers, unsigned long long seed, int hypotheses,
-                    int max_models, int fixed_iterations, const double* init_H, int n_init,
-                    int* labels_out, double* H_out, int max_H, int* iterations, double* energy,
-                    double* loop_seconds, int iter_hypotheses, int iter_max_new)
-{
-    std::vector<cv::Point2d> s(n), d(n);
-    std::vector<cv::Mat> a(n);
-    // r06: the affinities as NON-owning 2 x 2 headers over one copy of the caller's array (cv::Mat(rows, cols, type, data): the
-    // same with the real library) — 50 000 matrices that each own a 32-byte allocation cost 5 ms to build and to copy, a third
-    // of what this hook reported as "Process()" at configs[4].  The copy outlives the call below.
-    // aff == NULL: the point-only route, Process(src, dst)
-    std::vector<double> aff_copy;
-    if (aff) aff_copy.assign(aff, aff + 4 * (size_t)n);
-    for (int i = 0; i < n; ++i) {
-        s[i] = cv::Point2d(src_xy[2 * i], src_xy[2 * i + 1]);
-        d[i] = cv::Point2d(dst_xy[2 * i], dst_xy[2 * i + 1]);
-        if (aff) a[i] = cv::Mat(2, 2, CV_64F, aff_copy.data() + 4 * (size_t)i);
-    }
-    MultiH mh(thr_F, thr_H, locality, lambda, min_inliers);
-    if (F && e2) mh.SetEpipolarGeometry(F, e2);
-    mh.SetProposal(seed, hypotheses, max_models);
-    mh.SetFixedIterations(fixed_iterations);
-    mh.SetIterativeProposal(iter_hypotheses, iter_max_new < 0 ? 4 : iter_max_new);
-    if (g_shard_stream_fn) mh.SetShardingStream(g_shard_rank, g_shard_world, g_shard_stream_fn, g_shard_ctx);
-    else mh.SetSharding(g_shard_rank, g_shard_world, g_shard_fn, g_shard_ctx);
-    mh.SetDevice(g_device);
-    mh.SetCompatibilityCheck(g_post_filter != 0);
-    mh.SetProposalRefit(g_proposal_refit != 0);
-    if (g_proposal_sampler != 0) mh.SetProposalSampler(g_proposal_sampler, g_proposal_sampler_k, g_proposal_uniform_per_16);
-    if (g_proposal_source != 0) mh.SetProposalSource(g_proposal_source, g_proposal_haf_members, g_proposal_haf_stride);
-    if (g_fund_metric >= 0) mh.SetFundamentalMetric(g_fund_metric);
-    if (g_data_term >= 0) mh.SetDataTerm(g_data_term);
-    if (g_merge_mode >= 0) mh.SetMergeMode(g_merge_mode);
-    g_merge_log.clear();
-    if (g_label_cost != 0.0) mh.SetLabelCost(g_label_cost);
-    g_drop_log.clear();
-    if (g_residual >= 0) mh.SetResidual(g_residual);
-    if (g_tail_score >= 0) mh.SetTailScore(g_tail_score);
-    if (g_tail_refit >= 0) mh.SetTailRefit(g_tail_refit);
-    if (g_tail_polish >= 0) mh.SetTailPolish(g_tail_polish);
-    if (g_model_polish >= 0) mh.SetModelPolish(g_model_polish);
-    if (g_model_reweight >= 0) mh.SetModelReweight(g_model_reweight);
-    if (g_estimator_reweight >= 0) mh.SetEstimatorReweight(g_estimator_reweight);
-    if (g_model_reweight_auto >= 0) mh.SetModelReweightAuto(g_model_reweight_auto);
-    if (g_estimator_reweight_auto >= 0) mh.SetEstimatorReweightAuto(g_estimator_reweight_auto);
-    if (g_selection_score >= 0) mh.SetSelectionScore(g_selection_score);
-    if (g_estimator >= 0) mh.SetEstimator(g_estimator);
-    mh.SetEpipolarFree(g_epipolar_free != 0);
-    mh.SetCompatibilityFit(g_compat_fit, g_compat_trials, g_compat_limit_scale);
-    if (g_fund_estimator >= 0) mh.SetFundamentalEstimator(g_fund_estimator, g_fund_max_samples, g_fund_confidence);
-    for (const auto& kv : g_tuning) mh.SetEngineTuning(kv.first, kv.second);
-    if (g_radius > 0.0 && g_max_hits > 0) { mh.SetNeighbourRadius(g_radius, g_max_hits); if (g_knn > 0) mh.SetFallbackK(g_knn); }
-    else if (g_radius > 0.0) mh.SetNeighbourRadius(g_radius);
-    else if (g_knn > 0) mh.SetNeighbourK(g_knn);
-    if (g_approx_trees > 0) mh.SetNeighbourApprox(g_approx_trees, g_approx_checks, g_approx_seed);
-    if (!g_hits.empty() && (int)g_hits.size() == n) mh.SetNeighbours(g_hits);
-    if (iter_max_new < 0) mh.SetInitialisation(MultiH::INIT_STABLE_SETS);      // test hook: negative = reference-style init
-    if (init_H && n_init > 0) {
-        std::vector<cv::Mat> hs;
-        for (int i = 0; i < n_init; ++i) hs.push_back(MatFrom9(init_H + 9 * (size_t)i));
-        mh.SetInitialHomographies(hs);
-    }
-    if (aff ? !mh.Process(s, d, a) : !mh.Process(s, d)) return -1;
-    {
-        const MultiH::FrontStages st = mh.GetFrontStages();
-        g_front_stages[0] = st.input; g_front_stages[1] = st.in_ransac_mask; g_front_stages[2] = st.triangulated; g_front_stages[3] = st.affine_consistent;
-    }
-    std::vector<int> lab;
-    mh.GetLabels(lab);
-    for (size_t i = 0; i < lab.size() && i < (size_t)n; ++i) labels_out[i] = lab[i];
-    const int k = mh.GetClusterNumber();
-    for (int i = 1; i <= k && i <= max_H; ++i) {
-        cv::Mat h = mh.GetHomography(i);
-        for (int q = 0; q < 9; ++q) H_out[9 * (size_t)(i - 1) + q] = reinterpret_cast<double*>(h.data)[q];
-    }
-    if (iterations) *iterations = mh.GetIterationNumber();
-    if (energy) *energy = mh.GetEnergy();
-    if (loop_seconds) *loop_seconds = mh.GetLastLoopSeconds();
-    g_labeling_steps = mh.GetLabelingStepsRun();
-    g_merge_log = mh.GetMergeLog();
-    g_drop_log = mh.GetDropLog();
-    return k;
 }

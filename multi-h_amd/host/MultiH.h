@@ -18,6 +18,7 @@
 #pragma once
 
 #include <cstdint>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -349,6 +350,47 @@ public:
     void SetEngineTuning(int key, int value) { engine_tuning.emplace_back(key, value); }
     void SetVerbose(bool v) { log_to_console = v; }
     double GetLastLoopSeconds() const { return loop_seconds; }
+    // Which optional entry points the linked engine library has, one flag per mode that needs some (in brackets: the mh_*
+    // functions behind it).  An engine library from before a mode lacks its flag: PlanRun refuses the mode with a message.
+    struct EngineCaps {
+        bool point_only = false;                  // (mh_set_estimator, mh_refine_points)
+        bool fundamental_minimal = false;         // (mh_estimate_fundamental_minimal)
+        bool set_sampler = false;                 // (mh_set_sampler)
+        bool sample_neighbours = false;           // (mh_build_sample_neighbours)
+        bool data_term = false;                   // (mh_set_data_term)
+        bool residual_route = false;              // (mh_set_residual_mode, mh_set_residual_scope)
+        bool msac_scores = false;                 // (mh_score_msac, mh_select_best_msac)
+        bool get_model = false;                   // (mh_get_model)
+        bool refit = false;                       // (mh_refit_homography)
+        bool polish = false;                      // (mh_polish_homographies)
+        bool reweight = false;                    // (mh_reweight_homographies)
+        bool estimator_reweighting = false;       // (mh_set_estimator_reweighting)
+        bool reweight_auto = false;               // (mh_reweight_homographies_auto)
+        bool estimator_reweighting_auto = false;  // (mh_set_estimator_reweighting_auto)
+        bool select_greedy_msac = false;          // (mh_select_greedy_msac)
+        bool propose_haf = false;                 // (mh_propose_haf)
+        bool propose_3pt = false;                 // (mh_propose_3pt)
+        bool compat_dlt = false;                  // (mh_compat_dlt_medians)
+        bool energy_merge = false;                // (mh_merge_deltas, mh_labeling_energy)
+        bool drop_deltas = false;                 // (mh_drop_deltas)
+    };
+    // What one Process() call derives from the settings, made by PlanRun before anything touches an engine.
+    struct RunPlan {
+        bool points_only = false;                 // the point-only Process()
+        int est = 0;                              // the engine's re-estimator, MH_ESTIMATOR_*
+        // where the initial and the iterative batches of ProposeModels come from, PROPOSAL_SOURCE_*
+        int initial_source = PROPOSAL_SOURCE_DLT, iterative_source = PROPOSAL_SOURCE_DLT;
+        // known once the front half has said how many correspondences are left: the batches use the local sampler (its table
+        // is on the engine); the members of a HAF hypothesis (reduced where there are fewer correspondences)
+        bool proposal_local = false;
+        int haf_members = 0;
+        long long label_cost_beta = 0;            // SetLabelCost in energy units
+        int residual_mode = 0, residual_scope = 0;          // MH_RESIDUAL_*, MH_RESIDUAL_SCOPE_*
+        // the reweighted rounds of the loop's estimator: 0 unless est is the N-point DLT; c2 is the fixed rule's squared scale
+        int estimator_reweight_rounds = 0;
+        double estimator_reweight_c2 = 0.0;
+        bool estimator_reweight_auto = false;     // the rounds are self-scaled ones
+    };
 
 protected:
     std::vector<cv::Point2d> src_points_original, dst_points_original;   // M/MultiH.h:78
@@ -401,14 +443,10 @@ protected:
     double AutoScaleMax() const { return threshold_homography * threshold_homography * 81.0 / 16.0; }
     int selection_score = SELECTION_SCORE_COUNT;
     int proposal_sampler = PROPOSAL_UNIFORM, proposal_sampler_k = 32, proposal_uniform_per_16 = 4;
-    bool proposal_local_run = false;      // this Process() call proposes with the local sampler (its table is on the engine)
     bool ApplyProposalSampler(bool local);
     int proposal_source = PROPOSAL_SOURCE_DLT, proposal_haf_members = 16, proposal_haf_stride = 1;
-    bool proposal_haf_run = false;        // this Process() call proposes its initial batch with mh_propose_haf
-    int haf_members_run = 0;              // ... with this many members (reduced where there are fewer correspondences)
-    bool haf_batch_now = false;           // the batch ProposeModels is about to propose is the HAF one
-    bool proposal_3pt_run = false;        // this Process() call proposes its batches with mh_propose_3pt
-    bool point_only_run = false;                 // the last Process() was the point-only one
+    RunPlan plan;                         // of the last Process()
+    EngineCaps caps;                      // of the engine library that Process() ran against
     int fixed_iterations = 0;
     int iter_hypotheses = 0, iter_max_new = 4;
     int fundamental_hypotheses = 4000;
@@ -429,21 +467,36 @@ protected:
     StreamAllGatherFn shard_stream_allgather = nullptr;
     void* shard_ctx = nullptr;
 
+    // Process() with or without affinities, stage by stage: PlanRun, EnsureEngine, ConfigureEngine, UploadCorrespondences,
+    // FrontHalf, BuildProposalTables, InitialModels, ClusterMergingAndLabeling, PostFilter, Finish
+    bool Run(bool points_only);
+    bool PlanRun(bool points_only, const EngineCaps& have, RunPlan& out, std::string& error) const;
+    bool PlanFinishModes(const EngineCaps& have, RunPlan& out, std::string& error) const;      // PlanRun's second half
     bool EnsureEngine();
-    bool Run(bool points_only);           // Process() with or without affinities
+    bool ConfigureEngine(const RunPlan& p);                // the sticky settings of the engine, every one on every call
+    bool UploadCorrespondences(const std::vector<cv::Point2d>& src, const std::vector<cv::Point2d>& dst, const std::vector<cv::Mat>& aff);
+    struct StageClock;                                     // the "... done" lines under MULTIH_TIMING
+    bool FrontHalf();                                      // M/MultiH.cpp:770-848; may end in degenerate_case
+    bool RefineData(const std::vector<unsigned char>& mask);                                   // :807-838
+    bool BuildProposalTables(const StageClock& stage);
+    bool InitialModels();
+    bool PostFilter();                                     // :78-86
+    bool Finish();                                         // :88-94, or the final models' reweighted refit and polish
+    std::vector<double> FlatModels() const;                // cluster_homographies, 9 doubles each
     bool UploadModels();
     bool DownloadModels(int count);
     bool ProposeInitialModels();          // north_star propose: DLT batch + greedy selection
     bool EstablishStablePointSets();      // M/MultiH.cpp:604-694 (with ComputeLocalHomographies :696-717)
-    bool ProposeModels(uint64_t seed, long long first, int hypotheses, int max_models,
+    // `source`: what the batch is made of (PROPOSAL_SOURCE_*: RunPlan's initial_source or iterative_source)
+    bool ProposeModels(int source, uint64_t seed, long long first, int hypotheses, int max_models,
                        std::vector<unsigned char>& mask);
     void ClusterMergingAndLabeling();     // M/MultiH.cpp:224-312
+    bool BuildNeighbourhood();            // :233-253
     bool MergingStep(bool& changed);      // :352-471
     bool MergingStepEnergy(bool& changed);             // SetMergeMode(MERGE_ENERGY)
     int merge_mode = MERGE_MEAN_SHIFT;
     std::vector<MergeLogRecord> merge_log;
     double label_cost_points = 0.0;       // SetLabelCost
-    long long label_cost_beta = 0;        // ... in energy units, set by Run()
     std::vector<DropLogRecord> drop_log;
     bool labeling_is_current = false;     // a LabelingStep has run in this Process() and `labeling` is valid for cluster_homographies
     bool merge_log_open = false;          // the last record waits for its LabelingStep's energy

@@ -3,6 +3,7 @@ whose cv::Mat(rows, cols, type, void*) is a NON-owning header exactly like OpenC
 repeats ApplyMultiH's sequence (M/main.cpp:262-296, DrawClusters included) and a do-nothing stand-in for the
 engine library, and run under AddressSanitizer.  A Mat header left pointing into a dead buffer (the bug the
 round-1 review found at host/MultiH.cpp:163) is a heap-use-after-free here."""
+import importlib
 import os
 import shutil
 import subprocess
@@ -23,7 +24,7 @@ def _compile(tmp_path, sources, out, extra=()):
 
 def test_apply_multih_sequence_is_memory_clean_under_opencv_ownership_rules(tmp_path):
     srcs = [os.path.join(ROOT, "tests", "apply_multih_caller.cpp"), os.path.join(ROOT, "tests", "fake_engine.cpp"),
-            os.path.join(HOST, "MultiH.cpp"), os.path.join(HOST, "merge_step.cpp"), os.path.join(HOST, "approx_neighbours.cpp")]
+            *importlib.import_module("multi-h_amd.build").HOST_SOURCES]
     b = _compile(tmp_path, srcs, "caller")
     if b.returncode != 0 and ("cannot find" in b.stderr or "unrecognized" in b.stderr):
         pytest.skip("sanitizer runtime not installed")

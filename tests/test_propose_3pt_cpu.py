@@ -1,6 +1,7 @@
 """The 3-point proposer's twin (tests/propose_3pt_numpy.py) against the oracle, what a 3-point batch is worth to the selection
 beside the DLT batch from the same tuples, and what the built libraries must offer.  No GPU: the engine's batches are compared
 with this twin in tests/test_gpu_propose_3pt.py."""
+import importlib
 import os
 import re
 import shutil
@@ -39,7 +40,7 @@ def test_the_host_class_accepts_source_2_and_says_so_without_the_entry_point(tmp
     known source that fails with its own message — with affinities and point-only —, source 7 is unknown, and the default route
     gives the same clusters before and after."""
     srcs = [os.path.join(ROOT, "tests", "propose_3pt_caller.cpp"), os.path.join(ROOT, "tests", "fake_engine.cpp"),
-            os.path.join(HOST, "MultiH.cpp"), os.path.join(HOST, "merge_step.cpp"), os.path.join(HOST, "approx_neighbours.cpp")]
+            *importlib.import_module("multi-h_amd.build").HOST_SOURCES]
     exe = str(tmp_path / "caller")
     b = subprocess.run(["g++", "-std=c++17", "-O1", "-pthread", "-ffp-contract=off", "-I" + HOST, "-I" + os.path.join(ROOT, "include"),
                         *srcs, "-o", exe], capture_output=True, text=True, timeout=600)

@@ -1,6 +1,7 @@
 """The symmetric route (mh_set_residual_scope, MultiH::SetResidual) without a GPU: that the scenes the GPU tests use tell the
 two errors apart, what the built libraries must offer, and the host class over an engine library without the entry points.
 The engine's outputs are compared with the twin (tests/symmetric_route_numpy.py) in tests/test_gpu_symmetric_route.py."""
+import importlib
 import os
 import re
 import shutil
@@ -91,7 +92,7 @@ def test_the_host_class_over_an_engine_without_the_entry_points(tmp_path):
     references are weak), the forward route runs as before, RESIDUAL_SYMMETRIC fails with its message, an unknown value and
     the MSAC tail together with the symmetric error are refused, and the default route gives the same clusters afterwards."""
     srcs = [os.path.join(ROOT, "tests", "symmetric_route_caller.cpp"), os.path.join(ROOT, "tests", "fake_engine.cpp"),
-            os.path.join(HOST, "MultiH.cpp"), os.path.join(HOST, "merge_step.cpp"), os.path.join(HOST, "approx_neighbours.cpp")]
+            *importlib.import_module("multi-h_amd.build").HOST_SOURCES]
     exe = str(tmp_path / "caller")
     b = subprocess.run(["g++", "-std=c++17", "-O1", "-pthread", "-ffp-contract=off", "-I" + HOST, "-I" + os.path.join(ROOT, "include"),
                         *srcs, "-o", exe], capture_output=True, text=True, timeout=600)
