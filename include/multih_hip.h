@@ -96,8 +96,46 @@ MH_API int mh_build_neighbors_knn_radius(mh_engine* e, int k, double radius);
 MH_API int mh_build_neighbors_radius(mh_engine* e, double radius, long long max_hits, long long* hits_out);
 /* Copy the symmetric weighted graph the engine derived (rowptr n+1, col/w nnz).  Pass NULLs to
  * query nnz only.  The graph is built and kept on the device (csrc/graph.hip); the host copy is fetched by the
- * first call after a build. */
+ * first call after a build.  w receives the weights IN FORCE — what the labeling pays per arc under the rule of
+ * mh_set_smoothness_weights (the multiplicities under MH_SMOOTH_UNIFORM) —, read from the device after every change of the
+ * graph or of the rule. */
 MH_API int mh_get_sym_graph(mh_engine* e, int* rowptr, int* col, int* w, int* nnz);
+/* The hit multiplicities mult(p,q) = #[p->q] + #[q->p] of the same arcs (nnz ints, the order of mh_get_sym_graph's col),
+ * whatever rule is in force.  mult nullable.  MH_ERR_NOT_SET without a graph. */
+MH_API int mh_get_sym_multiplicity(mh_engine* e, int* mult /* nnz */);
+/* The weight of every arc (p,q) of the symmetric graph, i.e. what multiplies the Potts price round(100*lambda) of the pair
+ * in mh_expand, mh_labeling_step, mh_labeling_energy, mh_merge_deltas and mh_drop_deltas (they read the graph's w and its
+ * per-site totals and nothing else about an arc).
+ *   MH_SMOOTH_UNIFORM (0, default)   w_pq = mult(p,q): the reference's smoothnessEnergy.  rho and q_max are not looked at.
+ *   MH_SMOOTH_CAUCHY  (1)            w_pq = mult(p,q) * q, with
+ *     1. d  the float32 squared distance of the two sites in (x1,y1,x2,y2), in mh_build_neighbors_knn's arithmetic:
+ *           coordinates cast to float, dx = x1[p] - x1[q] (dy, dz, dw alike), d = ((dx*dx + dy*dy) + dz*dz) + dw*dw, every
+ *           operation rounded once, no fused multiply-add;
+ *     2. in double: r2 = rho*rho (once, on the host), t = r2 / (r2 + (double)d), qf = (double)q_max * t;
+ *     3. q  = qf >= 1.0 ? (int)round(qf) : 1   (C round(): halves away from zero; an infinite d gives t = 0 and a NaN d
+ *           fails the comparison: both give 1, and no NaN is ever converted to an int);
+ *     4. the product in int64.
+ *   So q == q_max at d == 0, q never rises with d, q >= 1 (no arc disappears, the reverse-arc index stays valid), the rule is
+ *   symmetric bit for bit (dx and -dx square alike), and q_max == 1 is the uniform graph.  (A rho so small that rho*rho
+ *   underflows to 0 gives q = 1 on every arc, d == 0 included: 0/0 is a NaN.)  This is PEARL's distance-weighted
+ *   smoothness with a Cauchy profile in place of exp(-d/rho^2): an exponential has no definition that a device and a CPU twin
+ *   share bit for bit, and is not offered.
+ * A near arc now costs q_max * round(100*lambda) where it cost round(100*lambda).  lambda scales BOTH terms of the energy
+ * (the data term by 100/lambda, the Potts price by 100*lambda), so lambda' = lambda / sqrt(q_max) keeps the short-range
+ * balance between them; the engine rescales nothing itself.
+ * q_max in [1, MH_SMOOTH_Q_MAX], rho finite and > 0; anything else, another rule, or a null engine: MH_ERR_INVALID, nothing
+ * changed.  MH_ERR_OVERFLOW when a product mult * q or a site's weight total leaves int32: the rule, the weights and the
+ * totals that were in force stay in force.
+ * Sticky per engine, like mh_set_data_term.  It applies at once to a resident graph (one kernel, csrc/graph.hip
+ * k_arc_weights, writing spare buffers that are swapped in on success; back to UNIFORM restores the multiplicities bit for
+ * bit, no rebuild) and to every graph that arrives later — mh_set_neighbors_csr and the three builders, on the device or
+ * through the host fallback for very long rows; a graph that arrives under CAUCHY and overflows is refused
+ * (MH_ERR_OVERFLOW) and the engine then holds no graph.  mh_set_correspondences drops the graph, not the setting.  Nothing
+ * else goes stale: the data cost does not depend on the weights. */
+#define MH_SMOOTH_UNIFORM 0
+#define MH_SMOOTH_CAUCHY 1
+#define MH_SMOOTH_Q_MAX 256
+MH_API int mh_set_smoothness_weights(mh_engine* e, int rule, double rho, int q_max);
 
 /* ---- epipolar front half --------------------------- */
 /* The reference estimates F inside Process() with cv::findFundamentalMat(RANSAC)

@@ -22,6 +22,7 @@ ESTIMATORS = {"haf": 0, "3pt": 1, "dlt": 2}      # MH_ESTIMATOR_HAF, MH_ESTIMATO
 SAMPLER_UNIFORM, SAMPLER_LOCAL = 0, 1  # MH_SAMPLER_UNIFORM, MH_SAMPLER_LOCAL
 RESIDUAL_SCOPES = {"score": 0, "route": 1}      # MH_RESIDUAL_SCOPE_SCORE, MH_RESIDUAL_SCOPE_ROUTE
 DATA_TERMS = {"reference": 0, "rising": 1}      # MH_DATA_TERM_REFERENCE, MH_DATA_TERM_RISING
+SMOOTH_RULES = {"uniform": 0, "cauchy": 1}      # MH_SMOOTH_UNIFORM, MH_SMOOTH_CAUCHY
 MERGE_OK, MERGE_EMPTY, MERGE_NO_FIT = 0, 1, 2   # MH_MERGE_*
 MERGE_NO_DELTA = 2**63 - 1                      # LLONG_MAX: the delta of a pair that is not OK
 DROP_OK, DROP_EMPTY = 0, 1                      # MH_DROP_*
@@ -33,7 +34,7 @@ K_DLT4, K_RESIDUAL, K_SCORE, K_DATACOST, K_EXPAND, K_REESTIMATE, K_COSTMATRIX = 
 SYMBOLS = [
     "mh_abi_version", "mh_last_error", "mh_device_count", "mh_create", "mh_destroy", "mh_set_params",
     "mh_set_stream", "mh_synchronize", "mh_set_correspondences", "mh_set_epipolar",
-    "mh_set_neighbors_csr", "mh_build_neighbors_knn", "mh_build_neighbors_knn_radius", "mh_build_neighbors_radius", "mh_get_sym_graph", "mh_set_fundamental_metric", "mh_propose_fund8",
+    "mh_set_neighbors_csr", "mh_build_neighbors_knn", "mh_build_neighbors_knn_radius", "mh_build_neighbors_radius", "mh_get_sym_graph", "mh_get_sym_multiplicity", "mh_set_smoothness_weights", "mh_set_fundamental_metric", "mh_propose_fund8",
     "mh_get_fund_hypotheses", "mh_score_sampson", "mh_refit_fundamental", "mh_estimate_fundamental", "mh_propose_fund7", "mh_get_fund7_samples", "mh_estimate_fundamental_minimal", "mh_epipoles", "mh_refine_correspondences", "mh_get_refine_reasons", "mh_refine_points",
     "mh_local_homographies", "mh_mean_shift", "mh_propose_dlt4",
     "mh_set_models", "mh_get_models", "mh_get_model_count", "mh_get_model", "mh_get_samples", "mh_set_sampler", "mh_build_sample_neighbours", "mh_get_sample_neighbours", "mh_propose_haf", "mh_get_haf_support", "mh_propose_3pt", "mh_set_residual_mode", "mh_set_residual_scope", "mh_score", "mh_score_msac", "mh_select_best_msac",
@@ -167,6 +168,24 @@ class Engine:
         w = np.empty(nnz.value, dtype=np.int32)
         self._check(self.lib.mh_get_sym_graph(self._h, _p(rp, C.c_int), _p(col, C.c_int), _p(w, C.c_int), None))
         return rp, col, w
+
+    def sym_multiplicity(self):
+        """mh_get_sym_multiplicity: the hit multiplicities of get_sym_graph()'s arcs, whatever smoothness rule is in force."""
+        nnz = C.c_int(0)
+        self._check(self.lib.mh_get_sym_graph(self._h, None, None, None, C.byref(nnz)))
+        mult = np.empty(nnz.value, dtype=np.int32)
+        self._check(self.lib.mh_get_sym_multiplicity(self._h, _p(mult, C.c_int)))
+        return mult
+
+    def set_smoothness_weights(self, rule, rho: float = 0.0, q_max: int = 1):
+        """mh_set_smoothness_weights: "uniform" (default; w = multiplicity) or "cauchy" (w = multiplicity x
+        max(1, round(q_max rho^2 / (rho^2 + d))), d the float32 squared distance of the arc's sites); sticky, applies to the
+        resident graph at once and to every later one."""
+        if isinstance(rule, str):
+            if rule not in SMOOTH_RULES:
+                raise ValueError(f"unknown smoothness rule {rule!r}")
+            rule = SMOOTH_RULES[rule]
+        self._check(self.lib.mh_set_smoothness_weights(self._h, int(rule), C.c_double(rho), int(q_max)))
 
     # -- epipolar front half ---------------------------------------------------
     def propose_fund8(self, seed: int, first: int, m: int):

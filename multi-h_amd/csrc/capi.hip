@@ -180,13 +180,13 @@ int build_sym_graph(mh_engine* e, const int* rowptr, const int* col, int n)
     for (int i = 0; i < n; ++i) e->g_rowptr[i + 1] += e->g_rowptr[i];
     const int nnz = e->g_rowptr[n];
     e->g_col.resize(nnz);
-    e->g_w.resize(nnz);
+    e->g_mult.resize(nnz);
     e->g_rev.assign(nnz, -1);
     host_parallel_for(n, [&](int b, int en) {
         for (int i = b; i < en; ++i) {
             const int len = e->g_rowptr[i + 1] - e->g_rowptr[i];
             std::copy(raw.data() + start[i], raw.data() + start[i] + len, e->g_col.data() + e->g_rowptr[i]);
-            std::copy(mult.data() + start[i], mult.data() + start[i] + len, e->g_w.data() + e->g_rowptr[i]);
+            std::copy(mult.data() + start[i], mult.data() + start[i] + len, e->g_mult.data() + e->g_rowptr[i]);
         }
     });
     host_parallel_for(n, [&](int b, int en) {
@@ -225,12 +225,38 @@ static int upload_order(mh_engine* e)
     return MH_OK;
 }
 
-// per-site weight totals of the graph that is on the device (d_rowptr, d_w)
-static int upload_wsum(mh_engine* e)
+// The weights of the graph that is on the device (d_rowptr, d_col, d_mult; nnz arcs) under a smoothness rule, and their
+// per-site totals.  UNIFORM: the weights are the multiplicities, the totals k_row_wsum's (enqueued; the caller waits).
+// CAUCHY: k_arc_weights writes the spare buffers, the host reads its overflow word, and only then are they swapped in — a
+// refused call (MH_ERR_OVERFLOW) leaves d_wq, d_wsum and the rule as they were.  The rule is committed here.
+static int apply_smoothness(mh_engine* e, int nnz, int rule, double rho, int q_max)
 {
-    HIPCHK(e->d_wsum.reserve(e->n));
-    HIPCHK(launch_row_weight_sums(e->n, e->d_rowptr.p, e->d_w.p, e->d_wsum.p, e->stream));
+    if (rule == MH_SMOOTH_CAUCHY) {
+        HIPCHK(e->d_wq_spare.reserve((size_t)std::max(nnz, 1)));
+        HIPCHK(e->d_wsum_spare.reserve(e->n));
+        HIPCHK(e->aw_flag.reserve(1));
+        HIPCHK(hipMemsetAsync(e->aw_flag.p, 0, sizeof(int), e->stream));
+        HIPCHK(launch_arc_weights(e->pts(), e->d_rowptr.p, e->d_col.p, e->d_mult.p, rho * rho, q_max, e->d_wq_spare.p,
+                                  e->d_wsum_spare.p, e->aw_flag.p, e->stream));
+        int over = 0;
+        HIPCHK(hipMemcpyAsync(&over, e->aw_flag.p, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (over) return fail(MH_ERR_OVERFLOW, "smoothness weights: multiplicity x q, or a site's weight total, exceeds int32");
+        std::swap(e->d_wq, e->d_wq_spare);
+        std::swap(e->d_wsum, e->d_wsum_spare);
+    } else {
+        HIPCHK(e->d_wsum.reserve(e->n));
+        HIPCHK(launch_row_weight_sums(e->n, e->d_rowptr.p, e->d_mult.p, e->d_wsum.p, e->stream));
+    }
+    e->smooth_rule = rule; e->smooth_rho = rho; e->smooth_q_max = q_max;
+    e->g_w_valid = false;
     return MH_OK;
+}
+
+// ... of a graph that has just arrived, under the rule in force
+static int upload_wsum(mh_engine* e, int nnz)
+{
+    return apply_smoothness(e, nnz, e->smooth_rule, e->smooth_rho, e->smooth_q_max);
 }
 
 // host copy (fallback path) -> device
@@ -239,18 +265,19 @@ int upload_graph(mh_engine* e)
     const int n = e->n, nnz = (int)e->g_col.size();
     HIPCHK(e->d_rowptr.reserve(n + 1));
     HIPCHK(e->d_col.reserve(nnz));
-    HIPCHK(e->d_w.reserve(nnz));
+    HIPCHK(e->d_mult.reserve(nnz));
     HIPCHK(e->d_rev.reserve(nnz));
     HIPCHK(hipMemcpyAsync(e->d_rowptr.p, e->g_rowptr.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, e->stream));
     if (nnz) {
         HIPCHK(hipMemcpyAsync(e->d_col.p, e->g_col.data(), sizeof(int) * nnz, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(hipMemcpyAsync(e->d_w.p, e->g_w.data(), sizeof(int) * nnz, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->d_mult.p, e->g_mult.data(), sizeof(int) * nnz, hipMemcpyHostToDevice, e->stream));
         HIPCHK(hipMemcpyAsync(e->d_rev.p, e->g_rev.data(), sizeof(int) * nnz, hipMemcpyHostToDevice, e->stream));
     }
     HIPCHK(hipStreamSynchronize(e->stream));
     int rc = upload_order(e);
     if (rc) return rc;
-    rc = upload_wsum(e);
+    e->have_graph = false;                             // (the arrays of the graph that was resident are overwritten)
+    rc = upload_wsum(e, nnz);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     e->g_nnz = nnz;
@@ -313,12 +340,13 @@ static int device_sym_graph(mh_engine* e, const int* rowptr_dev, int stride, con
     HIPCHK(hipMemcpyAsync(&nnz, e->d_rowptr.p + n, sizeof(int), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(e->d_col.reserve((size_t)std::max(nnz, 1)));
-    HIPCHK(e->d_w.reserve((size_t)std::max(nnz, 1)));
+    HIPCHK(e->d_mult.reserve((size_t)std::max(nnz, 1)));
     HIPCHK(e->d_rev.reserve((size_t)std::max(nnz, 1)));
-    HIPCHK(launch_sym_finish(n, e->gb_start.p, e->gb_raw.p, e->gb_mult.p, e->d_rowptr.p, e->d_col.p, e->d_w.p, e->d_rev.p, e->stream));
+    HIPCHK(launch_sym_finish(n, e->gb_start.p, e->gb_raw.p, e->gb_mult.p, e->d_rowptr.p, e->d_col.p, e->d_mult.p, e->d_rev.p, e->stream));
     int rc = upload_order(e);
     if (rc) return rc;
-    rc = upload_wsum(e);
+    e->have_graph = false;                             // (the arrays of the graph that was resident are overwritten)
+    rc = upload_wsum(e, nnz);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     e->g_nnz = nnz;
@@ -491,8 +519,8 @@ int mh_set_correspondences(mh_engine* e, const double* src_xy, const double* dst
     e->n = n;
     e->have_aff = affines != nullptr;
     e->have_graph = false;
-    e->g_rowptr.clear(); e->g_col.clear(); e->g_w.clear(); e->g_rev.clear();
-    e->g_host_valid = false; e->g_nnz = 0;
+    e->g_rowptr.clear(); e->g_col.clear(); e->g_mult.clear(); e->g_w.clear(); e->g_rev.clear();
+    e->g_host_valid = false; e->g_w_valid = false; e->g_nnz = 0;
     e->cost_L = 0;
     return MH_OK;
     });
@@ -663,26 +691,75 @@ int mh_build_neighbors_radius(mh_engine* e, double radius, long long max_hits, l
     });
 }
 
+// host copy of the structure and the multiplicities (complete after the fallback build, else fetched once per graph)
+static int fetch_host_graph(mh_engine* e)
+{
+    if (e->g_host_valid) return MH_OK;
+    HIPCHK(hipSetDevice(e->device));
+    e->g_rowptr.resize((size_t)e->n + 1); e->g_col.resize(e->g_nnz); e->g_mult.resize(e->g_nnz); e->g_rev.resize(e->g_nnz);
+    HIPCHK(fetch_ints(e, e->g_rowptr.data(), e->d_rowptr.p, (size_t)e->n + 1));
+    if (e->g_nnz) {
+        HIPCHK(fetch_ints(e, e->g_col.data(), e->d_col.p, (size_t)e->g_nnz));
+        HIPCHK(fetch_ints(e, e->g_mult.data(), e->d_mult.p, (size_t)e->g_nnz));
+        HIPCHK(fetch_ints(e, e->g_rev.data(), e->d_rev.p, (size_t)e->g_nnz));
+    }
+    e->g_host_valid = true;
+    return MH_OK;
+}
+
 int mh_get_sym_graph(mh_engine* e, int* rowptr, int* col, int* w, int* nnz)
 {
     return guarded([&]() -> int {
     if (!e) return fail(MH_ERR_INVALID, "null engine");
     if (!e->have_graph) return fail(MH_ERR_NOT_SET, "neighbour graph is not set");
-    if (!e->g_host_valid) {                            // built on the device: fetch once
+    int rc = fetch_host_graph(e);
+    if (rc) return rc;
+    if (w && !e->g_w_valid) {                          // the weights in force are the device's: never the fallback build's host arrays
         HIPCHK(hipSetDevice(e->device));
-        e->g_rowptr.resize((size_t)e->n + 1); e->g_col.resize(e->g_nnz); e->g_w.resize(e->g_nnz); e->g_rev.resize(e->g_nnz);
-        HIPCHK(fetch_ints(e, e->g_rowptr.data(), e->d_rowptr.p, (size_t)e->n + 1));
-        if (e->g_nnz) {
-            HIPCHK(fetch_ints(e, e->g_col.data(), e->d_col.p, (size_t)e->g_nnz));
-            HIPCHK(fetch_ints(e, e->g_w.data(), e->d_w.p, (size_t)e->g_nnz));
-            HIPCHK(fetch_ints(e, e->g_rev.data(), e->d_rev.p, (size_t)e->g_nnz));
-        }
-        e->g_host_valid = true;
+        e->g_w.resize(e->g_nnz);
+        if (e->g_nnz) HIPCHK(fetch_ints(e, e->g_w.data(), e->w_dev(), (size_t)e->g_nnz));
+        e->g_w_valid = true;
     }
     if (nnz) *nnz = e->g_nnz;
     if (rowptr) std::copy(e->g_rowptr.begin(), e->g_rowptr.end(), rowptr);
     if (col) std::copy(e->g_col.begin(), e->g_col.end(), col);
     if (w) std::copy(e->g_w.begin(), e->g_w.end(), w);
+    return MH_OK;
+    });
+}
+
+int mh_get_sym_multiplicity(mh_engine* e, int* mult)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (!e->have_graph) return fail(MH_ERR_NOT_SET, "neighbour graph is not set");
+    int rc = fetch_host_graph(e);
+    if (rc) return rc;
+    if (mult) std::copy(e->g_mult.begin(), e->g_mult.end(), mult);
+    return MH_OK;
+    });
+}
+
+int mh_set_smoothness_weights(mh_engine* e, int rule, double rho, int q_max)
+{
+    return guarded([&]() -> int {
+    if (!e) return fail(MH_ERR_INVALID, "null engine");
+    if (rule != MH_SMOOTH_UNIFORM && rule != MH_SMOOTH_CAUCHY) return fail(MH_ERR_INVALID, "unknown smoothness rule");
+    if (rule == MH_SMOOTH_CAUCHY) {
+        if (!std::isfinite(rho) || !(rho > 0.0)) return fail(MH_ERR_INVALID, "rho must be finite and positive");
+        if (q_max < 1 || q_max > MH_SMOOTH_Q_MAX) return fail(MH_ERR_INVALID, "q_max must be in [1, 256]");
+    } else {
+        rho = 0.0; q_max = 1;                          // (not looked at)
+    }
+    if (!e->have_graph) {                              // applies to the graphs that arrive later
+        e->smooth_rule = rule; e->smooth_rho = rho; e->smooth_q_max = q_max;
+        return MH_OK;
+    }
+    int rc = enter(e);
+    if (rc) return rc;
+    rc = apply_smoothness(e, e->g_nnz, rule, rho, q_max);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
     return MH_OK;
     });
 }

@@ -197,12 +197,20 @@ struct mh_engine : ResidentBatch {                    // (e->m, e->origin, e->ha
     Epipolar epi{};
 
     // symmetric weighted graph
-    std::vector<int> g_rowptr, g_col, g_w, g_rev;   // host copy of the symmetric graph (built here by the fallback path, else fetched on demand)
+    std::vector<int> g_rowptr, g_col, g_mult, g_rev;   // host copy of the symmetric graph (built here by the fallback path, else fetched on demand)
     bool g_host_valid = false;
+    std::vector<int> g_w;                    // host copy of the weights in force (mh_get_sym_graph), fetched on demand:
+    bool g_w_valid = false;                  //   every change of the graph or of the rule makes it stale
     int g_nnz = 0;
     DevBuf<int> gb_deg, gb_start, gb_cursor, gb_raw, gb_mult, gb_uniq, gb_info, gb_hits_rp, gb_hits_col;   // graph.hip scratch
     int order_n = -1;                        // d_order holds the solver's site order for this many sites
-    DevBuf<int> d_rowptr, d_col, d_w, d_rev;
+    DevBuf<int> d_rowptr, d_col, d_mult, d_rev;   // (d_mult: the hit multiplicities, what launch_sym_finish / upload_graph fill)
+    // mh_set_smoothness_weights (sticky): under MH_SMOOTH_CAUCHY d_wq holds mult x q and is what the labeling reads; under
+    // MH_SMOOTH_UNIFORM the labeling reads d_mult itself.  k_arc_weights writes the spare pair, which is swapped in on success.
+    int smooth_rule = MH_SMOOTH_UNIFORM, smooth_q_max = 1;
+    double smooth_rho = 0.0;
+    DevBuf<int> d_wq, d_wq_spare, d_wsum_spare, aw_flag;
+    const int* w_dev() const { return smooth_rule == MH_SMOOTH_CAUCHY ? d_wq.p : d_mult.p; }
 
     // model set (its record: ResidentBatch)
     DevBuf<double> H, H_one;

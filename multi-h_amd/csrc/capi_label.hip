@@ -62,7 +62,7 @@ int do_expand(mh_engine* e, const int* init_dev, long long* energy, int* cycles)
     if (e->cost_L != e->m + 1) return fail(MH_ERR_NOT_SET, "data cost is stale; call mh_data_cost first");
     int rc = ensure_expand_work(e);
     if (rc) return rc;
-    Graph g{ e->d_rowptr.p, e->d_col.p, e->d_w.p, e->d_rev.p, e->n, e->g_nnz, e->d_order.p, e->d_wsum.p };
+    Graph g{ e->d_rowptr.p, e->d_col.p, e->w_dev(), e->d_rev.p, e->n, e->g_nnz, e->d_order.p, e->d_wsum.p };
     // The solver launch synchronises through a grid barrier, so it must be resident as a whole: one 512-thread workgroup
     // per CU at most (what the occupancy query admits for this kernel is checked once per engine, solve_grid_limit).
     // One process per GPU — the deployment — always is.  Engines of several processes that share a GPU can keep each
@@ -594,7 +594,7 @@ int mh_merge_deltas(mh_engine* e, const int* labels, const int* pairs, int npair
     HIPCHK(e->me_H.reserve(9 * np)); HIPCHK(e->me_out.reserve(5 * np));
     HIPCHK(hipMemcpyAsync(e->me_labels.p, labels, sizeof(int) * e->n, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->me_pairs.p, pairs, sizeof(int) * 2 * np, hipMemcpyHostToDevice, e->stream));
-    const Graph g{ e->d_rowptr.p, e->d_col.p, e->d_w.p, e->d_rev.p, e->n, e->g_nnz, e->d_order.p, e->d_wsum.p };
+    const Graph g{ e->d_rowptr.p, e->d_col.p, e->w_dev(), e->d_rev.p, e->n, e->g_nnz, e->d_order.p, e->d_wsum.p };
     HIPCHK(launch_merge_pairs(e->pts(), e->me_labels.p, e->H.p, e->me_pairs.p, npairs, g, e->lambda, e->thr_H * e->thr_H, e->me_H.p,
                               e->me_out.p, e->me_status.p, e->stream, e->data_term == MH_DATA_TERM_RISING, e->route_symmetric()));
     std::vector<double> h_H(H_out ? 9 * np : 0);
@@ -625,7 +625,7 @@ int mh_labeling_energy(mh_engine* e, const int* labels, long long* energy, long 
     HIPCHK(e->me_labels.reserve(e->n)); HIPCHK(e->me_out.reserve(2));
     HIPCHK(hipMemcpyAsync(e->me_labels.p, labels, sizeof(int) * e->n, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemsetAsync(e->me_out.p, 0, sizeof(long long) * 2, e->stream));
-    const Graph g{ e->d_rowptr.p, e->d_col.p, e->d_w.p, e->d_rev.p, e->n, e->g_nnz, e->d_order.p, e->d_wsum.p };
+    const Graph g{ e->d_rowptr.p, e->d_col.p, e->w_dev(), e->d_rev.p, e->n, e->g_nnz, e->d_order.p, e->d_wsum.p };
     HIPCHK(launch_labeling_energy(e->pts(), e->me_labels.p, e->H.p, g, e->lambda, e->thr_H * e->thr_H,
                                   reinterpret_cast<unsigned long long*>(e->me_out.p), e->stream, e->data_term == MH_DATA_TERM_RISING,
                                   e->route_symmetric()));
@@ -696,7 +696,7 @@ int mh_drop_deltas(mh_engine* e, const int* labels, const int* cand, int ncand, 
     const size_t nc = (size_t)ncand, n = (size_t)e->n;
     HIPCHK(e->lc_cand.reserve(nc)); HIPCHK(e->me_status.reserve(nc)); HIPCHK(e->me_out.reserve(5 * nc));
     HIPCHK(hipMemcpyAsync(e->lc_cand.p, cand, sizeof(int) * nc, hipMemcpyHostToDevice, e->stream));
-    const Graph g{ e->d_rowptr.p, e->d_col.p, e->d_w.p, e->d_rev.p, e->n, e->g_nnz, e->d_order.p, e->d_wsum.p };
+    const Graph g{ e->d_rowptr.p, e->d_col.p, e->w_dev(), e->d_rev.p, e->n, e->g_nnz, e->d_order.p, e->d_wsum.p };
     HIPCHK(launch_drop_labels(e->pts(), e->me_labels.p, e->H.p, e->lc_cand.p, ncand, e->lc_alt.p, e->lc_cost.p, g, e->lambda,
                               e->thr_H * e->thr_H, e->me_out.p, e->me_status.p, e->stream, e->data_term == MH_DATA_TERM_RISING,
                               e->route_symmetric()));

@@ -13,6 +13,8 @@
 //   k_scan          final row pointers
 //   k_sym_compact   rows to their final place
 //   k_sym_rev       reverse-arc index by binary search in the neighbour's (sorted) row
+//   k_row_wsum      per-site weight totals of the multiplicities (MH_SMOOTH_UNIFORM), or
+//   k_arc_weights   multiplicity x distance weight per arc and the totals of those (MH_SMOOTH_CAUCHY)
 //
 // Entries land in a raw row in any order and are sorted there, so the result is deterministic.  The input is either
 // a CSR (rowptr != null) or a dense n x stride table (k-NN output); a column of -1 is "no hit".
@@ -215,9 +217,54 @@ k_row_wsum(int n, const int* __restrict__ rowptr, const int* __restrict__ w, int
     if (sub == 0) wsum[i] = t > 0x7fffffffll ? 0x7fffffff : (int)t;
 }
 
+// MH_SMOOTH_CAUCHY (include/multih_hip.h, mh_set_smoothness_weights): w[k] = mult[k] * q(d), d the float32 squared distance of
+// the arc's two sites in k_hits_filter's arithmetic, q = max(1, round(q_max * r2 / (r2 + d))) in double.  Sixteen lanes walk a
+// row as in the kernels above: the site's own coordinates are read once per lane, the partner's four are gathered (rows are
+// sorted by column, and k-NN partners lie close in the arrays only by accident: these are the pass's scattered reads, 32 B an
+// arc, nothing is staged in LDS).  The same pass folds the row's int64 sum into wsum, so it takes k_row_wsum's place under
+// this rule.  *overflow is raised when a product or a row sum leaves int32 (the stored value is then clamped and the caller
+// throws the buffers away).  d infinite gives t = 0, d NaN gives a NaN qf: both fail `qf >= 1.0` and take q = 1.
+__global__ void __launch_bounds__(256)
+k_arc_weights(Points p, const int* __restrict__ rowptr, const int* __restrict__ col, const int* __restrict__ mult,
+              double r2, int q_max, int* __restrict__ w, int* __restrict__ wsum, int* __restrict__ overflow)
+{
+    const int i = blockIdx.x * (256 / GL) + threadIdx.x / GL;
+    const int sub = threadIdx.x % GL;
+    if (i >= p.n) return;
+    const float xi = (float)p.x1[i], yi = (float)p.y1[i], zi = (float)p.x2[i], wi = (float)p.y2[i];
+    long long t = 0;
+    bool over = false;
+    for (int k = rowptr[i] + sub; k < rowptr[i + 1]; k += GL) {
+        const int j = col[k];
+        const float dx = xi - (float)p.x1[j], dy = yi - (float)p.y1[j];
+        const float dz = zi - (float)p.x2[j], dw = wi - (float)p.y2[j];
+        const float d = ((dx * dx + dy * dy) + dz * dz) + dw * dw;
+        const double qf = (double)q_max * (r2 / (r2 + (double)d));
+        const int q = qf >= 1.0 ? (int)round(qf) : 1;
+        const long long prod = (long long)mult[k] * q;
+        over = over || prod > 0x7fffffffll;
+        w[k] = prod > 0x7fffffffll ? 0x7fffffff : (int)prod;
+        t += prod;
+    }
+#pragma unroll
+    for (int m = GL / 2; m >= 1; m >>= 1) t += __shfl_xor(t, m, GL);
+    over = over || t > 0x7fffffffll;
+    if (over) atomicExch(overflow, 1);
+    if (sub == 0) wsum[i] = t > 0x7fffffffll ? 0x7fffffff : (int)t;
+}
+
 hipError_t launch_row_weight_sums(int n, const int* rowptr, const int* w, int* wsum, hipStream_t s)
 {
     hipLaunchKernelGGL(k_row_wsum, dim3((n + 256 / GL - 1) / (256 / GL)), dim3(256), 0, s, n, rowptr, w, wsum);
+    return hipGetLastError();
+}
+
+// *overflow must have been cleared on the stream
+hipError_t launch_arc_weights(const Points& p, const int* rowptr, const int* col, const int* mult, double r2, int q_max, int* w,
+                              int* wsum, int* overflow, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_arc_weights, dim3((p.n + 256 / GL - 1) / (256 / GL)), dim3(256), 0, s, p, rowptr, col, mult, r2, q_max,
+                       w, wsum, overflow);
     return hipGetLastError();
 }
 

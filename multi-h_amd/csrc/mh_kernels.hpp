@@ -492,6 +492,10 @@ hipError_t launch_sym_build(int n, const int* rowptr, int stride, const int* col
                             int* mult, int* uniq, int* out_rowptr /* n+1 */, int* info, hipStream_t s);
 // wsum[i] = sum of w over row i
 hipError_t launch_row_weight_sums(int n, const int* rowptr, const int* w, int* wsum, hipStream_t s);
+// MH_SMOOTH_CAUCHY: w[k] = mult[k] * q(distance of the arc's sites) and wsum[i] = sum of w over row i in one pass;
+// *overflow (cleared by the caller) is raised when a product or a row sum leaves int32
+hipError_t launch_arc_weights(const Points& p, const int* rowptr, const int* col, const int* mult, double r2, int q_max, int* w,
+                              int* wsum, int* overflow, hipStream_t s);
 hipError_t launch_sym_finish(int n, const int* start, const int* raw, const int* mult, const int* rowptr, int* col, int* w,
                              int* rev, hipStream_t s);
 

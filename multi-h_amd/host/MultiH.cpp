@@ -93,6 +93,7 @@ MultiH::EngineCaps multih::detail::LinkedEngineCaps()
     c.compat_dlt = mh_compat_dlt_medians;
     c.energy_merge = mh_merge_deltas && mh_labeling_energy;
     c.drop_deltas = mh_drop_deltas;
+    c.smoothness_weights = mh_set_smoothness_weights;
     return c;
 }
 
@@ -442,6 +443,17 @@ bool MultiH::PlanRun(bool points_only, const EngineCaps& have, RunPlan& out, std
     // the data term of the labeling (an unknown value is the engine's to refuse)
     if (!Offers(have.data_term, data_term != DATA_TERM_REFERENCE, "Error: the engine library has no selectable data term (mh_set_data_term)\n", error))
         return false;
+    // the weights of the smoothness term
+    if (smoothness_rule != SMOOTHNESS_UNIFORM && smoothness_rule != SMOOTHNESS_CAUCHY)
+        return Refuse(error) << "Error: unknown smoothness rule " << smoothness_rule << " (SMOOTHNESS_UNIFORM or SMOOTHNESS_CAUCHY)\n";
+    if (smoothness_rule == SMOOTHNESS_CAUCHY) {
+        if (!std::isfinite(smoothness_rho) || !(smoothness_rho > 0.0) || smoothness_q_max < 1 || smoothness_q_max > MH_SMOOTH_Q_MAX)
+            return Refuse(error) << "Error: SetSmoothnessWeights: rho = " << smoothness_rho << ", q_max = " << smoothness_q_max
+                                 << " (rho finite and > 0, q_max in [1, " << MH_SMOOTH_Q_MAX << "])\n";
+        if (!Offers(have.smoothness_weights, true, "Error: the engine library has no distance-weighted smoothness (mh_set_smoothness_weights)\n", error))
+            return false;
+        out.smoothness_rule = MH_SMOOTH_CAUCHY; out.smoothness_rho = smoothness_rho; out.smoothness_q_max = smoothness_q_max;
+    }
     // the error of the whole route
     if (residual != RESIDUAL_FORWARD && residual != RESIDUAL_SYMMETRIC)
         return Refuse(error) << "Error: unknown residual " << residual << " (RESIDUAL_FORWARD or RESIDUAL_SYMMETRIC)\n";
@@ -524,6 +536,9 @@ bool MultiH::ConfigureEngine(const RunPlan& p)
 {
     if (caps.point_only && !Check(mh_set_estimator(engine, p.est), "mh_set_estimator")) return false;
     if (caps.data_term && !Check(mh_set_data_term(engine, data_term), "mh_set_data_term")) return false;
+    if (caps.smoothness_weights &&
+        !Check(mh_set_smoothness_weights(engine, p.smoothness_rule, p.smoothness_rho, p.smoothness_q_max), "mh_set_smoothness_weights"))
+        return false;
     if (caps.residual_route && (!Check(mh_set_residual_mode(engine, p.residual_mode), "mh_set_residual_mode") ||
                                 !Check(mh_set_residual_scope(engine, p.residual_scope), "mh_set_residual_scope")))
         return false;

@@ -153,6 +153,20 @@ public:
     // (the loop's energy is the engine's).  Any other value makes Process() fail with a message.
     enum { DATA_TERM_REFERENCE = 0, DATA_TERM_RISING = 1 };
     void SetDataTerm(int t) { data_term = t; }
+    // The weight of a neighbour pair in the smoothness term (mh_set_smoothness_weights, include/multih_hip.h, which defines the
+    // rule): SMOOTHNESS_UNIFORM pays the Potts price round(100 lambda) times the pair's hit multiplicity whatever the distance
+    // (the reference's smoothnessEnergy; default; rho_px and q_max are not looked at).  SMOOTHNESS_CAUCHY multiplies that by
+    // q = max(1, round(q_max rho^2 / (rho^2 + d))), d the squared distance of the two correspondences in (x1,y1,x2,y2): q_max
+    // for coincident sites, q_max / 2 at distance rho_px, 1 far away — PEARL's distance-weighted smoothness with a profile
+    // that has an exact definition.  A near pair then costs q_max times what it cost; lambda scales both terms of the energy,
+    // so SetSmoothnessWeights(CAUCHY, rho, q) with lambda / sqrt(q) keeps the short-range balance.  Nothing is rescaled here.
+    // Process() applies it to its engine on every call — every rank of a sharded run does, the labeling is replicated —, with
+    // explicit neighbours (SetNeighbours) and under all three neighbourhood modes.  Nothing on the host evaluates the term:
+    // the LabelingStep, and the merges and drops of MERGE_ENERGY and SetLabelCost (mh_labeling_energy, mh_merge_deltas,
+    // mh_drop_deltas), pick the weights up through the engine.  CAUCHY with rho_px not finite or <= 0, q_max outside
+    // [1, 256], or another rule makes Process() fail with a message.
+    enum { SMOOTHNESS_UNIFORM = 0, SMOOTHNESS_CAUCHY = 1 };
+    void SetSmoothnessWeights(int rule, double rho_px, int q_max = 16) { smoothness_rule = rule; smoothness_rho = rho_px; smoothness_q_max = q_max; }
     // The error the whole route measures (mh_set_residual_mode with mh_set_residual_scope(MH_RESIDUAL_SCOPE_ROUTE),
     // include/multih_hip.h): RESIDUAL_FORWARD is the reference's one-way transfer error |H p1 - p2|^2 (default);
     // RESIDUAL_SYMMETRIC adds the backward term |adj(H) p2 - p1|^2.  Under it the route scores and selects its proposals,
@@ -373,6 +387,7 @@ public:
         bool compat_dlt = false;                  // (mh_compat_dlt_medians)
         bool energy_merge = false;                // (mh_merge_deltas, mh_labeling_energy)
         bool drop_deltas = false;                 // (mh_drop_deltas)
+        bool smoothness_weights = false;          // (mh_set_smoothness_weights)
     };
     // What one Process() call derives from the settings, made by PlanRun before anything touches an engine.
     struct RunPlan {
@@ -386,6 +401,8 @@ public:
         int haf_members = 0;
         long long label_cost_beta = 0;            // SetLabelCost in energy units
         int residual_mode = 0, residual_scope = 0;          // MH_RESIDUAL_*, MH_RESIDUAL_SCOPE_*
+        int smoothness_rule = 0, smoothness_q_max = 1;      // MH_SMOOTH_*; rho and q_max as the engine gets them (0 and 1 under UNIFORM)
+        double smoothness_rho = 0.0;
         // the reweighted rounds of the loop's estimator: 0 unless est is the N-point DLT; c2 is the fixed rule's squared scale
         int estimator_reweight_rounds = 0;
         double estimator_reweight_c2 = 0.0;
@@ -431,6 +448,8 @@ protected:
     bool epipolar_free = false;
     int data_term = DATA_TERM_REFERENCE;
     int residual = RESIDUAL_FORWARD;
+    int smoothness_rule = SMOOTHNESS_UNIFORM, smoothness_q_max = 16;      // SetSmoothnessWeights
+    double smoothness_rho = 0.0;
     int tail_score = TAIL_SCORE_COUNT;
     int tail_refit = 0;
     int tail_polish = 0, model_polish = 0;

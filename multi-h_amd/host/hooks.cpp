@@ -43,6 +43,8 @@ struct HookSettings {
     int compat_fit = 0, compat_trials = 501;                  // (COMPAT_FIT_3PT, 501, 0) is the class's default
     double compat_limit_scale = 0.0;
     int selection_score = -1;
+    int smoothness_rule = -1, smoothness_q_max = 16;          // mhh_set_smoothness_weights
+    double smoothness_rho = 0.0;
     int compat_fits_on_engine = 1;                            // mhh_compatibility_medians_on_engine: 1 = the fits on the device too (as Process() runs it since r06), 0 = on the host
 
     void Apply(MultiH& mh) const;
@@ -59,6 +61,7 @@ void HookSettings::Apply(MultiH& mh) const
     if (proposal_source != 0) mh.SetProposalSource(proposal_source, proposal_haf_members, proposal_haf_stride);
     if (fund_metric >= 0) mh.SetFundamentalMetric(fund_metric);
     if (data_term >= 0) mh.SetDataTerm(data_term);
+    if (smoothness_rule >= 0) mh.SetSmoothnessWeights(smoothness_rule, smoothness_rho, smoothness_q_max);
     if (merge_mode >= 0) mh.SetMergeMode(merge_mode);
     if (label_cost != 0.0) mh.SetLabelCost(label_cost);
     if (residual >= 0) mh.SetResidual(residual);
@@ -145,6 +148,11 @@ MHH_API void mhh_set_fundamental_estimator(int mode, int max_samples, double con
 MHH_API void mhh_set_merge_mode(int mode) { g_set.merge_mode = mode; }
 MHH_API void mhh_set_label_cost(double points) { g_set.label_cost = points; }
 MHH_API void mhh_set_data_term(int term) { g_set.data_term = term; }
+// MultiH::SetSmoothnessWeights (rule < 0: the class default again)
+MHH_API void mhh_set_smoothness_weights(int rule, double rho_px, int q_max)
+{
+    g_set.smoothness_rule = rule; g_set.smoothness_rho = rho_px; g_set.smoothness_q_max = q_max;
+}
 MHH_API void mhh_set_residual(int residual) { g_set.residual = residual; }
 MHH_API void mhh_set_tail_score(int score) { g_set.tail_score = score; }
 MHH_API void mhh_set_tail_refit(int iterations) { g_set.tail_refit = iterations; }

@@ -32,6 +32,10 @@
 //                                measured 256); "Compatibility check (4-point trials) .. clusters removed" reports it
 //                  [--data-term reference|rising]   the data term of the labeling (MultiH::SetDataTerm): reference, the default, is
 //                                the reference's dataEnergy (the cost falls as the fit gets worse); rising drops its `1.0 -`
+//                  [--smoothness uniform|cauchy:RHO[:QMAX]]   the weight of a neighbour pair in the smoothness term
+//                                (MultiH::SetSmoothnessWeights): uniform, the default, is the reference's (hit multiplicity);
+//                                cauchy multiplies it by max(1, round(QMAX RHO^2 / (RHO^2 + d))), d the pair's squared distance in
+//                                (x1,y1,x2,y2), RHO in pixels, QMAX in [1, 256] (default 16)
 //                  [--merge meanshift|energy]   how MergingStep decides (MultiH::SetMergeMode): meanshift, the default, is the
 //                                reference's rule; energy joins two labels only where the union with its own N-point refit lowers
 //                                the labeling's energy (mh_merge_deltas), and the LabelingStep behind it starts warm; "Energy merges:"
@@ -152,7 +156,7 @@ int main(int argc, char** argv)
         std::cerr << "usage: multih_harness <in_corr.txt> <out_result.txt> [--epipolar file] [--thrF v] [--thrH v] "
                      "[--locality v] [--lambda v] [--min-inliers n] [--hypotheses n] [--max-models n] [--seed n] "
                      "[--iterations n] [--neighbourhood knn|radius|approx] [--load-filter px] [--f-metric opencv|sampson] [--f-estimator ls8|minimal] "
-                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--compat-fit dlt[:trials[:limit_scale]]] [--data-term reference|rising] [--merge meanshift|energy] [--label-cost P] [--residual forward|symmetric] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--reweight n[:scale]] [--estimator-reweight n[:scale]] [--reweight-auto n[:kappa]] [--estimator-reweight-auto n[:kappa]] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
+                     "[--stages file] [--points] [--estimator haf|3pt|dlt] [--no-epipolar] [--compat-fit dlt[:trials[:limit_scale]]] [--data-term reference|rising] [--smoothness uniform|cauchy:RHO[:QMAX]] [--merge meanshift|energy] [--label-cost P] [--residual forward|symmetric] [--tail-score count|msac] [--tail-refit N] [--tail-polish N] [--polish N] [--reweight n[:scale]] [--estimator-reweight n[:scale]] [--reweight-auto n[:kappa]] [--estimator-reweight-auto n[:kappa]] [--sampler uniform|local[:k[:u]]] [--proposals dlt|haf[:members[:stride]]|3pt] [--ranks n]\n";
         return 2;
     }
     double thrF = 2.6, thrH = 2.2, locality = 0.005, lambda = 0.5;     // M/main.cpp:55-59
@@ -167,6 +171,8 @@ int main(int argc, char** argv)
     int estimator = MultiH::ESTIMATOR_HAF;
     int data_term = MultiH::DATA_TERM_REFERENCE;
     int residual = MultiH::RESIDUAL_FORWARD;
+    int smoothness_rule = MultiH::SMOOTHNESS_UNIFORM, smoothness_q_max = 16;
+    double smoothness_rho = 0.0;
     int merge_mode = MultiH::MERGE_MEAN_SHIFT;
     double label_cost = 0.0;
     int tail_score = MultiH::TAIL_SCORE_COUNT;
@@ -197,6 +203,15 @@ int main(int argc, char** argv)
             if (std::string(v) == "reference") data_term = MultiH::DATA_TERM_REFERENCE;
             else if (std::string(v) == "rising") data_term = MultiH::DATA_TERM_RISING;
             else { std::cerr << "--data-term: reference or rising\n"; return 2; }
+        }
+        else if (k == "--smoothness") {
+            const std::string sv(v);
+            char tail = 0;
+            if (sv == "uniform") smoothness_rule = MultiH::SMOOTHNESS_UNIFORM;
+            else if (std::sscanf(v, "cauchy:%lf:%d%c", &smoothness_rho, &smoothness_q_max, &tail) == 2 ||
+                     (smoothness_q_max = 16, std::sscanf(v, "cauchy:%lf%c", &smoothness_rho, &tail) == 1))
+                smoothness_rule = MultiH::SMOOTHNESS_CAUCHY;
+            else { std::cerr << "--smoothness: uniform or cauchy:RHO[:QMAX]\n"; return 2; }
         }
         else if (k == "--merge") {
             if (std::string(v) == "meanshift") merge_mode = MultiH::MERGE_MEAN_SHIFT;
@@ -498,6 +513,7 @@ int main(int argc, char** argv)
     multiH->SetEpipolarFree(no_epipolar);
     multiH->SetCompatibilityFit(compat_fit, compat_trials, compat_limit_scale);
     multiH->SetDataTerm(data_term);
+    multiH->SetSmoothnessWeights(smoothness_rule, smoothness_rho, smoothness_q_max);
     multiH->SetMergeMode(merge_mode);
     multiH->SetLabelCost(label_cost);
     multiH->SetResidual(residual);

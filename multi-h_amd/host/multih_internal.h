@@ -50,6 +50,8 @@
 #pragma weak mh_merge_deltas
 #pragma weak mh_labeling_energy
 #pragma weak mh_drop_deltas
+// the distance-weighted smoothness (SetSmoothnessWeights)
+#pragma weak mh_set_smoothness_weights
 
 namespace multih {
 namespace detail {

@@ -83,7 +83,7 @@ def _host():
     return C.CDLL(os.path.join(os.path.dirname(mh.LIB_PATH), "libmultih_host.so"))
 
 
-def run(route, corr, F, e2, seed=1234, hypotheses=20000, knn=0, approx=None):
+def run(route, corr, F, e2, seed=1234, hypotheses=20000, knn=0, approx=None, lam=0.5):
     host = _host()
     host.mhh_set_neighbourhood(int(knn), C.c_double(0.0))      # 0 = the class default (16 nearest hits within 1 / locality)
     # approx = (trees, checks): MultiH::SetNeighbourApprox — the reference's radiusMatch as FLANN's default search answers it
@@ -97,7 +97,7 @@ def run(route, corr, F, e2, seed=1234, hypotheses=20000, knn=0, approx=None):
     Fc, e2c = np.ascontiguousarray(F.reshape(9)), np.ascontiguousarray(e2)
     host.mhh_set_post_filter(1)
     k = host.mhh_run_process(src.ctypes.data_as(dp), dst.ctypes.data_as(dp), aff.ctypes.data_as(dp), n, Fc.ctypes.data_as(dp),
-                             e2c.ctypes.data_as(dp), C.c_double(2.6), C.c_double(2.2), C.c_double(0.005), C.c_double(0.5), 20,
+                             e2c.ctypes.data_as(dp), C.c_double(2.6), C.c_double(2.2), C.c_double(0.005), C.c_double(lam), 20,
                              C.c_ulonglong(seed), hypotheses, 32, 0, None, 0, labels.ctypes.data_as(C.POINTER(C.c_int)),
                              Hout.ctypes.data_as(dp), 256, C.byref(it), C.byref(en), None, 0, -1 if route == "stable_sets" else 4)
     C.CDLL(None).fflush(None)
@@ -119,7 +119,7 @@ def front_half(pts, seed=1234):
     return idx, np.ascontiguousarray(refined[idx]), F, e2
 
 
-def harness_route(pts, route, seed, load_filter=2.0, metric=1, hypotheses=20000):
+def harness_route(pts, route, seed, load_filter=2.0, metric=1, hypotheses=20000, lam=0.5):
     """The reference's caller on the RAW rows, stage by stage, as multih_harness runs it since r06 (host/main.cpp):
     LoadPointsFromFile's filter (M/main.cpp:399-409: F-RANSAC at `load_filter` px, 0 = off) through
     multih::FilterCorrespondencesByEpipolarGeometry, then Process() WITHOUT a given F (its own RANSAC at 2.6 px,
@@ -157,7 +157,7 @@ def harness_route(pts, route, seed, load_filter=2.0, metric=1, hypotheses=20000)
     Hout = np.zeros((256, 9))
     it, en = C.c_int(0), C.c_double(0)
     k = host.mhh_run_process(s2.ctypes.data_as(dp), d2.ctypes.data_as(dp), a2.ctypes.data_as(dp), len(sub), None, None,
-                             C.c_double(2.6), C.c_double(2.2), C.c_double(0.005), C.c_double(0.5), 20, C.c_ulonglong(seed), hypotheses, 32, 0,
+                             C.c_double(2.6), C.c_double(2.2), C.c_double(0.005), C.c_double(lam), 20, C.c_ulonglong(seed), hypotheses, 32, 0,
                              None, 0, labels.ctypes.data_as(C.POINTER(C.c_int)), Hout.ctypes.data_as(dp), 256, C.byref(it), C.byref(en),
                              None, 0, -1 if route == "stable_sets" else 4)
     host.mhh_set_fundamental_metric(-1)
